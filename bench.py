@@ -24,7 +24,20 @@ Extra leg `weak` (N > 1; BASELINE config 4): rank r compresses bytes [r GiB,
 (r+1) GiB) of the seed-4 rand stream, each rank's segment checked against the
 reference's, the N segments gathered to rank 0.
 
-    python bench.py                      # N=1, defaults
+A plain run does only what the headline figure needs: set up the main leg, warm up, time
+--steps steps, write --dump-outputs if asked, print the result line (metric, value, unit,
+ms_per_step, ...).  Everything else the benchmark measures or checks runs under --full: the
+per-kernel stage times and rooflines, the reference digests, the cold first call, the GPU
+decoder, the host-to-host path, the extra legs, the weak leg, the CPU baselines, the lz78
+codec and the change-of-kind transition (each still has its own --no-... switch there).
+
+--dump-outputs DIR writes what the last timed step left (rank 0), as float64 .npy files:
+out_bytes (the stream's length), stream_sums (two checksums per 64 KiB of the whole stream),
+stream_sample_offsets and, in float32, stream_sample (the bytes of a fixed, seeded set of
+4 KiB pieces).  The inputs are seeded, so two builds can be compared file by file.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5      # N=1, the headline only
+    python bench.py --full                               # every leg, check and baseline
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
         --master-port 29500 bench.py --gpus 8
 """
@@ -124,6 +137,39 @@ def timed(fn, steps, dist, dev):
     if dist:
         dist.barrier()
     return max_over_ranks(time.perf_counter() - t0, dist, dev)
+
+
+def dump_outputs(path, stream, total):
+    """--dump-outputs: the compressed stream a caller of the timed path receives (stream[:total],
+    on the device) as .npy files of about 17 MB together, the same files for the same bytes:
+      out_bytes.npy              float64 [1]      the stream's length
+      stream_sums.npy            float64 [S, 2]   per 64 KiB segment: the sum of its bytes and the sum
+                                                  of byte x (1 + offset in the segment); every byte counts
+      stream_sample_offsets.npy  float64 [P]      start of each sampled piece (seeded, sorted)
+      stream_sample.npy          float32 [P, 4096] the bytes of those pieces (a short stream: all of it)"""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    seg, piece, npieces, chunk = 1 << 16, 4096, 1024, 1 << 26
+    np.save(os.path.join(path, "out_bytes.npy"), np.array([total], dtype=np.float64))
+    w = torch.arange(1, seg + 1, dtype=torch.int64, device=stream.device)
+    sums = [torch.zeros((0, 2), dtype=torch.int64)]
+    for lo in range(0, total, chunk):
+        part = stream[lo:min(lo + chunk, total)].to(torch.int64)
+        part = torch.nn.functional.pad(part, (0, -part.numel() % seg)).view(-1, seg)
+        sums.append(torch.stack([part.sum(1), (part * w).sum(1)], 1).cpu())
+        del part
+    np.save(os.path.join(path, "stream_sums.npy"), torch.cat(sums).numpy().astype(np.float64))
+    if total <= piece * npieces:
+        starts = torch.arange(0, max(total, 1), piece, dtype=torch.int64)
+    else:
+        g = torch.Generator().manual_seed(0x5A17)
+        starts = torch.sort(torch.randint(0, total - piece + 1, (npieces,), generator=g, dtype=torch.int64)).values
+    idx = (starts[:, None] + torch.arange(piece, dtype=torch.int64)[None, :]).to(stream.device)
+    sample = torch.where(idx < total, stream[idx.clamp(max=max(total - 1, 0))], 0) if total else idx * 0
+    np.save(os.path.join(path, "stream_sample_offsets.npy"), starts.numpy().astype(np.float64))
+    np.save(os.path.join(path, "stream_sample.npy"), sample.cpu().numpy().astype(np.float32))
 
 
 def setup_leg(kind, seed, block, args, rank, world, dev, scaling, n_global, share0, concat, main_leg):
@@ -311,9 +357,17 @@ def run_leg(kind, seed, block, args, rank, world, dev, dist, profile_stages, sca
     step()   # validates the call, creates the communicators
     for _ in range(args.warmup):
         step()
+    def dump():   # --dump-outputs: what the last timed step left, before anything else runs
+        if main_leg and args.dump_outputs and rank == 0:
+            total = state["total"] if concat != "none" else (ctx.read_out_len() if n else 0)
+            dump_outputs(args.dump_outputs, d_out if concat != "allgather" else whole, total)
+
     # compress only (device-resident, no exchange): K steps back to back, then the per-kernel hipEvent
-    # times from K more steps outside the timed region (their per-step event reads synchronise)
-    dt_c = timed(compress, args.steps, dist, dev)
+    # times from K more steps outside the timed region (their per-step event reads synchronise).
+    # At N = 1 it is the timed step itself; at N > 1 it is a measurement of its own (--full)
+    dt_c = timed(compress, args.steps, dist, dev) if concat == "none" or args.full else None
+    if concat == "none":
+        dump()
     stage_sum = {}
     if profile_stages and n:
         ctx.set_profiling(True)
@@ -325,18 +379,22 @@ def run_leg(kind, seed, block, args, rank, world, dev, dist, profile_stages, sca
     seg_len = ctx.read_out_len() if n else 0
     # the whole job, K steps
     dt = timed(step, args.steps, dist, dev) if concat != "none" else dt_c
+    if concat != "none":
+        dump()
     total = state.get("total", seg_len)
     res = {
         "kind": kind, "block_bytes": block, "scaling": scaling, "global_bytes": n_global, "bytes_this_rank": n,
         "out_bytes": total, "ratio": total / max(n_global, 1), "concat": CONCAT_FORMS.get(concat, concat),
         "seconds": dt, "ms_per_step": dt / args.steps * 1e3, "value": n_global * args.steps / dt / 1e6,
-        "compress_only": {"value": n_global * args.steps / dt_c / 1e6, "ms_per_step": dt_c / args.steps * 1e3,
-                          "note": "device-resident compress of every rank's shard, no exchange (max over ranks)"},
+        "compress_only": dt_c and {
+            "value": n_global * args.steps / dt_c / 1e6, "ms_per_step": dt_c / args.steps * 1e3,
+            "note": "device-resident compress of every rank's shard, no exchange (max over ranks)"},
         "gen_s": gen_s, "stages_ms": {k: v / args.steps for k, v in stage_sum.items()}, "host_path": host_path,
         "seg_bytes_rank0": seg_len,
     }
     if concat != "none":
-        res["concat_ms_per_step"] = res["ms_per_step"] - res["compress_only"]["ms_per_step"]
+        if dt_c:
+            res["concat_ms_per_step"] = res["ms_per_step"] - res["compress_only"]["ms_per_step"]
         res["concat_impl"] = (f"fcx_dist (C++, {args.fcx_dist.transport()} transport)" if args.fcx_dist is not None
                               else f"torch.distributed ({dist.get_backend()})")
         res["partition"] = {"share0_ppm": share0, "rank_bytes": rank_bytes,
@@ -357,7 +415,7 @@ def run_leg(kind, seed, block, args, rank, world, dev, dist, profile_stages, sca
     res["match_kernel"] = ctx.match_kernel() if n else None   # (the timed steps' match stage)
     if n:   # tiles per match unit in the last call (fcx_route.hip)
         res["route"] = ctx.route_stats()
-    if n and kind in COLD_LEGS and (main_leg or world == 1):
+    if args.full and n and kind in COLD_LEGS and (main_leg or world == 1):
         res["cold_call"] = cold_call(d_in, n, cap, block, dev, res["compress_only"]["ms_per_step"])
     stats = ctx.stats() if n else {"tokens": 0, "matches": 0, "lazy_evals": 0, "lazy_tiles": 0}
     res["tokens"], res["matches"] = stats["tokens"], stats["matches"]
@@ -365,10 +423,10 @@ def run_leg(kind, seed, block, args, rank, world, dev, dist, profile_stages, sca
     if not args.no_verify:
         res.update(verify(kind, seed, block, n_global, scaling, rank, world, dev, dist, d_out, whole, concat,
                           seg_len, total))
-    if concat == "pipe" and n:   # (a peer's pieces sit at their bound offsets: its own records again)
-        compress()
-        seg_len = ctx.read_out_len()
     if not args.no_decode and (main_leg or world == 1):
+        if concat == "pipe" and n:   # (a peer's pieces sit at their bound offsets: its own records again)
+            compress()
+            seg_len = ctx.read_out_len()
         res["decode"] = decode_leg(d_out, seg_len, n, block, d_in, args, dev, dist, world)
     ctx.close()
     S.clear()
@@ -830,7 +888,19 @@ def main():
     ap.add_argument("--no-lz78", action="store_true", help="skip the -c lz78 codec leg")
     ap.add_argument("--no-transition", action="store_true", help="skip the rand -> text change-of-kind timing")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_latest.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: stage profile and rooflines, reference "
+                         "digests, cold call, decoder, host path, extra legs, weak leg, CPU baselines, lz78, transition")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's compressed stream (length, checksums of "
+                         "every 64 KiB, a seeded sample of its bytes) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: only what the headline figure needs
+        args.no_text = args.no_weak = args.no_cpu_baseline = args.no_decode = True
+        args.no_verify = args.no_lz78 = args.no_transition = True
+        args.host_path = False
 
     import torch
 
@@ -871,7 +941,7 @@ def main():
         if not int(flag.item()) and args.fcx_dist is not None:
             args.fcx_dist.close()
             args.fcx_dist = None
-    main_res = run_leg(args.kind, SEEDS[args.kind], args.block, args, rank, world, dev, dist, True,
+    main_res = run_leg(args.kind, SEEDS[args.kind], args.block, args, rank, world, dev, dist, args.full,
                        scaling=args.scaling, main_leg=True)
     legs = {}
     for name in ([] if args.no_text else [x for x in args.legs.split(",") if x]):
@@ -887,7 +957,7 @@ def main():
     if rank == 0:
         pmc = load_pmc(args.pmc)
         n = main_res["bytes_this_rank"]
-        roof = roofline(main_res, args.kind if args.block == 1 << 20 else None, pmc)
+        roof = roofline(main_res, args.kind if args.block == 1 << 20 else None, pmc) if args.full else None
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.kind, SEEDS[args.kind], args.block)
@@ -899,12 +969,14 @@ def main():
             "metric": METRIC, "value": main_res["value"], "unit": "MB/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u8",
+            "full": args.full,
             "data": "synthetic: glibc rand()%256 seed 4 (SURVEY.md §8(d)); the 1 GiB input is SURVEY's HL-rand "
-                    "(= the first GiB of BASELINE config 4); extra legs: text = enwik-style generator seed 3 at "
-                    "1 MiB (HL-text) and 256 KiB blocks (C3), c2 = rand seed 2, 64 MiB at 64 KiB blocks (config 2), zeros "
-                    "and runs seed 5 (config 5), dna = "
-                    "'ACGT'[rand()%4] seed 6, mix = 1 MiB blocks cycling rand / text / runs / dna (every match "
-                    "unit in one call)",
+                    "(= the first GiB of BASELINE config 4)" + (
+                        "; extra legs: text = enwik-style generator seed 3 at "
+                        "1 MiB (HL-text) and 256 KiB blocks (C3), c2 = rand seed 2, 64 MiB at 64 KiB blocks (config 2), "
+                        "zeros and runs seed 5 (config 5), dna = "
+                        "'ACGT'[rand()%4] seed 6, mix = 1 MiB blocks cycling rand / text / runs / dna (every match "
+                        "unit in one call)" if args.full else ""),
             "config": {"workload": f"{args.kind} {main_res['global_bytes'] >> 20} MiB, {args.block // 1024} KiB "
                                    f"blocks, {shard_note}; step = compress + concatenation of the segments "
                                    f"into one stream ({main_res['concat']})",
@@ -967,7 +1039,8 @@ def main():
         if "transition" in line:
             summ["transition"] = {"first_text_vs_steady": round(line["transition"]["first_text_vs_steady"], 3),
                                   "stream_vs_parts": round(line["transition"]["stream_vs_parts"], 3)}
-        line["legs"] = summ
+        if args.full:
+            line["legs"] = summ
         print(json.dumps(line), flush=True)
     if dist:
         dist.barrier()

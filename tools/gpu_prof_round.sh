@@ -9,9 +9,12 @@ R=$PWD
 export TMPDIR=/tmp
 LEGS="${LEGS:-rand:rand:1048576:1024 c2:rand:65536:64 text:text:1048576:1024 c3:text:262144:1024 zeros:zeros:1048576:1024 runs:runs:1048576:1024 dna:dna:1048576:1024}"
 if [ -z "${SKIP_STATS:-}" ]; then
+  OUT=${OUT:-$R/prof_out}   # step 1's kernel stats and bench lines
+  mkdir -p $OUT
   for leg in $LEGS; do
     IFS=: read name kind block mib <<< "$leg"
-    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$name -o run --output-format csv -- python3 $R/bench.py --kind $kind --block $block --global-mib $mib --no-text --no-cpu-baseline --no-decode --no-host-path --no-lz78 --no-transition > $R/gpurun_out/prof_$name.json 2> $R/gpurun_out/prof_$name.err) || exit 1
+    # (--full: the line's kernel_ms comes from the stage profile, which a plain run leaves out)
+    (cd "$TMPDIR" && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$name -o run --output-format csv -- python3 $R/bench.py --full --kind $kind --block $block --global-mib $mib --no-text --no-cpu-baseline --no-decode --no-host-path --no-lz78 --no-transition > $OUT/prof_$name.json 2> $OUT/prof_$name.err) || exit 1
   done
 fi
 if [ -z "${SKIP_TRAFFIC:-}" ]; then
