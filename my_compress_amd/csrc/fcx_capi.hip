@@ -14,33 +14,10 @@
 #include "fcx_device.h"
 
 namespace fcx {
-// one launcher per match unit (fcx_match*.hip); route null: the unit over every tile of the shard
-#define FCX_MATCH_LAUNCHER(name)                                                                               \
-    void name(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,              \
-              uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, hipStream_t st, uint32_t dbg_override = ~0u, \
-              const MatchRoute *route = nullptr, uint32_t grid = 0);
-FCX_MATCH_LAUNCHER(launch_match)
-FCX_MATCH_LAUNCHER(launch_match_k4)
-FCX_MATCH_LAUNCHER(launch_match_nf)
-FCX_MATCH_LAUNCHER(launch_match_runs)
-FCX_MATCH_LAUNCHER(launch_match_sparse)
-#undef FCX_MATCH_LAUNCHER
-// the units' looped remainders (fcx_match_rest_<unit>.hip)
-#define FCX_REST_LAUNCHER(name)                                                                               \
-    void name(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,              \
-              uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, const RouteRest &rest, const MatchRoute &rt, \
-              uint32_t grid, hipStream_t st);
-FCX_REST_LAUNCHER(launch_match_rest_sparse)
-FCX_REST_LAUNCHER(launch_match_rest_runs)
-FCX_REST_LAUNCHER(launch_match_rest_k4)
-FCX_REST_LAUNCHER(launch_match_rest_nf)
-#undef FCX_REST_LAUNCHER
+// (the match units' launchers: fcx_device.h)
 void launch_classify(const uint8_t *in, const Layout &L, uint32_t *lists, uint32_t stride, uint32_t *cnt,
                      uint8_t *tkind, hipStream_t st);
 void launch_route_mark(uint32_t *dst, const uint32_t *src, hipStream_t st);
-void launch_match_uniform(const uint8_t *in, const Layout &L, uint64_t *mbits, uint64_t *chain, uint64_t *chain_pfx,
-                          uint32_t *tinfo, const uint32_t *list, const uint32_t *cnt, uint32_t *runs_list,
-                          uint32_t *runs_cnt, uint8_t *tkind, uint32_t grid, hipStream_t st);
 void launch_parse(const uint8_t *in, const Layout &L, uint32_t *m, const uint64_t *mbits, uint64_t *chain,
                   const uint64_t *chain_pfx, const uint32_t *tinfo, const uint32_t *mtok, uint64_t *fp,
                   uint32_t *tile_off, uint32_t *tconv, BlockInfo *binfo, uint8_t *s_flags, uint8_t *s_chars,
@@ -107,27 +84,41 @@ namespace fcx {
 void set_last_error(const std::string &m) { g_err = m; }
 }  // namespace fcx
 
-// the match kernel's translation units (fcx_match.hip and the fcx_match_<kind>.hip units that include it)
+// the match kernel's units (fcx_match.hip under each row of the Makefile's unit table); the values of
+// fcx_ctx_match_kernel
 enum MatchKernel : int {
     kMatchAuto = -1, kMatchGeneral = 0, kMatchKey4 = 1, kMatchNoFilter = 2, kMatchRuns = 3, kMatchSparse = 4,
     kMatchUniform = 5   // (fcx_ctx_match_kernel only: the uniform unit, fcx_match_uniform.hip, routed calls)
 };
-using MatchLaunch = void (*)(const uint8_t *, const Layout &, uint32_t *, uint64_t *, uint64_t *, uint64_t *,
-                             uint32_t *, uint32_t *, hipStream_t, uint32_t, const MatchRoute *, uint32_t);
-// routed calls (fcx_route.hip): the unit of each list, in launch order (the sparse and runs units hand
-// tiles on to the no-filter unit's list, so it comes last)
-constexpr int kRouteKernel[kSearchUnits] = {kMatchSparse, kMatchRuns, kMatchKey4, kMatchNoFilter};
-constexpr uint32_t kRouteMinTiles = 8;      // a unit expected to get fewer tiles is not launched (k_match_rest)
+// One row per unit: the search units in the order of their route lists (row = list index), then the
+// general unit, which has no list.
+struct MatchUnit {
+    int kernel;            // MatchKernel
+    int route;             // its route list (fcx_route_plan.h), -1: none
+    int mode;              // the fcx_ctx_set_match_mode number that forces it, and its name there
+    const char *label;
+    MatchLaunch *launch;
+    RestLaunch *rest;      // its looped remainder (routed calls)
+};
+constexpr MatchUnit kUnits[] = {
+    {kMatchSparse, kRouteSparse, 7, "sparse kernel", launch_match_sparse, launch_match_rest_sparse},
+    {kMatchRuns, kRouteRuns, 6, "runs kernel", launch_match_runs, launch_match_rest_runs},
+    {kMatchKey4, kRouteKey4, 4, "4-byte-key kernel", launch_match_k4, launch_match_rest_k4},
+    {kMatchNoFilter, kRouteNoFilter, 5, "no-filter kernel", launch_match_nf, launch_match_rest_nf},
+    {kMatchGeneral, -1, 3, "general kernel", launch_match, nullptr},
+};
+constexpr int kNumUnits = sizeof(kUnits) / sizeof(kUnits[0]);
+static_assert(kUnits[kRouteSparse].route == kRouteSparse && kUnits[kRouteRuns].route == kRouteRuns &&
+              kUnits[kRouteKey4].route == kRouteKey4 && kUnits[kRouteNoFilter].route == kRouteNoFilter &&
+              kNumUnits == kSearchUnits + 1, "kUnits: row = route list");
+static const MatchUnit &match_unit(int kernel) {   // (auto: the general unit; its routed calls go by list)
+    for (const MatchUnit &u : kUnits)
+        if (u.kernel == kernel) return u;
+    return kUnits[kSearchUnits];
+}
 constexpr uint32_t kRestGrid = 512;         // k_match_rest_<unit>'s workgroups (2 per CU: <= 128 VGPRs)
-constexpr uint32_t kRestDirect = ~0u;       // last_grid: a direct launch (its list's remainder starts at the cover)
 constexpr uint64_t kRouteBytes = 4ull * kRouteWords * 8;   // route counters of kMaxGroups (= 8) groups
 constexpr uint64_t kWordBytes = 64 + kRouteBytes;          // dev_words
-static MatchLaunch match_launcher(int k) {
-    return k == kMatchKey4 ? launch_match_k4 : k == kMatchNoFilter ? launch_match_nf
-                                             : k == kMatchRuns    ? launch_match_runs
-                                             : k == kMatchSparse  ? launch_match_sparse
-                                                                  : launch_match;
-}
 
 struct fcx_ctx {
     int device = 0;
@@ -348,16 +339,20 @@ int fcx_ctx_set_profiling(fcx_ctx *c, int enable) {
 
 int fcx_ctx_set_match_mode(fcx_ctx *c, int mode) {
     if (!c) return fail(FCX_ERR_ARG, "NULL ctx");
-    if (mode < 0 || mode > 7)
-        return fail(FCX_ERR_ARG, "match mode must be 0 (auto), 1 (bucket search), 2 (run table), 3 (general kernel), "
-                                 "4 (4-byte-key kernel), 5 (no-filter kernel), 6 (runs kernel) or 7 (sparse kernel)");
-    c->match_mode = mode == 1 ? 4u | 128u : mode == 2 ? 8u : 0u;   // k_match dbg bits: all keep the output exact
-    c->kernel = mode == 0   ? kMatchAuto
-                : mode == 4 ? kMatchKey4
-                : mode == 5 ? kMatchNoFilter
-                : mode == 6 ? kMatchRuns
-                : mode == 7 ? kMatchSparse
-                            : kMatchGeneral;
+    // 0: routed; 1-2: the general unit under k_match dbg bits (all keep the output exact); from 3: a unit
+    int kernel = mode == 0 ? kMatchAuto : kMatchGeneral;
+    bool known = mode >= 0 && mode <= 2;
+    for (const MatchUnit &u : kUnits)
+        if (u.mode == mode) { kernel = u.kernel; known = true; }
+    if (!known) {
+        std::string msg = "match mode must be 0 (auto), 1 (bucket search), 2 (run table)";
+        for (int q = 3; q < 3 + kNumUnits; q++)   // (the units' numbers follow 2 without a gap)
+            for (const MatchUnit &u : kUnits)
+                if (u.mode == q) msg += (q == 2 + kNumUnits ? " or " : ", ") + std::to_string(q) + " (" + u.label + ")";
+        return fail(FCX_ERR_ARG, msg);
+    }
+    c->match_mode = mode == 1 ? 4u | 128u : mode == 2 ? 8u : 0u;
+    c->kernel = kernel;
     return FCX_OK;
 }
 
@@ -439,7 +434,6 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     c->last_cold = routed && !c->have_hint;
     c->last_groups = G;
     c->last_kernel = routed ? kMatchGeneral : c->kernel;
-    const MatchLaunch match = match_launcher(c->kernel);
     uint64_t cold_cnt[kRoutes] = {}, cold_valid = 0;
     HIP_TRY(hipMemsetAsync(c->dev_words, 0, kWordBytes, st));
     if (G > 1) {
@@ -457,17 +451,18 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
         for (uint32_t q = 0; q < kStreams; q++) sg_s[q] = c->s[q] + b0 * L.sstride[q];
         if (ev) HIP_TRY(hipEventRecord(ev[0], sg));   // (the memset above is not timed per group)
         const uint8_t *gin = d_in + b0 * c->B;
-        uint32_t *gm = c->m + b0 * c->B, *gtinfo = c->tinfo + 8 * t0, *gmtok = c->mtok + t0 * kTileMatches;
-        uint64_t *gmbits = c->mbits + b0 * L.wpb, *gchain = c->chain + b0 * L.wpb, *gpfx = c->chain_pfx + t0 * (kTile / 64);
+        const MatchArgs ma{gin, Lg, c->m + b0 * c->B, c->mbits + b0 * L.wpb, c->chain + b0 * L.wpb,
+                           c->chain_pfx + t0 * (kTile / 64), c->tinfo + 8 * t0, c->mtok + t0 * kTileMatches};
         if (!routed) {
             if (ev) HIP_TRY(hipEventRecord(ev[1], sg));
-            match(gin, Lg, gm, gmbits, gchain, gpfx, gtinfo, gmtok, sg, c->match_mode, nullptr, 0);
+            match_unit(c->kernel).launch(ma, sg, c->match_mode, nullptr, 0);
         } else {
             // classify the group's tiles into the unit lists, then each unit over its list with a grid
             // from the estimate (the first call waits for its own counts), k_match_rest for the rest
             uint32_t *rc = (uint32_t *)((uint8_t *)c->dev_words + 64) + kRouteWords * g;
             uint32_t *lists = c->rlist + t0;
             const uint32_t stride = (uint32_t)c->cap_tiles, ntg = Lg.nblocks * Lg.tpb;
+            auto list_of = [&](uint32_t u) { return lists + (uint64_t)u * stride; };
             launch_classify(gin, Lg, lists, stride, rc, c->tkind + t0, sg);
             if (ev) HIP_TRY(hipEventRecord(ev[1], sg));
             uint64_t est[kRoutes];
@@ -478,92 +473,47 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
                 for (uint32_t u = 0; u < kRoutes; u++) { est[u] = cold[u]; cold_cnt[u] += cold[u]; }
                 cold_valid += cold[kRcValid];
             } else {
-                const uint64_t v = std::max<uint64_t>(c->hint_valid, 1);
-                for (uint32_t u = 0; u < kRoutes; u++) est[u] = (c->hint_cnt[u] * ntg + v - 1) / v;
+                route_estimate(c->hint_cnt, c->hint_valid, ntg, est);
             }
-            // the uniform unit first (looped: any grid covers its list; a multiple of 8 for its XCD split):
-            // the tiles it hands on join the runs list before any runs launch reads it.  At least 2048
-            // one-wave workgroups (≈ 3 µs when the list is empty), so an unforeseen list is still
-            // taken by 8 waves per CU
-            const uint32_t ugrid = (uint32_t)std::min<uint64_t>(8192, std::max<uint64_t>(2048, (est[kRouteUniform] + 7) / 8 * 8));
-            launch_match_uniform(gin, Lg, gmbits, gchain, gpfx, gtinfo, lists + (uint64_t)kRouteUniform * stride,
-                                 rc + kRouteUniform, lists + (uint64_t)kRouteRuns * stride, rc + kRouteRuns,
-                                 c->tkind + t0, ugrid, sg);
-            // the unit expected to take most of the tiles (at least half) runs first, direct over every
-            // tile of the group: it drops the others by their kind byte -- or, when the estimate gives
-            // it (nearly) all tiles, it searches every tile with the unrouted kernel's exact code, and
-            // the few tiles of other kinds are searched again by their own units afterwards (the last
-            // writer's outputs are complete).  The others run over their lists.
-            uint32_t best = 0;
-            for (uint32_t u = 1; u < kSearchUnits; u++)
-                if (est[u] > est[best]) best = u;
-            // (a recent call with hand-ons or lazy tiles -- tiles its units' samples misfiled -- keeps
-            // every unit listed: only listed sparse / runs launches hand such tiles on)
-            const bool direct = 2 * est[best] >= ntg && c->hint_fix == 0;
-            const bool every = direct && 64 * est[best] >= 63ull * ntg;
-            uint32_t order[kSearchUnits], no = 0;
-            if (direct) order[no++] = best;
-            for (uint32_t u = 0; u < kSearchUnits; u++)
-                if (!(direct && u == best)) order[no++] = u;
-            MatchRoute rts[kSearchUnits];
-            RouteRest rest[kSearchUnits];
-            for (uint32_t q = 0; q < kSearchUnits; q++) {
-                const uint32_t u = order[q];
-                // a small margin over the estimate (its excess workgroups exit at once); the no-filter
-                // list also takes the tiles the sparse / runs units hand on
-                const uint64_t gr = est[u] >= kRouteMinTiles ? est[u] + est[u] / 16 + 32 : 0;
+            const RoutePlan plan = plan_route(est, ntg, c->hint_fix != 0);
+            // the uniform unit first: the tiles it hands on join the runs list before any runs launch reads it
+            launch_match_uniform(ma, list_of(kRouteUniform), rc + kRouteUniform, list_of(kRouteRuns), rc + kRouteRuns,
+                                 c->tkind + t0, plan.ugrid, sg);
+            MatchRoute rts[kSearchUnits];   // per unit: its routed form (its remainder's; its launch's unless direct)
+            for (uint32_t u : plan.order) {
+                const bool direct = plan.grid[u] == kRestDirect;
                 MatchRoute &rt = rts[u];
                 rt.kind = c->tkind + t0;
                 rt.mine = u;
                 rt.cnt = rc + u;
-                rest[u] = RouteRest{lists + (uint64_t)u * stride, rc + u, 0u, nullptr};
-                uint32_t grid = 0;
-                MatchRoute launch = rt;
-                if (direct && u == best) {
-                    // the direct launch (first) has every entry of its list; the no-filter list grows by
-                    // later hand-ons, past the entries the classifier filed (cnt[4])
-                    rest[u].start = ~0u;
-                    if (u == kRouteNoFilter) rest[u].start_dev = rc + kRcNfFiled;
-                    if (every) launch = MatchRoute{};   // (unrouted code: no kind check, no hand-on)
-                } else {
-                    grid = (uint32_t)std::min<uint64_t>(gr, ntg);
-                    rest[u].start = grid;
-                    rt.list = lists + (uint64_t)u * stride;
-                    launch = rt;
-                    if (u == kRouteNoFilter && grid) {
-                        // covers min(grid, its count now); later hand-ons land past that count, possibly
-                        // below the grid: its remainder starts at the smaller of the two
-                        launch_route_mark(rc + kRcCover, rc + kRouteNoFilter, sg);
-                        rest[u].start_dev = rc + kRcCover;
-                    }
-                }
+                if (!direct) rt.list = list_of(u);
                 if (u == kRouteSparse || u == kRouteRuns) {
-                    rt.defer_list = lists + (uint64_t)kRouteNoFilter * stride;
+                    rt.defer_list = list_of(kRouteNoFilter);
                     rt.defer_cnt = rc + kRouteNoFilter;
-                    if (launch.list || launch.kind) {
-                        launch.defer_list = rt.defer_list;
-                        launch.defer_cnt = rt.defer_cnt;
-                    }
                 }
-                match_launcher(kRouteKernel[u])(gin, Lg, gm, gmbits, gchain, gpfx, gtinfo, gmtok, sg, 0u, &launch, grid);
-                c->last_grid[g][u] = direct && u == best ? kRestDirect : grid;
+                // the no-filter list's length now, before its listed launch (rest_start)
+                if (rest_start(plan.grid[u], u).word == (int)kRcCover)
+                    launch_route_mark(rc + kRcCover, rc + kRouteNoFilter, sg);
+                // (direct over every tile: the unrouted code, no kind check and no hand-on)
+                const MatchRoute launch = direct && plan.every ? MatchRoute{} : rt;
+                kUnits[u].launch(ma, sg, 0u, &launch, direct ? 0u : plan.grid[u]);
+                c->last_grid[g][u] = plan.grid[u];
             }
             if (g == 0)
-                c->last_kernel = est[kRouteUniform] > est[best] ? kMatchUniform : est[best] ? kRouteKernel[best] : kMatchGeneral;
+                c->last_kernel = est[kRouteUniform] > est[plan.best] ? kMatchUniform
+                                 : est[plan.best]                    ? kUnits[plan.best].kernel
+                                                                     : kMatchGeneral;
             // each unit's remainder (the no-filter one last: it takes the others' hand-ons); a direct
             // sparse / runs / 4-byte launch leaves none
-            using RestLaunch = void (*)(const uint8_t *, const Layout &, uint32_t *, uint64_t *, uint64_t *, uint64_t *,
-                                        uint32_t *, uint32_t *, const RouteRest &, const MatchRoute &, uint32_t,
-                                        hipStream_t);
-            const RestLaunch rest_launch[kSearchUnits] = {launch_match_rest_sparse, launch_match_rest_runs,
-                                                          launch_match_rest_k4, launch_match_rest_nf};
-            for (uint32_t u = 0; u < kSearchUnits; u++)
-                if (rest[u].start != ~0u || rest[u].start_dev)
-                    rest_launch[u](gin, Lg, gm, gmbits, gchain, gpfx, gtinfo, gmtok, rest[u], rts[u], kRestGrid, sg);
+            for (uint32_t u = 0; u < kSearchUnits; u++) {
+                const RestStart rs = rest_start(plan.grid[u], u);
+                if (rs.none()) continue;
+                const RouteRest rest{list_of(u), rc + u, rs.start, rs.word >= 0 ? rc + rs.word : nullptr};
+                kUnits[u].rest(ma, rest, rts[u], kRestGrid, sg);
+            }
         }
         if (ev) HIP_TRY(hipEventRecord(ev[2], sg));
-        launch_parse(gin, Lg, c->m + b0 * c->B, c->mbits + b0 * L.wpb, c->chain + b0 * L.wpb,
-                     c->chain_pfx + t0 * (kTile / 64), c->tinfo + 8 * t0, c->mtok + t0 * kTileMatches, c->fp + 12 * t0,
+        launch_parse(gin, Lg, ma.m, ma.mbits, ma.chain, ma.chain_pfx, ma.tinfo, ma.mtok, c->fp + 12 * t0,
                      c->tile_off + 3 * t0, c->tconv + t0, c->binfo + b0, sg_s[0], sg_s[1], sg_s[2], sg_s[3],
                      c->thist + t0 * 256, c->sdesc + b0 * ((c->B + kCharSeg - 1) / kCharSeg), err, sg, ev ? ev + 3 : nullptr,
                      c->emit_dbg);
@@ -657,11 +607,7 @@ int fcx_ctx_route_stats(fcx_ctx *c, uint64_t *out, int n) {
             const uint32_t *r = rc + kRouteWords * g;
             for (uint32_t u = 0; u < kSearchUnits; u++) {
                 v[u] += r[u];
-                uint32_t s0 = c->last_grid[g][u] != kRestDirect ? c->last_grid[g][u]
-                              : u == kRouteNoFilter                ? r[kRcNfFiled]
-                                                                   : r[u];
-                if (u == kRouteNoFilter && c->last_grid[g][u] != kRestDirect && c->last_grid[g][u])
-                    s0 = std::min(s0, r[kRcCover]);
+                const uint32_t s0 = rest_start(c->last_grid[g][u], u, r);
                 v[6] += r[u] > s0 ? r[u] - s0 : 0u;
             }
             v[4] += r[kRouteNoFilter] - r[kRcNfFiled] + r[kRouteRuns] - r[kRcRunsFiled];
@@ -681,11 +627,30 @@ int fcx_debug_match(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t dbg, v
     HIP_TRY(hipSetDevice(c->device));
     int r = ensure_scratch(c, n);
     if (r) return r;
-    const Layout L = make_layout(n, c->B);
-    match_launcher(c->kernel)(d_in, L, c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok, (hipStream_t)stream,
-                              dbg, nullptr, 0);
+    const MatchArgs ma{d_in, make_layout(n, c->B), c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok};
+    match_unit(c->kernel).launch(ma, (hipStream_t)stream, dbg, nullptr, 0);
     HIP_TRY(hipGetLastError());
     return FCX_OK;
+}
+
+// development only (not in fcx.h): the routed call's launch plan (fcx_route_plan.h) for the tests; no GPU.
+// out: ugrid, best, direct, every, order[4], grid[4]
+int fcx_debug_route_plan(const uint64_t est[5], uint32_t ntg, int fix, uint32_t out[12]) {
+    if (!est || !out) return fail(FCX_ERR_ARG, "fcx_debug_route_plan: NULL");
+    const RoutePlan p = plan_route(est, ntg, fix != 0);
+    out[0] = p.ugrid; out[1] = p.best; out[2] = p.direct; out[3] = p.every;
+    for (uint32_t u = 0; u < kSearchUnits; u++) { out[4 + u] = p.order[u]; out[8 + u] = p.grid[u]; }
+    return FCX_OK;
+}
+// ... its estimates from a recent call's counts (est[5]) ...
+int fcx_debug_route_estimate(const uint64_t cnt[5], uint64_t valid, uint32_t ntg, uint64_t est[5]) {
+    if (!cnt || !est) return fail(FCX_ERR_ARG, "fcx_debug_route_estimate: NULL");
+    route_estimate(cnt, valid, ntg, est);
+    return FCX_OK;
+}
+// ... and where a unit's remainder starts, given its grid in the plan and the call's 16 route counters
+uint32_t fcx_debug_rest_start(uint32_t grid, uint32_t unit, const uint32_t counters[16]) {
+    return unit < kSearchUnits && counters ? rest_start(grid, unit, counters) : ~0u;
 }
 
 int fcx_ctx_info(fcx_ctx *c, int *device, uint32_t *block_bytes, uint64_t *shard_bytes) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fcx_route_plan.h"
+
 namespace fcx {
 
 // ---- format constants (my_compress.cpp:1261-1277, 222-224) ----------------
@@ -87,19 +89,7 @@ struct Layout {
 // ---- per-tile routing of the match search (fcx_route.hip) ------------------
 // k_classify sorts the shard's tiles into one list per match unit; each unit's kernel then runs over
 // its own list, so the unit that searches a tile depends only on that tile's bytes.
-// Lists 0-3 are the match units (fcx_match_<unit>.hip); list 4 the uniform unit (fcx_match_uniform.hip:
-// tiles whose sample is one byte value, checked over their whole window, the others handed on to runs).
-enum : uint32_t {
-    kRouteSparse = 0, kRouteRuns = 1, kRouteKey4 = 2, kRouteNoFilter = 3, kSearchUnits = 4,
-    kRouteUniform = 4, kRoutes = 5
-};
-// route counters per block group (k_classify, the units' hand-ons, the host's cover mark): [0, kRoutes)
-// list lengths, then these
-constexpr uint32_t kRcNfFiled = 5;    // tiles the classifier filed as no-filter (its list grows by hand-ons)
-constexpr uint32_t kRcValid = 6;      // tiles with bytes
-constexpr uint32_t kRcCover = 7;      // the no-filter list's length at its listed launch
-constexpr uint32_t kRcRunsFiled = 8;  // tiles the classifier filed as runs (its list grows by the uniform unit's hand-ons)
-constexpr uint32_t kRouteWords = 16;
+// The lists, their counters and the host's launch plan: fcx_route_plan.h.
 struct MatchRoute {
     const uint32_t *list = nullptr;   // the launch's tiles (null: the grid is every tile of the shard)
     const uint32_t *cnt = nullptr;    // entries in list
@@ -115,6 +105,26 @@ struct RouteRest {                    // k_match_rest_<unit>: its list's entries
     const uint32_t *start_dev;        // ... or, when set, the smaller of it and the count read here (the
                                       //   entries the no-filter launch covered; later ones are hand-ons)
 };
+
+// the match search's buffers of one launch (host side: the kernels take them as loose parameters)
+struct MatchArgs {
+    const uint8_t *in;
+    Layout L;
+    uint32_t *m;
+    uint64_t *mbits, *chain, *chain_pfx;
+    uint32_t *tinfo, *mtok;
+};
+// One launcher per match unit (fcx_match.hip, compiled once per row of the Makefile's unit table).
+// route null: the unit over every tile of the shard, dbg its experiment bits; else grid workgroups
+// over the route's list (direct when it has none)
+using MatchLaunch = void(const MatchArgs &a, hipStream_t st, uint32_t dbg, const MatchRoute *route, uint32_t grid);
+MatchLaunch launch_match, launch_match_k4, launch_match_nf, launch_match_runs, launch_match_sparse;
+// the units' looped remainders (k_match_rest_<unit>)
+using RestLaunch = void(const MatchArgs &a, const RouteRest &rest, const MatchRoute &rt, uint32_t grid, hipStream_t st);
+RestLaunch launch_match_rest_sparse, launch_match_rest_runs, launch_match_rest_k4, launch_match_rest_nf;
+// the uniform unit (fcx_match_uniform.hip; it writes no m and no mtok)
+void launch_match_uniform(const MatchArgs &a, const uint32_t *list, const uint32_t *cnt, uint32_t *runs_list,
+                          uint32_t *runs_cnt, uint8_t *tkind, uint32_t grid, hipStream_t st);
 
 // ---- wave64 helpers --------------------------------------------------------
 __device__ inline uint32_t lane_id() { return __lane_id(); }

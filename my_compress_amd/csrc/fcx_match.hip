@@ -43,34 +43,42 @@
 #define FCX_MATCH_EXIT 0u   // development: a dbg timing-exit bit compiled into the product kernel (tools/phase_libs.sh)
 #endif
 
-// FCX_KEY4 (fcx_match_k4.hip): the same kernel with the bucket search over 4-byte keys, for shards of
+// This file is compiled once per kernel instance, each time under a unit's switch set and name
+// (-DFCX_UNIT_NAME=<unit>) plus an instance switch: the Makefile's unit table is the one definition
+// of both.  With no unit name the kernel is the general k_match.  Every instance is a translation
+// unit of its own: k_match's register allocation moves when a second kernel sits beside it, and
+// with any edit of its source -- the switches below only remove or swap code by the preprocessor,
+// so the other units' source is unchanged by a unit's branches.
+//
+// FCX_KEY4 (the k4 unit): the same kernel with the bucket search over 4-byte keys, for tiles of
 // dense keys (small alphabets such as 'ACGT' data: 64 distinct 3-byte keys, ~32 candidates per
 // query).  A match of length >= 4 shares its query's first four bytes, so the 4-byte bucket holds
 // every candidate of a longest match >= 4 (a quarter of the 3-byte candidates on 'ACGT' data); a
-// query without one takes the leftmost 3-byte match by a window scan.  The context picks this
-// translation unit per call from the previous call's share of small-alphabet blocks (k_tree);
-// both units give the same bytes.  The K3 unit's source is unchanged by the K4 branches below
-// (preprocessor): k_match's register allocation moves with any edit of its source.
+// query without one takes the leftmost 3-byte match by a window scan.  Small-alphabet tiles always
+// reach the bucket search, so the unit also drops the repeat filter and the run count
+// (FCX_NOFILTER; dna k_match 25.0 -> 24.4 ms per GiB).  Every unit gives the same bytes.
 #ifndef FCX_KEY4
 #define FCX_KEY4 0
 #endif
-// FCX_NOFILTER (fcx_match_nf.hip): the kernel without the repeat sample, the repeat filter, the
-// sparse search and the run count, for shards of match-dense blocks (text: every tile takes the
+// FCX_NOFILTER (the nf unit): the kernel without the repeat sample, the repeat filter, the
+// sparse search and the run count, for match-dense tiles (text: every tile takes the
 // bucket search there, so the sampled filter that sends random-data tiles to the sparse search and
 // the run count that sends long-run tiles to the run mode are wasted work, ~0.8 ms per GiB).
-// Chosen per call like the 4-byte-key unit; the same bytes either way.
 #ifndef FCX_NOFILTER
 #define FCX_NOFILTER 0
 #endif
-// FCX_RUNS (fcx_match_runs.hip): the kernel with the run-mode walk inlined, for shards of long-match
-// blocks (runs, zeros).  Out of line, the walk saves callee-saved VGPRs to scratch on every run-mode
+// FCX_RUNS (the runs unit): the kernel with the run-mode walk inlined, for long-match tiles (runs,
+// zeros).  Out of line, the walk saves callee-saved VGPRs to scratch on every run-mode
 // tile (16 KB per tile, written to HBM); inlined, the other tile modes' register allocation moves,
-// which only this unit's shards pay.
+// which only this unit's tiles pay.  They take the run mode or the sparse search, so the unit also
+// drops the bucket search (FCX_NOBUCKET; runs k_match 8.97 -> 8.83 ms per GiB, zeros 1.92 -> 1.82)
+// and the repeat sample (a tile that is not run mode always runs the filter; zeros 1.83 -> 1.63,
+// runs 8.82 -> 8.76).
 #ifndef FCX_RUNS
 #define FCX_RUNS 0
 #endif
-// FCX_SPARSE (fcx_match_sparse.hip): the kernel without the bucket search, the repeat sample and the
-// run count, for shards of few-match blocks (random data: every tile takes the sparse search).  Every
+// FCX_SPARSE (the sparse unit): the kernel without the bucket search, the repeat sample and the
+// run count, for few-match tiles (random data: every tile takes the sparse search).  Every
 // tile runs the repeat filter; a tile it does not send to the sparse search takes the whole-tile
 // run-table mode instead (exact for any tile, slow where the runs overflow the table:
 // fcx_ctx_set_match_mode 2); the sparse search is inlined.  Rand k_match 2.64 -> 2.31 ms per GiB
@@ -79,7 +87,7 @@
 #define FCX_SPARSE 0
 #endif
 // FCX_NOBUCKET: no bucket search; a tile the repeat filter does not send to the sparse search takes
-// the whole-tile run-table mode (the sparse unit)
+// the whole-tile run-table mode (the sparse and runs units)
 #ifndef FCX_NOBUCKET
 #define FCX_NOBUCKET FCX_SPARSE
 #endif
@@ -88,12 +96,18 @@
 #ifndef FCX_SHORTK
 #define FCX_SHORTK 0
 #endif
-// FCX_REST (fcx_match_rest_<unit>.hip): the unit's tile body in k_match_rest_<unit>, a loop over the
-// entries of the unit's list that its launch did not cover (fcx_route.hip).  Its own translation
-// unit, so the unit's k_match keeps its code generation.
+// FCX_UNIT_ILP: interleaved bucket walks per lane, where a unit has its own width (default 4).  The
+// k4 and nf units take 2: dna k_match 24.6 -> 24.0 ms per GiB, text 9.95 -> 9.67 (4: 0 spills, but
+// the wider walk pays on text's short buckets)
+//
+// FCX_REST (build/fcx_match_rest_<unit>.o): the unit's tile body in k_match_rest_<unit>, a loop over
+// the entries of the unit's list that no launch of the unit covered in a routed call (fcx_route.hip).
+// Its own translation unit, so the unit's k_match keeps its code generation.
 #ifndef FCX_REST
 #define FCX_REST 0
 #endif
+// FCX_REST_WAVES: k_match_rest's waves per SIMD.  The build gives 4: looped, the body needs up to
+// 128 VGPRs (at the 8-wave cap: 22-95 spilled)
 #ifndef FCX_REST_WAVES
 #define FCX_REST_WAVES 8
 #endif
@@ -107,50 +121,38 @@
 #else
 #define FCX_SAMPLE 0
 #endif
-// the unit's kernel and launcher names (a unit may combine switches: the 4-byte-key unit also drops
-// the filter and the run count)
-#if FCX_KEY4
-#define k_match k_match_k4
-#define launch_match launch_match_k4
-#define launch_match_listed launch_match_k4_listed
-#define launch_match_direct launch_match_k4_direct
-#define k_match_rest k_match_rest_k4
-#define launch_match_rest launch_match_rest_k4
-#elif FCX_NOFILTER
-#define k_match k_match_nf
-#define launch_match launch_match_nf
-#define launch_match_listed launch_match_nf_listed
-#define launch_match_direct launch_match_nf_direct
-#define k_match_rest k_match_rest_nf
-#define launch_match_rest launch_match_rest_nf
-#elif FCX_SPARSE
-#define k_match k_match_sparse
-#define launch_match launch_match_sparse
-#define launch_match_listed launch_match_sparse_listed
-#define launch_match_direct launch_match_sparse_direct
-#define k_match_rest k_match_rest_sparse
-#define launch_match_rest launch_match_rest_sparse
-#elif FCX_RUNS
-#define k_match k_match_runs
-#define launch_match launch_match_runs
-#define launch_match_listed launch_match_runs_listed
-#define launch_match_direct launch_match_runs_direct
-#define k_match_rest k_match_rest_runs
-#define launch_match_rest launch_match_rest_runs
+// the unit's kernel and launcher names: k_match_<unit>, launch_match_<unit>[_listed|_direct],
+// k_match_rest_<unit>, launch_match_rest_<unit>
+#ifdef FCX_UNIT_NAME
+#define FCX_UNIT 1
+#define FCX_PASTE3_(a, b, c) a##b##c
+#define FCX_PASTE3(a, b, c) FCX_PASTE3_(a, b, c)
+#define k_match FCX_PASTE3(k_match_, FCX_UNIT_NAME, )
+#define launch_match FCX_PASTE3(launch_match_, FCX_UNIT_NAME, )
+#define launch_match_listed FCX_PASTE3(launch_match_, FCX_UNIT_NAME, _listed)
+#define launch_match_direct FCX_PASTE3(launch_match_, FCX_UNIT_NAME, _direct)
+#define k_match_rest FCX_PASTE3(k_match_rest_, FCX_UNIT_NAME, )
+#define launch_match_rest FCX_PASTE3(launch_match_rest_, FCX_UNIT_NAME, )
+#else
+#define FCX_UNIT 0
 #endif
-// FCX_LISTED (fcx_match_<unit>_listed.hip): the unit's listed kernel instance alone (routed calls,
-// fcx_route.hip), in its own translation unit: next to it the direct instance's code moved
+#if FCX_UNIT != (FCX_KEY4 || FCX_NOFILTER || FCX_SPARSE || FCX_RUNS)
+#error "a unit's switch set comes with its name (FCX_UNIT_NAME), the general kernel has neither"
+#endif
+// FCX_LISTED (build/fcx_match_<unit>_listed.o): the unit's listed kernel instance alone
+// (k_match<false, true, true>: its tiles from the unit's list in a routed call, fcx_route.hip), in
+// its own translation unit: next to it the direct instance's code moved
 #ifndef FCX_LISTED
 #define FCX_LISTED 0
 #endif
-// FCX_DIRECT (fcx_match_<unit>_direct.hip): the unit's checked direct instance alone (a routed call
-// whose estimate gives the unit most but not nearly all tiles).  Beside the unrouted instances it
-// moved their code: the helpers the kernels share are inlined differently with a third caller (the
-// runs unit went from 54 VGPRs / 12 B of stack to 62 / 40).
+// FCX_DIRECT (build/fcx_match_<unit>_direct.o): the unit's checked direct instance alone
+// (k_match<false, false, true>: every tile of the grid, those of other kinds ending at their kind
+// byte; a routed call whose estimate gives the unit most but not nearly all tiles).  Beside the
+// unrouted instances it moved their code: the helpers the kernels share are inlined differently with
+// a third caller (the runs unit went from 54 VGPRs / 12 B of stack to 62 / 40).
 #ifndef FCX_DIRECT
 #define FCX_DIRECT 0
 #endif
-#define FCX_UNIT (FCX_KEY4 || FCX_NOFILTER || FCX_SPARSE || FCX_RUNS)
 #if FCX_RUNS
 #define FCX_RMODE_CALL __forceinline__
 #else
@@ -177,7 +179,7 @@ constexpr uint32_t kMT = kMatchThreads;              // 512
 constexpr uint32_t kSeg = kTile / kMT;               // 8 positions per lane in the parse
 constexpr uint32_t kQPL = kTile / kMT;               // 8 queries per lane
 #if defined(FCX_UNIT_ILP)
-constexpr uint32_t kIlp = FCX_UNIT_ILP;   // a unit's own width (fcx_match_nf.hip, fcx_match_k4.hip)
+constexpr uint32_t kIlp = FCX_UNIT_ILP;              // a unit's own width
 #else
 constexpr uint32_t kIlp = 4;                         // interleaved chain walks per lane
 #endif
@@ -1724,39 +1726,29 @@ __global__ __launch_bounds__(kMT, FCX_REST_WAVES) void k_match_rest(const uint8_
     }
 }
 
-void launch_match_rest(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,
-                       uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, const RouteRest &rest, const MatchRoute &rt,
-                       uint32_t grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_match_rest, dim3(grid), dim3(kMT), 0, st, in, L, m, mbits, chain, chain_pfx, tinfo, mtok, rest,
-                       rt);
+void launch_match_rest(const MatchArgs &a, const RouteRest &rest, const MatchRoute &rt, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_match_rest, dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain, a.chain_pfx, a.tinfo,
+                       a.mtok, rest, rt);
 }
 #endif
 
+#if FCX_UNIT && !FCX_REST
+// the unit's routed instances, each defined in its own translation unit (FCX_LISTED, FCX_DIRECT)
+void launch_match_listed(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid);
+void launch_match_direct(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid);
+#endif
 #if FCX_LISTED
-void launch_match_listed(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,
-                         uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, hipStream_t st, const MatchRoute &rt,
-                         uint32_t grid) {
-    hipLaunchKernelGGL((k_match<false, true, true>), dim3(grid), dim3(kMT), 0, st, in, L, m, mbits, chain, chain_pfx,
-                       tinfo, mtok, 0u, rt);
+void launch_match_listed(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid) {
+    hipLaunchKernelGGL((k_match<false, true, true>), dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain,
+                       a.chain_pfx, a.tinfo, a.mtok, 0u, rt);
 }
 #elif FCX_DIRECT
-void launch_match_direct(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,
-                         uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, hipStream_t st, const MatchRoute &rt,
-                         uint32_t grid) {
-    hipLaunchKernelGGL((k_match<false, false, true>), dim3(grid), dim3(kMT), 0, st, in, L, m, mbits, chain, chain_pfx,
-                       tinfo, mtok, 0u, rt);
+void launch_match_direct(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid) {
+    hipLaunchKernelGGL((k_match<false, false, true>), dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain,
+                       a.chain_pfx, a.tinfo, a.mtok, 0u, rt);
 }
 #elif !FCX_REST
-#if FCX_UNIT
-void launch_match_listed(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,
-                         uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, hipStream_t st, const MatchRoute &rt,
-                         uint32_t grid);   // (fcx_match_<unit>_listed.hip)
-void launch_match_direct(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain,
-                         uint64_t *chain_pfx, uint32_t *tinfo, uint32_t *mtok, hipStream_t st, const MatchRoute &rt,
-                         uint32_t grid);   // (fcx_match_<unit>_direct.hip)
-#endif
-void launch_match(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbits, uint64_t *chain, uint64_t *chain_pfx,
-                  uint32_t *tinfo, uint32_t *mtok, hipStream_t st, uint32_t dbg_override, const MatchRoute *route,
+void launch_match(const MatchArgs &a, hipStream_t st, uint32_t dbg_override, const MatchRoute *route,
                   uint32_t grid_override) {
     // dbg bits (k_match<true> only): fcx_debug_match's phase exits and experiment bits
     // (development; the kernel alone on scratch the caller discards) and the forced tile modes
@@ -1765,22 +1757,20 @@ void launch_match(const uint8_t *in, const Layout &L, uint32_t *m, uint64_t *mbi
     // without any of them; nothing is read from the environment.
     const uint32_t dbg = dbg_override != ~0u ? dbg_override : 0u;
     const MatchRoute rt = route ? *route : MatchRoute{};
-    const uint32_t grid = rt.list ? grid_override : L.nblocks * L.tpb;
+    const uint32_t grid = rt.list ? grid_override : a.L.nblocks * a.L.tpb;
     if (grid == 0) return;
     if (rt.list) {
 #if FCX_UNIT
-        launch_match_listed(in, L, m, mbits, chain, chain_pfx, tinfo, mtok, st, rt, grid);
-#endif
-#if FCX_UNIT
+        launch_match_listed(a, st, rt, grid);
     } else if (rt.kind) {   // direct, checked: tiles of other kinds end at their kind byte
-        launch_match_direct(in, L, m, mbits, chain, chain_pfx, tinfo, mtok, st, rt, grid);
+        launch_match_direct(a, st, rt, grid);
 #endif
     } else if (dbg == 0)   // unrouted, or direct over every tile
-        hipLaunchKernelGGL((k_match<false, false, false>), dim3(grid), dim3(kMT), 0, st, in, L, m, mbits, chain, chain_pfx,
-                           tinfo, mtok, 0u, rt);
+        hipLaunchKernelGGL((k_match<false, false, false>), dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain,
+                           a.chain_pfx, a.tinfo, a.mtok, 0u, rt);
     else
-        hipLaunchKernelGGL((k_match<true, false, false>), dim3(grid), dim3(kMT), 0, st, in, L, m, mbits, chain, chain_pfx,
-                           tinfo, mtok, dbg, rt);
+        hipLaunchKernelGGL((k_match<true, false, false>), dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain,
+                           a.chain_pfx, a.tinfo, a.mtok, dbg, rt);
 }
 #endif
 

@@ -104,11 +104,10 @@ __global__ __launch_bounds__(64, 8) void k_match_uniform(const uint8_t *__restri
     }
 }
 
-void launch_match_uniform(const uint8_t *in, const Layout &L, uint64_t *mbits, uint64_t *chain, uint64_t *chain_pfx,
-                          uint32_t *tinfo, const uint32_t *list, const uint32_t *cnt, uint32_t *runs_list,
+void launch_match_uniform(const MatchArgs &a, const uint32_t *list, const uint32_t *cnt, uint32_t *runs_list,
                           uint32_t *runs_cnt, uint8_t *tkind, uint32_t grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_match_uniform, dim3(grid), dim3(64), 0, st, in, L, mbits, chain, chain_pfx, tinfo, list, cnt,
-                       runs_list, runs_cnt, tkind);
+    hipLaunchKernelGGL(k_match_uniform, dim3(grid), dim3(64), 0, st, a.in, a.L, a.mbits, a.chain, a.chain_pfx, a.tinfo,
+                       list, cnt, runs_list, runs_cnt, tkind);
 }
 
 }  // namespace fcx

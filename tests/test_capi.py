@@ -44,6 +44,37 @@ def test_library_carries_gfx950_code_object(tmp_path):
     assert "gfx950" in (out.stdout + out.stderr)
 
 
+def test_library_carries_every_match_kernel_once(tmp_path):
+    """the build's unit table (csrc/Makefile): each match unit's kernel instances under their names
+    (profiles/, Context.MATCH_KERNELS and bench.py look kernels up by them), each in one code object"""
+    llvm = "/opt/rocm/lib/llvm/bin/"
+    lib = tmp_path / "libfcx.so"
+    shutil.copyfile(mc.lib_path(), lib)
+    subprocess.run([llvm + "llvm-objdump", "--offloading", str(lib)], capture_output=True, check=True)
+    where = {}   # kernel symbol -> code objects that define it
+    for co in sorted(tmp_path.glob("libfcx.so.*gfx950*")):
+        syms = subprocess.run([llvm + "llvm-readelf", "-s", "--wide", str(co)], capture_output=True, text=True,
+                              check=True).stdout
+        for line in syms.splitlines():
+            f = line.split()
+            if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND" and "k_match" in f[7]:
+                where.setdefault(f[7], set()).add(co.name)
+    sig = "EEEvPKhNS_6LayoutEPjPmS5_S5_S4_S4_jNS_10MatchRouteE"   # k_match<kDev, kListed, kRouted>'s parameters
+    rest = "EPKhNS_6LayoutEPjPmS4_S4_S3_S3_NS_9RouteRestENS_10MatchRouteE"
+    want = {f"_ZN3fcx7k_matchILb{d}ELb0ELb0" + sig for d in (0, 1)}
+    want.add("_ZN3fcx15k_match_uniformEPKhNS_6LayoutEPmS3_S3_PjPKjS6_S4_S4_Ph")
+    for unit in ("k4", "nf", "runs", "sparse"):
+        name = f"k_match_{unit}"
+        for inst in ("Lb0ELb0ELb0", "Lb1ELb0ELb0", "Lb0ELb1ELb1", "Lb0ELb0ELb1"):
+            want.add(f"_ZN3fcx{len(name)}{name}I{inst}" + sig)
+        name = f"k_match_rest_{unit}"
+        want.add(f"_ZN3fcx{len(name)}{name}" + rest)
+    assert len(want) == 23
+    assert set(where) == want, sorted(set(where) ^ want)
+    assert all(len(cos) == 1 for cos in where.values()), {k: v for k, v in where.items() if len(v) > 1}
+    # 17 match instances + the uniform unit; the listed, direct and rest objects hold one kernel each
+    assert len(set.union(*where.values())) == 18
+
 def test_header_roundtrip():
     h = mc.write_header(5, 1)
     assert h == b"FCX7" + struct.pack("<IH", 5, 1)

@@ -329,7 +329,7 @@ def _small_alphabet_mix(seed: int, n: int) -> bytes:
 
 @pytest.mark.parametrize("block", [1 << 20, 65536, 5000])
 def test_key4_kernel_vs_oracle(cuda, block):
-    """the 4-byte-key match unit (fcx_match_k4.hip): forced (mode 4) and routed (mode 0: 'ACGT'
+    """the 4-byte-key match unit (fcx_match.hip under FCX_KEY4, k_match_k4): forced (mode 4) and routed (mode 0: 'ACGT'
     tiles go to it from the first call on), against the oracle on dna, mixed small-alphabet /
     text / random / periodic data and a ragged tail"""
     import torch

@@ -1,6 +1,7 @@
 # Development: build my_compress_amd/lib/libfcx_<name>.so with one source (default fcx_match) replaced by
 # a variant (the other objects from the current build), for tools/gpu_ab.sh; EXTRA: more compiler flags.
 #   [EXTRA="-mllvm ..."] bash tools/variant_lib.sh name file.hip [fcx_parse]
+# (a match unit's object, e.g. fcx_match_nf_listed: EXTRA carries its switches from csrc/Makefile's unit table)
 set -eu
 name=$1; src=$(readlink -f $2); tgt=${3:-fcx_match}
 cd "$(dirname "$0")/../my_compress_amd/csrc"
