@@ -12,6 +12,7 @@
 
 #include "fcx.h"
 #include "fcx_device.h"
+#include "fcx_sparse_filter.h"
 
 namespace fcx {
 // (the match units' launchers: fcx_device.h)
@@ -651,6 +652,27 @@ int fcx_debug_route_estimate(const uint64_t cnt[5], uint64_t valid, uint32_t ntg
 // ... and where a unit's remainder starts, given its grid in the plan and the call's 16 route counters
 uint32_t fcx_debug_rest_start(uint32_t grid, uint32_t unit, const uint32_t counters[16]) {
     return unit < kSearchUnits && counters ? rest_start(grid, unit, counters) : ~0u;
+}
+
+// development only (not in fcx.h): the sparse unit's repeat filter on the host (fcx_sparse_filter.h), for
+// the tests; no GPU.  The 3-byte keys at positions 0 .. nkeys - 1 of win (nkeys + 2 bytes) are inserted
+// in position order into an empty bitmap; flags (may be NULL): 1 per flagged position.
+// out: flagged count, the flagged-key cap, R's capacity, bits per key
+int fcx_debug_sparse_filter(const uint8_t *win, uint32_t nkeys, uint8_t *flags, uint32_t out[4]) {
+    if (!win || !out) return fail(FCX_ERR_ARG, "fcx_debug_sparse_filter: NULL");
+    std::vector<uint32_t> bm(kSfWords, 0u);
+    uint32_t nflag = 0;
+    for (uint32_t x = 0; x < nkeys; x++) {
+        const uint32_t key = (uint32_t)win[x] | ((uint32_t)win[x + 1] << 8) | ((uint32_t)win[x + 2] << 16);
+        const uint32_t bits = sf_bits(key);
+        uint32_t &w = bm[sf_word(key)];
+        const bool flagged = (w & bits) == bits;
+        w |= bits;
+        nflag += flagged;
+        if (flags) flags[x] = flagged;
+    }
+    out[0] = nflag; out[1] = kSfFlagCap; out[2] = kSfRCap; out[3] = kSfK;
+    return FCX_OK;
 }
 
 int fcx_ctx_info(fcx_ctx *c, int *device, uint32_t *block_bytes, uint64_t *shard_bytes) {

@@ -82,9 +82,15 @@
 // tile runs the repeat filter; a tile it does not send to the sparse search takes the whole-tile
 // run-table mode instead (exact for any tile, slow where the runs overflow the table:
 // fcx_ctx_set_match_mode 2); the sparse search is inlined.  Rand k_match 2.64 -> 2.31 ms per GiB
-// (DESIGN.md §4).
+// (DESIGN.md §4).  The unit has its own filter and search (fcx_sparse_filter.h, sparse_pairs below:
+// a handful of flagged keys per window instead of ~140 hash repeats, the equal keys found by
+// direct compares, no dup bitmap and no counting sort: 2.28 -> 2.02); the other
+// units keep the 17-bit filter and sparse_search.
 #ifndef FCX_SPARSE
 #define FCX_SPARSE 0
+#endif
+#if FCX_SPARSE
+#include "fcx_sparse_filter.h"   // the unit's own repeat filter (sparse_pairs below)
 #endif
 // FCX_NOBUCKET: no bucket search; a tile the repeat filter does not send to the sparse search takes
 // the whole-tile run-table mode (the sparse and runs units)
@@ -195,15 +201,27 @@ constexpr uint32_t kSparseEvents = 448;              // repeats up to which the 
 constexpr uint32_t kSampleWords = 128;               // repeat sample: 2^12-bit bitmap of 512 sampled keys
 constexpr uint32_t kSampleEvents = 96;               // sampled repeats above which the filter is skipped
 constexpr uint32_t kSparseBuckets = 1024;            // buckets of the sparse search's counting sort
+#if !FCX_SPARSE
 // sparse-search layout inside the region (words): step (u16 x 4096) | P | counters | sorted | mbits
 constexpr uint32_t kSpP = kTile / 2, kSpCnt = kSpP + 2 * kSparseEvents, kSpSrt = kSpCnt + kSparseBuckets / 2 + 2,
                    kSpMb = kSpSrt + kSparseEvents;   // P: u32 x 2 kSparseEvents; srt: u16 x 2 kSparseEvents
 static_assert(kSpMb % 2 == 0 && kSpMb + 128 <= kFilterWords - kTile, "sparse layout below the results");
+#endif
 constexpr uint32_t kBucketWords = kHeadWords + kEntWords > kTile / 2 + 3 * kMT + 1
                                       ? kHeadWords + kEntWords : kTile / 2 + 3 * kMT + 1;
 constexpr uint32_t kRegionWords = kBucketWords > kFilterWords ? kBucketWords : kFilterWords;
+#if FCX_SPARSE
+// the sparse unit's region (words): the filter's bitmap (fcx_sparse_filter.h) over its first kSfWords
+// words, later step (u16 x 4096) | the parse's scratch | results; past the bitmap the search's lists,
+// laid out while the bitmap is live: flagged keys | R | mbits
+constexpr uint32_t kResLds = kTile / 2 + 3 * kMT + 4;   // (results right after the parse scratch)
+constexpr uint32_t kSpP = kTile / 2, kSpKey = kResLds + kTile, kSpR = kSpKey + kSfFlagCap, kSpMb = kSpR + kSfRCap;
+static_assert(kSfWords <= kSpKey && kSpMb % 2 == 0 && kSpMb + 128 <= kRegionWords, "sparse lists past the bitmap");
+static_assert(kRegionWords == kFilterWords && kSfRCap <= kMT && kSfFlagCap <= 64, "sparse lists");
+#else
 constexpr uint32_t kResLds = kRegionWords - kTile;   // search results (m) per tile position, kept for the
                                                      // compact match list; clear of step and the parse scratch
+#endif
 static_assert(kResLds >= kTile / 2 + 3 * kMT + 1, "results clear of step and the parse scratch");
 // bucket scan pass B (bucket search only): each wave's hot-query slots and owner marks, in the
 // region words the counters and entries leave free
@@ -607,6 +625,7 @@ __device__ inline void scan_candidate(const uint32_t *sdw, uint32_t xe, uint32_t
 // compare, leftmost maximum, extension budget); every other position is a literal.
 // Writes step (LDS), m and the tile's mbits words.  Kept out of line: its registers do
 // not weigh on the bucket search.
+#if !FCX_SPARSE
 template <bool kDev>
 __device__ FCX_SPARSE_CALL void sparse_search(const uint32_t *sdw, uint32_t *region, uint32_t kw0, uint32_t kw1,
                                            uint32_t kw2, uint32_t kw3, uint32_t *s_red,
@@ -713,6 +732,117 @@ __device__ FCX_SPARSE_CALL void sparse_search(const uint32_t *sdw, uint32_t *reg
         if (tid < (ntile + 63) / 64) mbw[tid] = mbl[tid];
     }
 }
+#endif
+
+#if FCX_SPARSE
+// ---- 2b'. the sparse unit's search.  Its filter (fcx_sparse_filter.h) flags a handful of keys per
+// window of random data (about 3, against the ~140 hash repeats of the 17-bit filter above), and of
+// every set of equal keys in the window all but at most one are flagged.  So a flag means "this key
+// value repeats somewhere in the window", and the positions that really share a key are found
+// directly: the filter lists the flagged keys, every wave compares the list against its lanes' 12
+// keys (held in registers; one compare per key and entry, the hits gathered as wave masks in
+// scalar registers), and the positions that equal a listed key -- the flagged ones and their
+// unflagged partners -- form R.  Each R position inside the tile takes the other R entries of its
+// key in [x - 2047, x) as candidates, through scan_candidate.  No dup bitmap, no sort.
+// fm: this lane's flagged keys (bit r: window position 12 tid + r), fwave: its wave's flagged keys,
+// nflag: the window's (<= kSfFlagCap; their list and R entries are in place; the match words are 0
+// since the staging).  Writes step (LDS), m and the tile's mbits words like
+// sparse_search.  Returns false, with nothing of the tile written, when R overflows
+// (workgroup-uniform): the tile is not sparse.
+template <bool kDev>
+__device__ __forceinline__ bool sparse_pairs(const uint32_t *sdw, uint32_t *region, uint32_t kw0, uint32_t kw1,
+                                             uint32_t kw2, uint32_t kw3, uint32_t fm, uint32_t fwave, uint32_t nflag,
+                                             uint32_t *s_np, uint32_t *s_unknown, uint32_t *s_match, uint32_t *mrow,
+                                             uint64_t *mbw, uint32_t q0, uint32_t npos, uint32_t ins_end, uint32_t w0,
+                                             uint32_t blen, uint32_t ntile, uint32_t dbg_in) {
+    const uint32_t dbg = kDev ? uni(dbg_in) : 0u;
+    const uint32_t tid = FCX_TID, lane = tid & 63;
+    const uint32_t kw[4] = {kw0, kw1, kw2, kw3};
+    uint16_t *step = (uint16_t *)region;
+    const uint32_t *lkey = region + kSpKey;
+    uint32_t *R = region + kSpR;
+    uint64_t *mbl = (uint64_t *)(region + kSpMb);
+    // (the bitmap is dead: the caller's barrier after the filter)
+    static_assert(kTile / 2 / 4 == kMT, "one 16-B store per lane fills step");
+    ((uint4 *)region)[tid] = make_uint4(0x00010001u, 0x00010001u, 0x00010001u, 0x00010001u);   // step = 1 (literal)
+    // equal-key search: acc[r] = the wave's lanes whose key r equals a listed key
+    uint32_t ky[kIns];
+#pragma unroll
+    for (uint32_t r = 0; r < kIns; r++) ky[r] = __builtin_amdgcn_alignbyte(kw[(r >> 2) + 1], kw[r >> 2], r & 3) & 0xFFFFFFu;
+    uint64_t acc[kIns];
+#pragma unroll
+    for (uint32_t r = 0; r < kIns; r++) acc[r] = 0ull;
+    const uint32_t lk = lane < nflag ? lkey[lane] : 0u;   // (one read: no LDS round trip per entry)
+    for (uint32_t i = 0; i < nflag; i++) {
+        const uint32_t K = (uint32_t)__builtin_amdgcn_readlane((int)lk, (int)i);
+#pragma unroll
+        for (uint32_t r = 0; r < kIns; r++) acc[r] |= __ballot(ky[r] == K);
+    }
+    // every flagged key hits itself: a wave with as many hits as flagged keys has no partner
+    // (all but about one wave in ten of a random tile; scalar work only)
+    uint32_t nhit = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kIns; r++) nhit += (uint32_t)__builtin_popcountll(acc[r]);
+    if (nhit != fwave) {
+        uint32_t hit = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < kIns; r++) hit |= (uint32_t)((acc[r] >> lane) & 1ull) << r;
+        // the unflagged partners join R (the flagged are in it); keys past the block's end are none
+        const uint32_t nv = ins_end > kIns * tid ? min(kIns, ins_end - kIns * tid) : 0u;
+        hit &= ~fm & ((1u << nv) - 1u);
+        const uint32_t nh = (uint32_t)__builtin_popcount(hit);
+        if (__ballot(nh != 0)) {
+            const uint32_t inch = wave_incl_scan(nh);
+            uint32_t base = 0;
+            if (lane == 63) base = atomicAdd(s_np, inch);
+            base = nflag + (uint32_t)__builtin_amdgcn_readlane((int)base, 63) + inch - nh;
+            for (uint32_t bits = hit; bits; bits &= bits - 1, base++) {
+                const uint32_t x = kIns * tid + __builtin_ctz(bits);
+                if (base < kSfRCap) R[base] = x | (lds_key3(sdw, x) << 13);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t nr = nflag + *s_np;
+    if (nr > kSfRCap) return false;   // not sparse (nothing but this workgroup's LDS was written)
+    if (dbg & 32u) return true;       // timing: + filter and equal-key search
+    if ((tid & ~63u) < nr) {   // R entry tid is this lane's query; each wave holds 64 entries at a time
+        const uint32_t me = tid < nr ? R[tid] : 0u, x = me & 0x1FFFu;
+        const uint32_t i = w0 + x;
+        const bool q = tid < nr && !(x < q0 || x >= npos || i == 0 || blen - i < 4 || (dbg & 1u));
+        if (__ballot(q)) {
+            const uint32_t cap = q ? min(kMaxL, blen - i) - 1 : 0u;
+            const uint32_t xq = q ? x : 0u;
+            const uint32_t qa = lds_ld4(sdw, xq), qb = lds_ld4(sdw, xq + 4), qc = lds_ld4(sdw, xq + 8);
+            const uint32_t xlo = max(i, kWin) - kWin - w0;
+            uint32_t best = 0, next = 0;
+            bool unk = false;
+            for (uint32_t e0 = 0; e0 < nr; e0 += 64) {
+                const uint32_t rv = e0 + lane < nr ? R[e0 + lane] : 0u;
+                const uint32_t ne = min(64u, nr - e0);
+                for (uint32_t e = 0; e < ne; e++) {
+                    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)rv, (int)e), xe = o & 0x1FFFu;
+                    if (q && !unk && ((o ^ me) >> 13) == 0 && xe < x && xe >= xlo)
+                        scan_candidate(sdw, xe, x, qa, qb, qc, cap, best, next, unk, dbg);
+                }
+            }
+            const uint32_t Lb = best >> 13;
+            if (q && (unk || Lb >= kMinL)) {
+                const uint32_t res = unk ? kUnknown : m_pack(Lb, x - (8191u - (best & 0x1FFFu)));
+                mrow[x] = res;
+                region[kResLds + x - q0] = res;
+                step[x - q0] = (uint16_t)(unk ? 0u : Lb + 1);
+                atomicOr(&mbl[(x - q0) >> 6], 1ull << ((x - q0) & 63));
+                if (unk) *s_unknown = 1;
+                else *s_match = 1;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < (ntile + 63) / 64) mbw[tid] = mbl[tid];
+    return true;
+}
+#endif
 
 // ---- sparse tiles with a few matches (random data) ----
 // Every position is a literal except the handful of match positions the sparse search found,
@@ -1052,6 +1182,9 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
     };
 
     bool sparse = false;   // the sparse search ran (few repeated keys: random data)
+#if FCX_SPARSE
+    uint32_t sp_fm = 0, sp_wave = 0;   // this lane's flagged keys and its wave's count of them
+#endif
     if (rmode) {
         if (nruns_img == 1 && !(dbg & 12u)) {   // one byte value over the whole image (zeros)
             uniform_tile_out(region, s_red, mbits + (uint64_t)b * L.wpb,
@@ -1075,6 +1208,68 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
 #else
     if (s_sample <= kSampleEvents && !(dbg & 128u)) {
 #endif
+#if FCX_SPARSE
+    // (the sparse unit: one bitmap, kSfK bits per key in one word (fcx_sparse_filter.h); a key is
+    // flagged when all its bits were set.  Random data flags about 3 keys per window, so
+    // sparse_pairs finds the equal keys directly.)
+    {
+        // all 12 atomics in flight at once (same-word atomics serialise: of equal keys, every one
+        // but the first to run finds its bits set).  A wave whose 768 keys all exist (every wave but
+        // a block end's last) inserts them unchecked.
+        uint32_t old[kIns], fb[kIns];
+        (void)hash_of;
+        uint8_t *bm = (uint8_t *)region;
+        auto key_of = [&](uint32_t r) -> uint32_t {   // r: compile-time after unrolling
+            return __builtin_amdgcn_alignbyte(kw[(r >> 2) + 1], kw[r >> 2], r & 3) & 0xFFFFFFu;
+        };
+        if (uni(kIns * ((tid | 63u) + 1u)) <= ins_end) {
+#pragma unroll
+            for (uint32_t r = 0; r < kIns; r++) {
+                fb[r] = sf_bits(key_of(r));
+                old[r] = atomicOr((uint32_t *)(bm + sf_word_x4(key_of(r))), fb[r]);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t r = 0; r < kIns; r++) {
+                old[r] = 0;
+                fb[r] = 1u;   // (no key here: never flagged)
+                if (kIns * tid + r < ins_end) {
+                    fb[r] = sf_bits(key_of(r));
+                    old[r] = atomicOr((uint32_t *)(bm + sf_word_x4(key_of(r))), fb[r]);
+                }
+            }
+        }
+        uint64_t anyf = 0ull;
+#pragma unroll
+        for (uint32_t r = 0; r < kIns; r++) anyf |= __ballot((old[r] & fb[r]) == fb[r]);
+        if (anyf) {   // (about half of a random tile's waves flag nothing)
+#pragma unroll
+            for (uint32_t r = 0; r < kIns; r++)
+                if ((old[r] & fb[r]) == fb[r]) sp_fm |= 1u << r;
+            // the flagged keys' list slots, one reservation per wave: s_events counts them.  The
+            // lists lie below the bitmap, so they are written at once: the key values, and the
+            // flagged positions as R's first entries (position | key << 13, the key's low 19 bits)
+            const uint32_t nf = (uint32_t)__builtin_popcount(sp_fm);
+            const uint32_t incf = wave_incl_scan(nf);
+            uint32_t base = 0;
+            if ((tid & 63) == 63) base = atomicAdd(&s_events, incf);
+            base = (uint32_t)__builtin_amdgcn_readlane((int)base, 63) + incf - nf;
+            sp_wave = (uint32_t)__builtin_amdgcn_readlane((int)incf, 63);
+            for (uint32_t bits = sp_fm; bits; bits &= bits - 1, base++) {
+                const uint32_t x = kIns * tid + __builtin_ctz(bits);
+                const uint32_t key = lds_key3(sdw, x);
+                if (base < kSfFlagCap) {
+                    region[kSpKey + base] = key;
+                    region[kSpR + base] = x | (key << 13);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (dbg & 4096u) return;   // timing: + repeat filter
+    sparse = s_events <= kSfFlagCap;
+    }   // repeat filter
+#else
     uint32_t *seen = region, *dupm = region + kFilterWords / 2;   // (zeroed with the staging)
     {
         // all 12 "seen" atomics in flight at once (program order keeps a lane's own
@@ -1105,12 +1300,24 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
     if (dbg & 4096u) return;   // timing: + repeat filter
     sparse = s_events <= kSparseEvents;
     }   // repeat filter
+#endif
 
+#if FCX_SPARSE
+    // (R may overflow its capacity: the tile is then not sparse, with nothing of it written yet)
+    if (sparse)
+        sparse = sparse_pairs<kDev>(sdw, region, kw[0], kw[1], kw[2], kw[3], sp_fm, sp_wave, s_events, &s_np, &s_unknown,
+                                    &s_match, m + bstart + w0, mbits + (uint64_t)b * L.wpb + (t0 >> 6), q0, npos, ins_end,
+                                    w0, blen, t1 - t0, dbg);
+    if (sparse) {
+        __syncthreads();
+        if (dbg & 32u) return;
+#else
     if (sparse) {
         sparse_search<kDev>(sdw, region, kw[0], kw[1], kw[2], kw[3], s_red, &s_np, &s_unknown, &s_match, m + bstart + w0,
                       mbits + (uint64_t)b * L.wpb + (t0 >> 6), q0, npos, ins_end, w0, blen, t1 - t0, dbg);
         __syncthreads();
         if (dbg & 32u) return;
+#endif
 #if FCX_NOBUCKET
     } else if (kRt && rt.defer_list) {
         // not sparse, in a routed call: the tile goes on to the no-filter unit's list (launched after

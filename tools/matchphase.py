@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """k_match per-phase timing (development): the kernel alone through fcx_debug_match
-with phase exits (16: staging + run count, 32: + sort, 64: + queries, 0: whole)."""
+with phase exits (16: staging + run count, 4096: + repeat filter, 32: + sort (the sparse unit: +
+equal-key search), 64: + queries, 0: whole)."""
 import argparse, ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
