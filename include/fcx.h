@@ -16,6 +16,10 @@
  *                            per record                                            :4160-4204, :2255
  *                            (GPU decoder: every record of a device-resident run)
  *   fcx_decompress_host   <- the whole decompress mode of main() on host buffers  :4137-4204
+ *                            (FCX7 and FCX8: dispatch on the header's kind, :4140-4159)
+ *   fcx_lz78_decompress_shard <- main()'s per-block decompress loop for FCX8,
+ *                            my_decompress_file_lz78 per record                    :4160-4204, :3478
+ *                            (GPU decoder: every record of a device-resident run)
  *   fcx_dist_*            <- main()'s compress loop (:4090-4122) with the blocks spread over
  *                            several GPUs: contiguous block ranges per GPU, the segments
  *                            concatenated in block order over RCCL (the reference writes the
@@ -183,17 +187,21 @@ void fcx_dctx_destroy(fcx_dctx *ctx);
  * for malformed input, FCX_ERR_CAPACITY if cap is too small. */
 int fcx_decompress_shard(fcx_dctx *ctx, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
                          uint64_t cap, uint64_t *out_len, void *stream);
-/* Host-to-host: a whole FCX7 file (header included) into `out` (capacity cap),
+/* Host-to-host: a whole FCX7 or FCX8 file (header included) into `out` (capacity cap),
  * through fcx_decompress_stream. */
 int fcx_decompress_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap,
                         uint64_t *out_len);
-/* Streams an FCX7 file (header first) through the GPU decoder in groups of up
- * to 256 whole records; max_in (0 = unknown) bounds the staging buffers.
- * Reports the header's total (mod 2^32), the decoded bytes and the records. */
+/* Streams an FCX7 or FCX8 file (header first; the header's kind selects the decoder, as
+ * main() does, :4140-4159) through the GPU decoder in groups of up to 256 whole records;
+ * max_in (0 = unknown) bounds the staging buffers.  An FCX7 file is read to its end; of an
+ * FCX8 file the header's counted records are read (main() reads block_num records), in
+ * groups that also close when the next record (<= 10 len + 4096 bytes) would not fit the
+ * 128 MiB staging.  Reports the header's total (mod 2^32), the decoded bytes and the records. */
 int fcx_decompress_stream(fcx_dctx *ctx, fcx_read_fn read, fcx_write_fn write, void *user, uint64_t max_in,
                           uint32_t *hdr_total, uint64_t *total_out, uint64_t *nblocks);
 int fcx_dctx_device(fcx_dctx *ctx, int *device);
-/* per-stage hipEvent timing of subsequent fcx_decompress_shard calls */
+/* per-stage hipEvent timing of subsequent fcx_decompress_shard / fcx_lz78_decompress_shard calls;
+ * the stage functions report the last such call (FCX8: ms summed over its record batches) */
 int fcx_dctx_set_profiling(fcx_dctx *ctx, int enable);
 int fcx_dctx_stage_count(fcx_dctx *ctx);
 int fcx_dctx_stage(fcx_dctx *ctx, int i, const char **name, float *ms);
@@ -218,11 +226,25 @@ int fcx_lz78_release(void);
 uint32_t fcx_lz78_compress_block(const void *in, uint32_t len, uint8_t *out);
 /*   fcx_lz78_decompress_block <- my_decompress_file_lz78(void*, uInt32, FILE*)       :3478 (called at :4189)
  *   fcx_lz78_decompress_host  <- the whole decompress mode of main() for FCX8        :4137-4204
- * GPU decoder, one lane per record; keeps the reference's quirks (a block whose decoded
- * bytes end in 0x00 loses that byte, 3701-3703; a one-symbol char stream decodes as
- * zeros).  decompress_block returns decoded bytes or a negative FCX_ERR_*. */
+ * Both run the token-parallel GPU decoder below through a per-thread, lazily created fcx_dctx on
+ * the current device; it keeps the reference's quirks (a block whose decoded bytes end in 0x00
+ * loses that byte, 3701-3703; a one-symbol char stream decodes as zeros; symbols a stream runs
+ * out of are 0).  decompress_block returns decoded bytes or a negative FCX_ERR_*;
+ * decompress_host reads the header's counted records and ignores bytes after them. */
 int64_t fcx_lz78_decompress_block(const uint8_t *in, uint32_t len, uint8_t *out, uint64_t cap);
 int fcx_lz78_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap, uint64_t *out_len);
+/* FCX8 twin of fcx_decompress_shard: nblocks records ([u32 len][payload]..., the file
+ * without its header) of in_len device bytes at d_in -> decoded blocks back to back at
+ * d_out (device, capacity cap).  Bytes equal my_decompress_file_lz78's (:3478).  Runs on
+ * `stream`; records are decoded in batches of fcx_lz78_decode_batch_records(), with scratch (in
+ * the context, grown on demand) per token of the batch in flight, and the stream is synchronised
+ * once per batch (to size that scratch) and at the end.  FCX_ERR_ARG for a NULL ctx, d_in, d_out
+ * or out_len (before the device is touched); FCX_ERR_FORMAT "malformed record k" (1-based) for
+ * the first bad record; FCX_ERR_CAPACITY when the decoded bytes exceed cap. */
+int fcx_lz78_decompress_shard(fcx_dctx *ctx, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks,
+                              uint8_t *d_out, uint64_t cap, uint64_t *out_len, void *stream);
+/* records per internal batch of fcx_lz78_decompress_shard */
+uint32_t fcx_lz78_decode_batch_records(void);
 
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so

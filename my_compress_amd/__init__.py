@@ -106,6 +106,12 @@ def lib():
     L.fcx_lz78_decompress_block.restype = ctypes.c_int64
     L.fcx_lz78_decompress_host.argtypes = [c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64,
                                            ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "fcx_lz78_decompress_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        L.fcx_lz78_decompress_shard.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.c_void_p]
+        L.fcx_lz78_decode_batch_records.argtypes = []
+        L.fcx_lz78_decode_batch_records.restype = ctypes.c_uint32
     P64 = ctypes.POINTER(ctypes.c_uint64)
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
@@ -300,8 +306,17 @@ class DContext:
                                           cap, ctypes.byref(out), ctypes.c_void_p(stream)), "fcx_decompress_shard")
         return out.value
 
+    def decompress_lz78_shard(self, d_in: int, in_len: int, nblocks: int, d_out: int, cap: int,
+                              stream: int = 0) -> int:
+        """FCX8 records on the device in, decoded bytes at d_out; returns the decoded byte count"""
+        out = ctypes.c_uint64(0)
+        _check(lib().fcx_lz78_decompress_shard(self._h, ctypes.c_void_p(d_in), in_len, nblocks,
+                                               ctypes.c_void_p(d_out), cap, ctypes.byref(out),
+                                               ctypes.c_void_p(stream)), "fcx_lz78_decompress_shard")
+        return out.value
+
     def decompress_host(self, blob: bytes, cap: int = None) -> bytes:
-        """a whole FCX7 file -> the decoded bytes, on the GPU"""
+        """a whole FCX7 or FCX8 file -> the decoded bytes, on the GPU"""
         if cap is None:
             cap = max(16, struct.unpack_from("<I", blob, 4)[0] if len(blob) >= HEADER_BYTES else 0)
         out = ctypes.create_string_buffer(cap)
@@ -311,7 +326,7 @@ class DContext:
         return out.raw[:got.value]
 
     def decompress_stream(self, src, sink):
-        """FCX7 file from src (binary reader) to sink through the GPU decoder;
+        """FCX7 or FCX8 file from src (binary reader) to sink through the GPU decoder;
         returns (header total, decoded bytes, records)"""
         rd, wr = _stream_fns(src, sink)
         t = ctypes.c_uint32()
@@ -449,6 +464,11 @@ def decompress_lz78(blob: bytes, cap: int = None) -> bytes:
             continue
         _check(rc, "fcx_lz78_decompress_host")
         return out.raw[:n.value]
+
+
+def lz78_decode_batch_records() -> int:
+    """records per internal batch of DContext.decompress_lz78_shard (its scratch is per batch)"""
+    return int(lib().fcx_lz78_decode_batch_records())
 
 
 def lz78_release() -> None:

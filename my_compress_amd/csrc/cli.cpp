@@ -12,8 +12,8 @@
 // -d/--device N and -g/--gpus N (-c lz77 over N GPUs of this node, devices d .. d+N-1:
 // contiguous block ranges per GPU, segments gathered over RCCL, byte-identical
 // output).  `-c lz78` runs the LZ78 codec (FCX8) on the GPU: 256 MiB shards
-// through fcx_lz78_compress_host / fcx_lz78_decompress_host (whole files in host
-// memory for decompress).
+// through fcx_lz78_compress_host; an FCX8 file decompresses through
+// fcx_decompress_stream like an FCX7 one (GPU-only: no host decoder for FCX8).
 #include <getopt.h>
 
 #include <chrono>
@@ -201,32 +201,6 @@ static int compress_lz78(FILE *fin, FILE *fout, uint32_t block) {
     return 0;
 }
 
-static int decompress_lz78(FILE *fin, FILE *fout, uint32_t total) {
-    rewind(fin);
-    std::vector<uint8_t> blob;
-    uint8_t tmp[1 << 16];
-    size_t n;
-    while ((n = fread(tmp, 1, sizeof(tmp), fin)) > 0) blob.insert(blob.end(), tmp, tmp + n);
-    uint16_t nblocks;
-    memcpy(&nblocks, blob.data() + 8, 2);
-    // decoded bytes <= the header's total (mod 2^32; the reference decoder never adds
-    // bytes, it may drop a trailing 0x00 per block): size by it, and only when that
-    // fails on capacity (a total that wrapped) by the decoder's per-block bound (:2373)
-    std::vector<uint8_t> out((uint64_t)total + 64ull * nblocks + 64);
-    uint64_t got = 0;
-    int r = fcx_lz78_decompress_host(blob.data(), blob.size(), out.data(), out.size(), &got);
-    if (r == FCX_ERR_CAPACITY) {
-        out.assign((uint64_t)nblocks * (FCX_MAX_BLOCK_BYTES + 8) + 1, 0);
-        r = fcx_lz78_decompress_host(blob.data(), blob.size(), out.data(), out.size(), &got);
-    }
-    if (r) {
-        fprintf(stderr, "fcx: %s\n", fcx_last_error());
-        return -1;
-    }
-    fwrite(out.data(), 1, (size_t)got, fout);
-    return report(got, total);
-}
-
 static int do_decompress(FILE *fin, FILE *fout, int device) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -240,13 +214,16 @@ static int do_decompress(FILE *fin, FILE *fout, int device) {
         fprintf(stderr, "This file is not support to decompress!!!!\n");
         return -1;
     }
-    if (kind != '7') return decompress_lz78(fin, fout, total);
     fcx_dctx *d = nullptr;
     if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
         return decompress_host(fin, fout, total, nblocks);
     }
-    // GPU decoder over whole records (the stream path re-reads the header)
+    // GPU decoder over whole records, FCX7 and FCX8 alike (the stream path re-reads the header)
     rewind(fin);
     Files io{fin, fout};
     uint64_t got_total = 0, nrec = 0;

@@ -28,6 +28,10 @@
 //             the tokens whose output fits an LDS tile, scatters literal bytes
 //             and copy links (x -> x - p), and resolves the links by pointer
 //             jumping against the tile and the 2 KiB history before it.
+//
+// The bit reader, the table probes, the segment decoder and the block scan are in
+// fcx_dec_shared.h, which the FCX8 decoder (fcx_lz78_dec.hip) includes as well; it also
+// runs k_dtable and k_dsyms on its char streams (dec_launch_tables8 / dec_launch_syms8).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -38,32 +42,15 @@
 
 #include "fcx.h"
 #include "fcx_device.h"
+#include "fcx_dec_shared.h"
 
 namespace fcx {
 void set_last_error(const std::string &m);
 
-// device error bits of the decoder
-constexpr uint32_t kDErrRecord = 1, kDErrHeader = 2, kDErrTree = 4, kDErrGolomb = 8, kDErrDist = 16,
-                   kDErrOutCap = 32, kDErrScratch = 64;
-
-constexpr uint32_t kDSymThreads = 1024;
 constexpr uint32_t kDLzThreads = 1024;
 constexpr uint32_t kDLzTile = 8192;              // output bytes resolved per LDS step
 constexpr uint32_t kDLzTPT = 4;                  // tokens read per lane and step
-constexpr uint32_t kDTblBits = 10;
 constexpr uint32_t kMaxTokensPerBlock = FCX_MAX_BLOCK_BYTES;
-
-struct DStream {         // one Huffman sub-stream (or the raw flags byte)
-    uint64_t words_bit;  // absolute bit offset of the code words in the input
-    uint64_t pairs_off;  // byte offset of the (l, r) pairs; bitmap is just before
-    uint64_t dst;        // byte offset of the decoded symbols in the symbol scratch
-    uint32_t nbits;      // 32 W
-    uint32_t count;      // symbols to produce
-    uint32_t ts;         // internal nodes (0: single symbol, decodes as zeros)
-    uint32_t raw;        // 1: no Huffman stream, `rawv` is the one flags byte (nb <= 1)
-    uint32_t rawv;
-    uint32_t pad;
-};
 
 struct DBlock {
     uint64_t payload_off;   // byte offset of the payload in the input
@@ -77,10 +64,6 @@ struct DBlock {
     uint32_t glen_got;      // golomb values decoded
     uint32_t pad[2];
 };
-
-__device__ inline uint32_t ld_u32le(const uint8_t *p, uint64_t off) {
-    return p[off] | (p[off + 1] << 8) | (p[off + 2] << 16) | ((uint32_t)p[off + 3] << 24);
-}
 
 // ---------------------------------------------------------------------------
 __global__ void k_dindex(const uint8_t *in, uint64_t in_len, uint32_t nblocks, DBlock *blk, uint32_t *err) {
@@ -239,9 +222,10 @@ __global__ void k_dscan(uint32_t nblocks, DBlock *blk, DStream *ds, const uint64
 // decode tables: one wave per (block, stream) with a tree.
 // tbl[1024] u16: bit 15 clear: symbol | len << 8 (len <= 10); bit 15 set: continue
 // the tree walk from internal node (entry & 0x1FF) after 10 bits; 0xFFFF: invalid.
-// child[2 * 256] u16: < 256 leaf symbol, 256 + k internal node k.
+// child[2 * 256] u16: < 256 leaf symbol, 256 + k internal node k.  A bad tree sets kDErrTree and
+// lowers *badq (when given) to its stream.
 __global__ __launch_bounds__(64) void k_dtable(const uint8_t *in, uint32_t nblocks, const DStream *ds,
-                                               uint16_t *tbl, uint16_t *child, uint32_t *err) {
+                                               uint16_t *tbl, uint16_t *child, uint32_t *err, uint32_t *badq) {
     __shared__ uint16_t ch[512];
     __shared__ uint16_t par[256];    // parent node | side << 15; 0xFFFF = none
     __shared__ uint8_t dep[256];
@@ -312,245 +296,13 @@ __global__ __launch_bounds__(64) void k_dtable(const uint8_t *in, uint32_t nbloc
         }
     }
     __syncthreads();
-    if (lane == 0 && bad) atomicOr(err, kDErrTree);
+    if (lane == 0 && bad) {
+        atomicOr(err, kDErrTree);
+        if (badq) atomicMin(badq, q);
+    }
 }
 
 // ---------------------------------------------------------------------------
-// LSB-first sequential bit reader: a 64-bit register buffer fed from a queue of
-// four dwords (one 16-B load), with the next 16-B load in flight: the wait for a
-// load falls every 128 bits consumed, one load behind.  The byte buffer of `len`
-// bytes starts at bit `bit0` of its 16-B-aligned base.
-struct BitBuf {
-    const uint32_t *w;   // 16-B-aligned base
-    uint64_t nw;         // dwords that hold valid bytes
-    uint64_t buf, ni;    // ni: next 16-B unit to load
-    uint32_t nbuf, qn, q0, q1, q2, q3;
-    uint4 nxt;
-    __device__ uint4 load4(uint64_t i) const {
-        if (4 * i + 4 <= nw) return ((const uint4 *)w)[i];
-        uint4 v;
-        v.x = 4 * i < nw ? w[4 * i] : 0u;
-        v.y = 4 * i + 1 < nw ? w[4 * i + 1] : 0u;
-        v.z = 4 * i + 2 < nw ? w[4 * i + 2] : 0u;
-        v.w = 4 * i + 3 < nw ? w[4 * i + 3] : 0u;
-        return v;
-    }
-    __device__ uint32_t pop() {
-        const uint32_t v = q0;
-        q0 = q1; q1 = q2; q2 = q3;
-        if (--qn == 0) {
-            q0 = nxt.x; q1 = nxt.y; q2 = nxt.z; q3 = nxt.w;
-            qn = 4;
-            nxt = load4(ni++);
-        }
-        return v;
-    }
-    __device__ void refill() {
-        if (nbuf <= 32) { buf |= (uint64_t)pop() << nbuf; nbuf += 32; }
-    }
-    __device__ void seek(uint64_t absbit) {   // afterwards >= 33 bits are buffered
-        const uint64_t wi = absbit >> 5, i4 = wi >> 2;
-        const uint4 c = load4(i4);
-        nxt = load4(i4 + 1);
-        ni = i4 + 2;
-        const uint32_t skip = (uint32_t)(wi & 3);
-        q0 = c.x; q1 = c.y; q2 = c.z; q3 = c.w;
-        qn = 4;
-        for (uint32_t k = 0; k < skip; k++) (void)pop();
-        buf = pop();
-        nbuf = 32;
-        buf >>= (absbit & 31);
-        nbuf -= (uint32_t)(absbit & 31);
-        refill();
-    }
-    __device__ uint32_t peek() const { return (uint32_t)buf; }
-    __device__ void drop(uint32_t n) { buf >>= n; nbuf -= n; refill(); }   // n <= 32
-};
-
-__device__ inline BitBuf make_bits(const uint8_t *buf, uint64_t len, uint64_t &bit0) {
-    const uintptr_t a = (uintptr_t)buf;
-    BitBuf s;
-    s.w = (const uint32_t *)(a & ~(uintptr_t)15);
-    bit0 = 8 * (a & 15);
-    s.nw = ((a & 15) + len + 3) / 4;
-    s.buf = 0; s.ni = 0; s.nbuf = 0; s.qn = 0; s.q0 = s.q1 = s.q2 = s.q3 = 0;
-    s.nxt = make_uint4(0, 0, 0, 0);
-    return s;
-}
-
-// one Huffman symbol from the low bits of a 32-bit window; len = 0 if none
-__device__ inline uint32_t huff_sym(uint32_t win, const uint16_t *T, const uint16_t *C, uint32_t &len) {
-    const uint32_t e = T[win & ((1u << kDTblBits) - 1)];
-    if (!(e & 0x8000u)) { len = (e >> 8) & 0x1Fu; return e & 0xFFu; }
-    len = 0;
-    if (e == 0xFFFFu) return 0;
-    uint32_t node = e & 0x1FFu;
-    win >>= kDTblBits;
-    for (uint32_t d = kDTblBits + 1; d <= 32; d++) {   // codes are <= 32 bits (k_dtable)
-        const uint32_t nx = C[2 * node + (win & 1u)];
-        win >>= 1;
-        if (nx < 256) { len = d; return nx; }
-        node = nx - 256;
-    }
-    return 0;
-}
-
-// one code at relative bit `pos` (the reader is positioned there); false if the
-// stream cannot supply it.  Golomb-Rice (golomb_rice_decode 309-358): q ones, a
-// zero, r in 2 bits, value 4q + r.
-template <bool GOLOMB>
-__device__ inline bool code_step(BitBuf &bb, uint32_t &pos, uint32_t nbits, const uint16_t *T, const uint16_t *C,
-                                 uint32_t &v) {
-    if (!GOLOMB) {
-        uint32_t len;
-        v = huff_sym(bb.peek(), T, C, len);
-        if (len == 0 || pos + len > nbits) return false;
-        bb.drop(len);
-        pos += len;
-        return true;
-    }
-    uint32_t q = 0;
-    for (;;) {
-        const uint32_t w = bb.peek();
-        if (w == 0xFFFFFFFFu) {
-            q += 32;
-            pos += 32;
-            if (pos + 3 > nbits) return false;
-            bb.drop(32);
-            continue;
-        }
-        const uint32_t ones = (uint32_t)__builtin_ctz(~w);
-        q += ones;
-        pos += ones;
-        if (pos + 3 > nbits) return false;
-        bb.drop(ones);
-        v = 4 * q + ((bb.peek() >> 1) & 3u);
-        bb.drop(3);
-        pos += 3;
-        return true;
-    }
-}
-
-// Segment decoder: one workgroup decodes `count` symbols of an nbits stream at
-// absolute bit sb.  Lane i owns bits [i S, (i+1) S) (S = nbits / lanes, a multiple
-// of 32) and decodes the codes that START there.  The first code boundary in each
-// segment is agreed by a Jacobi fixed point, start_{i+1} = exit of segment i
-// walked from start_i; only lanes whose start moved walk again.  Huffman codes
-// resynchronise within a few symbols, so this settles in 2-3 rounds; past
-// kDMaxRounds the lanes walk one after another (exact, serial).  Then a scan of
-// the counts and a second walk that stores the symbols.  Returns symbols produced.
-constexpr uint32_t kDMaxRounds = 12;
-constexpr uint32_t kDMinSegBits = 256;
-constexpr uint32_t kDRetryScale = 16;   // an unsettled stream retries with segments this much longer
-
-template <bool GOLOMB>
-__device__ uint32_t seg_decode(const BitBuf &src, uint64_t sb, uint32_t nbits, uint32_t count, const uint16_t *T,
-                               const uint16_t *C, uint8_t *dst8, uint32_t *dst32, uint32_t *st, uint32_t *cnt,
-                               uint32_t *flag, uint64_t *stats) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr uint32_t kW = kDSymThreads / 64;
-    // segments of >= kDMinSegBits (Jacobi needs room to resynchronise), a multiple of 32
-    const uint32_t S0 = max(kDMinSegBits, ((nbits + kDSymThreads - 1) / kDSymThreads + 31) & ~31u);
-    uint32_t seg_lo = 0, seg_hi = 0;
-    auto walk = [&](uint32_t start, uint32_t &ex) -> uint32_t {
-        BitBuf bb = src;
-        uint32_t pos = start, n = 0, v;
-        bool ok = true;
-        if (pos < seg_hi) bb.seek(sb + pos);
-        while (pos < seg_hi) {
-            if (!code_step<GOLOMB>(bb, pos, nbits, T, C, v)) { ok = false; break; }
-            n++;
-        }
-        ex = ok ? pos : nbits;   // a code that cannot complete ends the stream
-        return n;
-    };
-    bool settled = false;
-    uint32_t rounds = 0, mine = 0, ex = 0, n = 0;
-    // codes that resynchronise slowly (near fixed-length, e.g. the packed distance
-    // bytes) may not settle within short segments: a second attempt uses longer ones
-    for (uint32_t attempt = 0; attempt < 2 && !settled; attempt++) {
-        const uint64_t S = attempt == 0 ? S0 : (uint64_t)S0 * kDRetryScale;
-        seg_lo = (uint32_t)min<uint64_t>(tid * S, nbits);
-        seg_hi = (uint32_t)min<uint64_t>(seg_lo + S, nbits);
-        __syncthreads();
-        st[tid] = seg_lo;
-        if (tid == 0) { flag[0] = 0; flag[1] = 0; }
-        __syncthreads();
-        mine = seg_lo;
-        n = walk(mine, ex);
-        for (uint32_t round = 0; round < kDMaxRounds; round++) {
-            if (tid == 0) flag[(round + 1) & 1] = 0;
-            if (tid + 1 < kDSymThreads && st[tid + 1] != ex) { st[tid + 1] = ex; flag[round & 1] = 1; }
-            __syncthreads();
-            rounds++;
-            if (!flag[round & 1]) { settled = true; break; }
-            if (st[tid] != mine) { mine = st[tid]; n = walk(mine, ex); }
-            __syncthreads();
-        }
-    }
-    if (!settled) {   // serial fallback over the long segments: every start exact before its lane walks
-        const uint32_t active = (uint32_t)min<uint64_t>(kDSymThreads, (nbits + (uint64_t)S0 * kDRetryScale - 1) /
-                                                                         ((uint64_t)S0 * kDRetryScale));
-        for (uint32_t i = 0; i < active; i++) {
-            if (tid == i) {
-                mine = st[i];
-                n = walk(mine, ex);
-                if (i + 1 < kDSymThreads) st[i + 1] = ex;
-            }
-            __syncthreads();
-        }
-        mine = st[tid];
-        if (tid >= active) n = 0;
-    }
-    if (tid == 0 && stats) {   // Jacobi rounds, serial fallbacks
-        atomicAdd((unsigned long long *)stats, (unsigned long long)rounds);
-        if (!settled) atomicAdd((unsigned long long *)stats + 1, 1ull);
-        if (!settled && !GOLOMB) atomicAdd((unsigned long long *)stats + 4 + (blockIdx.x & 3), 1ull);
-    }
-    // exclusive scan of the per-lane counts
-    uint32_t inc = n;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += t;
-    }
-    if (lane == 63) cnt[wv] = inc;
-    __syncthreads();
-    uint32_t idx = inc - n, tot = 0;
-    for (uint32_t w = 0; w < kW; w++) {
-        if (w < wv) idx += cnt[w];
-        tot += cnt[w];
-    }
-    // walk again and store
-    if (mine < seg_hi && idx < count) {
-        BitBuf bb = src;
-        uint32_t pos = mine, v;
-        bb.seek(sb + pos);
-        const uint32_t stop = min(count, idx + n);
-        if (GOLOMB) {
-            while (idx < stop && code_step<GOLOMB>(bb, pos, nbits, T, C, v)) dst32[idx++] = v;
-        } else {
-            // whole dwords inside this lane's range are stored at once; the partial
-            // dwords at its two ends (shared with neighbours) byte by byte
-            const uint32_t first = idx;
-            uint32_t acc = 0;
-            while (idx < stop && code_step<GOLOMB>(bb, pos, nbits, T, C, v)) {
-                acc |= v << (8 * (idx & 3));
-                if ((idx & 3) == 3) {
-                    if (idx - 3 >= first) ((uint32_t *)dst8)[idx >> 2] = acc;
-                    else
-                        for (uint32_t q = first; q <= idx; q++) dst8[q] = (uint8_t)(acc >> (8 * (q & 3)));
-                    acc = 0;
-                }
-                idx++;
-            }
-            if (idx & 3)
-                for (uint32_t q = max(first, idx & ~3u); q < idx; q++) dst8[q] = (uint8_t)(acc >> (8 * (q & 3)));
-        }
-    }
-    __syncthreads();
-    return min(tot, count);
-}
-
 // one workgroup per sub-stream: Huffman symbols into the symbol scratch.  64 VGPRs (a few
 // spilled) for two workgroups per CU: the serial code walks are latency-bound, and twice
 // the waves took text's symbol streams from 15.1 to 9.9 ms per GiB
@@ -656,26 +408,6 @@ __global__ __launch_bounds__(kDSymThreads) void k_dgolomb(uint32_t nblocks, DBlo
 }
 
 // ---------------------------------------------------------------------------
-// block-wide exclusive scan (blockDim.x threads, <= 16 waves); returns the prefix, total in *tot
-__device__ inline uint32_t block_xscan(uint32_t v, uint32_t *sh, uint32_t *tot) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += t;
-    }
-    if (lane == 63) sh[wv] = inc;
-    __syncthreads();
-    uint32_t pre = inc - v, all = 0;
-    for (uint32_t w = 0; w < nw; w++) {
-        const uint32_t x = sh[w];
-        if (w < wv) pre += x;
-        all += x;
-    }
-    __syncthreads();
-    *tot = all;
-    return pre;
-}
 
 // one workgroup per block: tokens decoded (the reference stops at the first match
 // token past pCnt, 2331-2335), matches among them, decoded length
@@ -974,7 +706,7 @@ void dec_launch(const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t 
     }
     auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], st); };
     mark(0);
-    hipLaunchKernelGGL(k_dtable, dim3(4 * nblocks), dim3(64), 0, st, d_in, nblocks, ds, tbl, child, err);
+    hipLaunchKernelGGL(k_dtable, dim3(4 * nblocks), dim3(64), 0, st, d_in, nblocks, ds, tbl, child, err, (uint32_t *)nullptr);
     mark(1);
     hipLaunchKernelGGL(k_dsyms, dim3(4 * nblocks), dim3(kDSymThreads), 0, st, d_in, in_len, nblocks, ds, tbl, child, sym, err,
                        words + 4);
@@ -986,6 +718,18 @@ void dec_launch(const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t 
     mark(4);
     hipLaunchKernelGGL(k_dlz, dim3(nblocks), dim3(kDLzThreads), 0, st, nblocks, blk, ds, sym, glen, d_out, err);
     mark(5);
+}
+
+void dec_launch_tables8(const uint8_t *d_in, uint32_t nstreams, const DStream *ds, uint16_t *tbl, uint16_t *child,
+                        uint32_t *err, uint32_t *badq, hipStream_t st) {
+    hipLaunchKernelGGL(k_dtable, dim3(nstreams), dim3(64), 0, st, d_in, nstreams / 4, ds, tbl, child, err, badq);
+}
+
+void dec_launch_syms8(const uint8_t *d_in, uint64_t in_len, uint32_t nstreams, const DStream *ds,
+                      const uint16_t *tbl, const uint16_t *child, uint8_t *sym, const uint32_t *err,
+                      uint64_t *stats, hipStream_t st) {
+    hipLaunchKernelGGL(k_dsyms, dim3(nstreams), dim3(kDSymThreads), 0, st, d_in, in_len, nstreams / 4, ds, tbl, child, sym,
+                       err, stats);
 }
 
 }  // namespace fcx
@@ -1005,25 +749,10 @@ int dfail(int code, const std::string &m) {
         if (e_ != hipSuccess) return dfail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 const char *kDStageNames[] = {"tables", "symbols", "golomb", "lengths", "lz"};
-constexpr int kDStages = 5;
+// the FCX8 stages (fcx_lz78_dec.hip records them)
+const char *kD78StageNames[] = {"header", "index", "tables", "symbols", "links", "expand"};
+static_assert(sizeof(kD78StageNames) / sizeof(kD78StageNames[0]) == kD78Stages, "FCX8 stage names");
 }  // namespace
-
-struct fcx_dctx {
-    int device = 0;
-    uint32_t cap_blocks = 0;
-    uint64_t sym_cap = 0, glen_cap = 0;
-    DBlock *blk = nullptr;
-    DStream *ds = nullptr;
-    uint64_t *symb = nullptr;
-    uint16_t *tbl = nullptr, *child = nullptr;
-    uint8_t *sym = nullptr;
-    uint32_t *glen = nullptr;
-    uint64_t *words = nullptr;        // [0] total out, [1] error bits, [2] symbol bytes, [3] golomb values,
-                                      // [4..7] Jacobi rounds / serial fallbacks (symbols, golomb)
-    uint64_t *host_words = nullptr;
-    bool profiling = false, timed = false;
-    hipEvent_t ev[kDStages + 1] = {};
-};
 
 namespace {
 template <typename T>
@@ -1056,6 +785,7 @@ int fcx_dctx_create(fcx_dctx **out, int device) {
         return dfail(FCX_ERR_NOMEM, "fcx_dctx_create: allocation failed");
     }
     for (auto &e : c->ev) (void)hipEventCreate(&e);
+    for (auto &e : c->ev78) (void)hipEventCreate(&e);
     *out = c;
     return FCX_OK;
 }
@@ -1067,8 +797,11 @@ void fcx_dctx_destroy(fcx_dctx *c) {
     void *ptrs[] = {c->blk, c->ds, c->symb, c->tbl, c->child, c->sym, c->glen, c->words};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (c->lz78 && c->lz78_free) c->lz78_free(c->lz78);
     if (c->host_words) (void)hipHostFree(c->host_words);
     for (auto &e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev78)
         if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1079,9 +812,15 @@ int fcx_dctx_set_profiling(fcx_dctx *c, int enable) {
     return FCX_OK;
 }
 
-int fcx_dctx_stage_count(fcx_dctx *c) { return c && c->timed ? kDStages : 0; }
+int fcx_dctx_stage_count(fcx_dctx *c) { return !c ? 0 : c->timed78 ? kD78Stages : c->timed ? kDStages : 0; }
 
 int fcx_dctx_stage(fcx_dctx *c, int i, const char **name, float *ms) {
+    if (c && c->timed78) {   // the last call was fcx_lz78_decompress_shard: ms summed over its batches
+        if (i < 0 || i >= kD78Stages) return dfail(FCX_ERR_ARG, "bad stage");
+        if (name) *name = kD78StageNames[i];
+        if (ms) *ms = c->ms78[i];
+        return FCX_OK;
+    }
     if (!c || i < 0 || i >= kDStages || !c->timed) return dfail(FCX_ERR_ARG, "bad stage / not profiled");
     DHIP(hipEventSynchronize(c->ev[kDStages]));
     float v = 0;
@@ -1097,6 +836,7 @@ int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint
     hipStream_t st = (hipStream_t)stream;
     DHIP(hipSetDevice(c->device));
     c->timed = false;
+    c->timed78 = false;
     if (nblocks == 0) {
         if (out_len) *out_len = 0;
         return FCX_OK;

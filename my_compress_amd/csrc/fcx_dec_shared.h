@@ -1,0 +1,363 @@
+// fcx_dec_shared.h — device code and context shared by the GPU decoders: fcx_dec.hip (FCX7) and
+// fcx_lz78_dec.hip (FCX8).  The sequential bit reader, the Huffman table probes, the segment
+// decoder (Jacobi-synchronised parallel entropy decode) and the block scan live here once.
+#ifndef FCX_DEC_SHARED_H
+#define FCX_DEC_SHARED_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace fcx {
+
+// device error bits of the decoders
+constexpr uint32_t kDErrRecord = 1, kDErrHeader = 2, kDErrTree = 4, kDErrGolomb = 8, kDErrDist = 16,
+                   kDErrOutCap = 32, kDErrScratch = 64;
+
+constexpr uint32_t kDSymThreads = 1024;
+constexpr uint32_t kDTblBits = 10;
+
+struct DStream {         // one Huffman sub-stream (or the raw flags byte)
+    uint64_t words_bit;  // absolute bit offset of the code words in the input
+    uint64_t pairs_off;  // byte offset of the (l, r) pairs; bitmap is just before
+    uint64_t dst;        // byte offset of the decoded symbols in the symbol scratch
+    uint32_t nbits;      // 32 W
+    uint32_t count;      // symbols to produce
+    uint32_t ts;         // internal nodes (0: single symbol, decodes as zeros)
+    uint32_t raw;        // 1: no Huffman stream, `rawv` is the one flags byte (nb <= 1)
+    uint32_t rawv;
+    uint32_t pad;
+};
+
+__device__ inline uint32_t ld_u32le(const uint8_t *p, uint64_t off) {
+    return p[off] | (p[off + 1] << 8) | (p[off + 2] << 16) | ((uint32_t)p[off + 3] << 24);
+}
+
+// ---------------------------------------------------------------------------
+// LSB-first sequential bit reader: a 64-bit register buffer fed from a queue of
+// four dwords (one 16-B load), with the next 16-B load in flight: the wait for a
+// load falls every 128 bits consumed, one load behind.  The byte buffer of `len`
+// bytes starts at bit `bit0` of its 16-B-aligned base.
+struct BitBuf {
+    const uint32_t *w;   // 16-B-aligned base
+    uint64_t nw;         // dwords that hold valid bytes
+    uint64_t buf, ni;    // ni: next 16-B unit to load
+    uint32_t nbuf, qn, q0, q1, q2, q3;
+    uint4 nxt;
+    __device__ uint4 load4(uint64_t i) const {
+        if (4 * i + 4 <= nw) return ((const uint4 *)w)[i];
+        uint4 v;
+        v.x = 4 * i < nw ? w[4 * i] : 0u;
+        v.y = 4 * i + 1 < nw ? w[4 * i + 1] : 0u;
+        v.z = 4 * i + 2 < nw ? w[4 * i + 2] : 0u;
+        v.w = 4 * i + 3 < nw ? w[4 * i + 3] : 0u;
+        return v;
+    }
+    __device__ uint32_t pop() {
+        const uint32_t v = q0;
+        q0 = q1; q1 = q2; q2 = q3;
+        if (--qn == 0) {
+            q0 = nxt.x; q1 = nxt.y; q2 = nxt.z; q3 = nxt.w;
+            qn = 4;
+            nxt = load4(ni++);
+        }
+        return v;
+    }
+    __device__ void refill() {
+        if (nbuf <= 32) { buf |= (uint64_t)pop() << nbuf; nbuf += 32; }
+    }
+    __device__ void seek(uint64_t absbit) {   // afterwards >= 33 bits are buffered
+        const uint64_t wi = absbit >> 5, i4 = wi >> 2;
+        const uint4 c = load4(i4);
+        nxt = load4(i4 + 1);
+        ni = i4 + 2;
+        const uint32_t skip = (uint32_t)(wi & 3);
+        q0 = c.x; q1 = c.y; q2 = c.z; q3 = c.w;
+        qn = 4;
+        for (uint32_t k = 0; k < skip; k++) (void)pop();
+        buf = pop();
+        nbuf = 32;
+        buf >>= (absbit & 31);
+        nbuf -= (uint32_t)(absbit & 31);
+        refill();
+    }
+    __device__ uint32_t peek() const { return (uint32_t)buf; }
+    __device__ void drop(uint32_t n) { buf >>= n; nbuf -= n; refill(); }   // n <= 32
+};
+
+__device__ inline BitBuf make_bits(const uint8_t *buf, uint64_t len, uint64_t &bit0) {
+    const uintptr_t a = (uintptr_t)buf;
+    BitBuf s;
+    s.w = (const uint32_t *)(a & ~(uintptr_t)15);
+    bit0 = 8 * (a & 15);
+    s.nw = ((a & 15) + len + 3) / 4;
+    s.buf = 0; s.ni = 0; s.nbuf = 0; s.qn = 0; s.q0 = s.q1 = s.q2 = s.q3 = 0;
+    s.nxt = make_uint4(0, 0, 0, 0);
+    return s;
+}
+
+// one Huffman symbol from the low bits of a 32-bit window; len = 0 if none
+__device__ inline uint32_t huff_sym(uint32_t win, const uint16_t *T, const uint16_t *C, uint32_t &len) {
+    const uint32_t e = T[win & ((1u << kDTblBits) - 1)];
+    if (!(e & 0x8000u)) { len = (e >> 8) & 0x1Fu; return e & 0xFFu; }
+    len = 0;
+    if (e == 0xFFFFu) return 0;
+    uint32_t node = e & 0x1FFu;
+    win >>= kDTblBits;
+    for (uint32_t d = kDTblBits + 1; d <= 32; d++) {   // codes are <= 32 bits (k_dtable)
+        const uint32_t nx = C[2 * node + (win & 1u)];
+        win >>= 1;
+        if (nx < 256) { len = d; return nx; }
+        node = nx - 256;
+    }
+    return 0;
+}
+
+// The wide form of the same probe, for alphabets past 256 symbols (the FCX8 group ids, up to
+// ~4100): T is 1024 u32 entries (handed over as u16 *), bit 31 clear: symbol | len << 16; bit 31
+// set: continue from internal node (entry & 0x7FFF) after 10 bits; 0xFFFFFFFF invalid.  C holds
+// 2 u16 children per node: bit 15 set = internal node (low 15 bits), else the leaf's symbol.
+constexpr uint32_t kWideNode = 0x8000u;
+__device__ inline uint32_t huff_sym_wide(uint32_t win, const uint16_t *T, const uint16_t *C, uint32_t &len) {
+    const uint32_t e = ((const uint32_t *)T)[win & ((1u << kDTblBits) - 1)];
+    if (!(e & 0x80000000u)) { len = (e >> 16) & 0x3Fu; return e & 0xFFFFu; }
+    len = 0;
+    if (e == 0xFFFFFFFFu) return 0;
+    uint32_t node = e & 0x7FFFu;
+    win >>= kDTblBits;
+    for (uint32_t d = kDTblBits + 1; d <= 32; d++) {   // codes are <= 32 bits (the table builder checks)
+        const uint32_t nx = C[2 * node + (win & 1u)];
+        win >>= 1;
+        if (!(nx & kWideNode)) { len = d; return nx; }
+        node = nx & 0x7FFFu;
+    }
+    return 0;
+}
+
+// the code kinds the segment decoder walks
+constexpr int kCodeHuff = 0, kCodeGolomb = 1, kCodeHuffWide = 2;
+
+// one code at relative bit `pos` (the reader is positioned there); false if the
+// stream cannot supply it.  Golomb-Rice (golomb_rice_decode 309-358): q ones, a
+// zero, r in 2 bits, value 4q + r.
+template <int MODE>
+__device__ inline bool code_step(BitBuf &bb, uint32_t &pos, uint32_t nbits, const uint16_t *T, const uint16_t *C,
+                                 uint32_t &v) {
+    if (MODE != kCodeGolomb) {
+        uint32_t len;
+        v = MODE == kCodeHuffWide ? huff_sym_wide(bb.peek(), T, C, len) : huff_sym(bb.peek(), T, C, len);
+        if (len == 0 || pos + len > nbits) return false;
+        bb.drop(len);
+        pos += len;
+        return true;
+    }
+    uint32_t q = 0;
+    for (;;) {
+        const uint32_t w = bb.peek();
+        if (w == 0xFFFFFFFFu) {
+            q += 32;
+            pos += 32;
+            if (pos + 3 > nbits) return false;
+            bb.drop(32);
+            continue;
+        }
+        const uint32_t ones = (uint32_t)__builtin_ctz(~w);
+        q += ones;
+        pos += ones;
+        if (pos + 3 > nbits) return false;
+        bb.drop(ones);
+        v = 4 * q + ((bb.peek() >> 1) & 3u);
+        bb.drop(3);
+        pos += 3;
+        return true;
+    }
+}
+
+// Segment decoder: one workgroup decodes `count` symbols of an nbits stream at
+// absolute bit sb.  Lane i owns bits [i S, (i+1) S) (S = nbits / lanes, a multiple
+// of 32) and decodes the codes that START there.  The first code boundary in each
+// segment is agreed by a Jacobi fixed point, start_{i+1} = exit of segment i
+// walked from start_i; only lanes whose start moved walk again.  Huffman codes
+// resynchronise within a few symbols, so this settles in 2-3 rounds; past
+// kDMaxRounds the lanes walk one after another (exact, serial).  Then a scan of
+// the counts and a second walk that stores the symbols: bytes at dst8 (kCodeHuff), u32 at
+// dst32 (kCodeGolomb), u16 at (uint16_t *)dst32 (kCodeHuffWide).  Returns symbols produced.
+constexpr uint32_t kDMaxRounds = 12;
+constexpr uint32_t kDMinSegBits = 256;
+constexpr uint32_t kDRetryScale = 16;   // an unsettled stream retries with segments this much longer
+
+template <int MODE>
+__device__ uint32_t seg_decode(const BitBuf &src, uint64_t sb, uint32_t nbits, uint32_t count, const uint16_t *T,
+                               const uint16_t *C, uint8_t *dst8, uint32_t *dst32, uint32_t *st, uint32_t *cnt,
+                               uint32_t *flag, uint64_t *stats) {
+    constexpr bool GOLOMB = MODE == kCodeGolomb;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr uint32_t kW = kDSymThreads / 64;
+    // segments of >= kDMinSegBits (Jacobi needs room to resynchronise), a multiple of 32
+    const uint32_t S0 = max(kDMinSegBits, ((nbits + kDSymThreads - 1) / kDSymThreads + 31) & ~31u);
+    uint32_t seg_lo = 0, seg_hi = 0;
+    auto walk = [&](uint32_t start, uint32_t &ex) -> uint32_t {
+        BitBuf bb = src;
+        uint32_t pos = start, n = 0, v;
+        bool ok = true;
+        if (pos < seg_hi) bb.seek(sb + pos);
+        while (pos < seg_hi) {
+            if (!code_step<MODE>(bb, pos, nbits, T, C, v)) { ok = false; break; }
+            n++;
+        }
+        ex = ok ? pos : nbits;   // a code that cannot complete ends the stream
+        return n;
+    };
+    bool settled = false;
+    uint32_t rounds = 0, mine = 0, ex = 0, n = 0;
+    // codes that resynchronise slowly (near fixed-length, e.g. the packed distance
+    // bytes) may not settle within short segments: a second attempt uses longer ones
+    for (uint32_t attempt = 0; attempt < 2 && !settled; attempt++) {
+        const uint64_t S = attempt == 0 ? S0 : (uint64_t)S0 * kDRetryScale;
+        seg_lo = (uint32_t)min<uint64_t>(tid * S, nbits);
+        seg_hi = (uint32_t)min<uint64_t>(seg_lo + S, nbits);
+        __syncthreads();
+        st[tid] = seg_lo;
+        if (tid == 0) { flag[0] = 0; flag[1] = 0; }
+        __syncthreads();
+        mine = seg_lo;
+        n = walk(mine, ex);
+        for (uint32_t round = 0; round < kDMaxRounds; round++) {
+            if (tid == 0) flag[(round + 1) & 1] = 0;
+            if (tid + 1 < kDSymThreads && st[tid + 1] != ex) { st[tid + 1] = ex; flag[round & 1] = 1; }
+            __syncthreads();
+            rounds++;
+            if (!flag[round & 1]) { settled = true; break; }
+            if (st[tid] != mine) { mine = st[tid]; n = walk(mine, ex); }
+            __syncthreads();
+        }
+    }
+    if (!settled) {   // serial fallback over the long segments: every start exact before its lane walks
+        const uint32_t active = (uint32_t)min<uint64_t>(kDSymThreads, (nbits + (uint64_t)S0 * kDRetryScale - 1) /
+                                                                         ((uint64_t)S0 * kDRetryScale));
+        for (uint32_t i = 0; i < active; i++) {
+            if (tid == i) {
+                mine = st[i];
+                n = walk(mine, ex);
+                if (i + 1 < kDSymThreads) st[i + 1] = ex;
+            }
+            __syncthreads();
+        }
+        mine = st[tid];
+        if (tid >= active) n = 0;
+    }
+    if (tid == 0 && stats) {   // Jacobi rounds, serial fallbacks
+        atomicAdd((unsigned long long *)stats, (unsigned long long)rounds);
+        if (!settled) atomicAdd((unsigned long long *)stats + 1, 1ull);
+        if (!settled && MODE == kCodeHuff) atomicAdd((unsigned long long *)stats + 4 + (blockIdx.x & 3), 1ull);
+    }
+    // exclusive scan of the per-lane counts
+    uint32_t inc = n;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= (uint32_t)o) inc += t;
+    }
+    if (lane == 63) cnt[wv] = inc;
+    __syncthreads();
+    uint32_t idx = inc - n, tot = 0;
+    for (uint32_t w = 0; w < kW; w++) {
+        if (w < wv) idx += cnt[w];
+        tot += cnt[w];
+    }
+    // walk again and store
+    if (mine < seg_hi && idx < count) {
+        BitBuf bb = src;
+        uint32_t pos = mine, v;
+        bb.seek(sb + pos);
+        const uint32_t stop = min(count, idx + n);
+        if (GOLOMB) {
+            while (idx < stop && code_step<MODE>(bb, pos, nbits, T, C, v)) dst32[idx++] = v;
+        } else if (MODE == kCodeHuffWide) {
+            uint16_t *dst16 = (uint16_t *)dst32;
+            while (idx < stop && code_step<MODE>(bb, pos, nbits, T, C, v)) dst16[idx++] = (uint16_t)v;
+        } else {
+            // whole dwords inside this lane's range are stored at once; the partial
+            // dwords at its two ends (shared with neighbours) byte by byte
+            const uint32_t first = idx;
+            uint32_t acc = 0;
+            while (idx < stop && code_step<MODE>(bb, pos, nbits, T, C, v)) {
+                acc |= v << (8 * (idx & 3));
+                if ((idx & 3) == 3) {
+                    if (idx - 3 >= first) ((uint32_t *)dst8)[idx >> 2] = acc;
+                    else
+                        for (uint32_t q = first; q <= idx; q++) dst8[q] = (uint8_t)(acc >> (8 * (q & 3)));
+                    acc = 0;
+                }
+                idx++;
+            }
+            if (idx & 3)
+                for (uint32_t q = max(first, idx & ~3u); q < idx; q++) dst8[q] = (uint8_t)(acc >> (8 * (q & 3)));
+        }
+    }
+    __syncthreads();
+    return min(tot, count);
+}
+
+// block-wide exclusive scan (blockDim.x threads, <= 16 waves); returns the prefix, total in *tot
+__device__ inline uint32_t block_xscan(uint32_t v, uint32_t *sh, uint32_t *tot) {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= (uint32_t)o) inc += t;
+    }
+    if (lane == 63) sh[wv] = inc;
+    __syncthreads();
+    uint32_t pre = inc - v, all = 0;
+    for (uint32_t w = 0; w < nw; w++) {
+        const uint32_t x = sh[w];
+        if (w < wv) pre += x;
+        all += x;
+    }
+    __syncthreads();
+    *tot = all;
+    return pre;
+}
+
+struct DBlock;
+
+// The 8-bit Huffman sub-streams of ds[0, nstreams) (nstreams a multiple of 4; unused entries raw with
+// count 0): decode tables (k_dtable) and symbols into sym + ds[q].dst (k_dsyms), zeros past a
+// stream's end.  A bad tree sets kDErrTree in *err and, when badq is given, lowers *badq to the
+// first such stream.  Shared with the FCX8 decoder, whose char streams have this serialisation.
+void dec_launch_tables8(const uint8_t *d_in, uint32_t nstreams, const DStream *ds, uint16_t *tbl, uint16_t *child,
+                        uint32_t *err, uint32_t *badq, hipStream_t st);
+void dec_launch_syms8(const uint8_t *d_in, uint64_t in_len, uint32_t nstreams, const DStream *ds,
+                      const uint16_t *tbl, const uint16_t *child, uint8_t *sym, const uint32_t *err,
+                      uint64_t *stats, hipStream_t st);
+
+constexpr int kDStages = 5;       // FCX7 stages
+constexpr int kD78Stages = 6;     // FCX8 stages (fcx_lz78_dec.hip)
+
+}  // namespace fcx
+
+// the decoder context of include/fcx.h: FCX7 scratch (fcx_dec.hip) and FCX8 scratch (fcx_lz78_dec.hip)
+struct fcx_dctx {
+    int device = 0;
+    uint32_t cap_blocks = 0;
+    uint64_t sym_cap = 0, glen_cap = 0;
+    fcx::DBlock *blk = nullptr;
+    fcx::DStream *ds = nullptr;
+    uint64_t *symb = nullptr;
+    uint16_t *tbl = nullptr, *child = nullptr;
+    uint8_t *sym = nullptr;
+    uint32_t *glen = nullptr;
+    uint64_t *words = nullptr;        // [0] total out, [1] error bits, [2] symbol bytes, [3] golomb values,
+                                      // [4..7] Jacobi rounds / serial fallbacks (symbols, golomb)
+    uint64_t *host_words = nullptr;
+    bool profiling = false, timed = false;
+    hipEvent_t ev[fcx::kDStages + 1] = {};
+    // FCX8 (fcx_lz78_decompress_shard): its scratch, and the stage times of the last profiled call
+    void *lz78 = nullptr;
+    void (*lz78_free)(void *) = nullptr;
+    bool timed78 = false;
+    float ms78[fcx::kD78Stages] = {};
+    hipEvent_t ev78[fcx::kD78Stages + 1] = {};
+};
+
+#endif  // FCX_DEC_SHARED_H

@@ -18,6 +18,9 @@
 
 namespace fcx {
 void set_last_error(const std::string &m);
+// fcx_lz78_decompress_shard whose messages number the records from rec_base (fcx_lz78_dec.hip)
+int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
+                             uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
 }
 
 namespace {
@@ -258,50 +261,68 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
     uint8_t hdr[FCX_HEADER_BYTES];
     if (read_full(rd, user, hdr, sizeof(hdr)) != (int64_t)sizeof(hdr)) return sfail(FCX_ERR_FORMAT, "short header");
     uint32_t total = 0;
+    uint16_t counted = 0;
     char kind = 0;
-    int r = fcx_parse_header(hdr, &total, nullptr, &kind);
+    int r = fcx_parse_header(hdr, &total, &counted, &kind);
     if (r) return r;
-    if (kind != '7') return sfail(FCX_ERR_FORMAT, "LZ78 streams are outside this build's scope");
+    const bool lz78 = kind != '7';   // as main() (4140-4159): anything but '7' selects LZ78
     int dev = 0;
     if (fcx_dctx_device(dctx, &dev)) return FCX_ERR_ARG;
     SHIP(hipSetDevice(dev));
-    // groups of whole records: up to kGroup blocks (<= 1 MiB decoded each) per device call
-    // (max_in, when known, bounds the staging: small inputs do not pin a whole group)
+    // groups of whole records: up to kGroup blocks (<= 1 MiB decoded each, + 8 for FCX8) per device
+    // call (max_in, when known, bounds the staging: small inputs do not pin a whole group).  An FCX7
+    // record is <= 2 len + 4096 bytes and a group's staging holds kGroup of them; an FCX8 record may
+    // be 10 len + 4096, so its groups close at kGroup records or when the next record no longer fits
+    // the staging of kIn78 bytes (>= 12 records of the largest size).
     constexpr uint32_t kGroup = 256;
-    const uint64_t rec_max = 2ull * FCX_MAX_BLOCK_BYTES + 4096 + 4;
-    uint64_t in_cap = (uint64_t)kGroup * rec_max;
-    uint64_t out_cap = (uint64_t)kGroup * FCX_MAX_BLOCK_BYTES;
+    constexpr uint64_t kIn78 = 128ull << 20;
+    const uint64_t len_max = lz78 ? 10ull * FCX_MAX_BLOCK_BYTES + 4096 : 2ull * FCX_MAX_BLOCK_BYTES + 4096;
+    const uint64_t blk_max = lz78 ? FCX_MAX_BLOCK_BYTES + 8ull : FCX_MAX_BLOCK_BYTES;
+    uint64_t in_cap = lz78 ? kIn78 : (uint64_t)kGroup * (len_max + 4);
+    uint64_t out_cap = (uint64_t)kGroup * blk_max;
     if (max_in && max_in < in_cap) {
         in_cap = max_in;
-        // each record of >= 4 + 3 bytes decodes to <= 1 MiB
-        out_cap = (uint64_t)FCX_MAX_BLOCK_BYTES * ((max_in + 6) / 7 < kGroup ? (max_in + 6) / 7 : kGroup);
+        // each record of >= 4 + 3 bytes decodes to <= 1 MiB (+ 8)
+        out_cap = blk_max * ((max_in + 6) / 7 < kGroup ? (max_in + 6) / 7 : kGroup);
     }
     Pipeline *PP = nullptr;
     if ((r = get_pipe(1, dev, in_cap, out_cap, &PP))) return r;
     Pipeline &P = *PP;
     Slot &x = P.s[0];
     uint64_t tout = 0, tblocks = 0;
-    bool eof = false;
-    while (!eof) {
+    // FCX8: the header's counted records and no more (main() reads block_num records, 4162-4201)
+    uint64_t left = lz78 ? counted : ~0ull;
+    bool eof = false, have_len = false;
+    uint32_t len = 0;   // (have_len: the length of a record that did not fit the group before)
+    while (!eof && left) {
         uint64_t used = 0;
         uint32_t nb = 0;
-        while (nb < kGroup) {
-            uint32_t len;
-            const int64_t g = read_full(rd, user, (uint8_t *)&len, 4);
-            if (g == 0) { eof = true; break; }
-            if (g != 4) return sfail(FCX_ERR_FORMAT, "truncated block record");
-            if (len > 2 * FCX_MAX_BLOCK_BYTES + 4096) return sfail(FCX_ERR_FORMAT, "block record too long");
-            if (used + 4 + (uint64_t)len > in_cap) return sfail(FCX_ERR_FORMAT, "truncated block record");
+        while (nb < kGroup && left) {
+            if (!have_len) {
+                const int64_t g = read_full(rd, user, (uint8_t *)&len, 4);
+                if (g == 0 && !lz78) { eof = true; break; }
+                if (g != 4) return sfail(FCX_ERR_FORMAT, "truncated block record");
+                if (len > len_max) return sfail(FCX_ERR_FORMAT, "block record too long");
+            }
+            have_len = false;
+            if (used + 4 + (uint64_t)len > in_cap) {
+                if (!lz78 || nb == 0) return sfail(FCX_ERR_FORMAT, "truncated block record");
+                have_len = true;   // opens the next group
+                break;
+            }
             memcpy(x.hin + used, &len, 4);
             if (read_full(rd, user, x.hin + used + 4, len) != (int64_t)len)
                 return sfail(FCX_ERR_FORMAT, "truncated block record");
             used += 4 + (uint64_t)len;
             nb++;
+            left--;
         }
         if (nb == 0) break;
         SHIP(hipMemcpyAsync(x.din, x.hin, used, hipMemcpyHostToDevice, P.scomp));
         uint64_t got = 0;
-        if ((r = fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp))) return r;
+        if (lz78) r = fcx::lz78_decompress_shard_at(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp, tblocks);
+        else r = fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp);
+        if (r) return r;
         SHIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, P.scomp));
         SHIP(hipStreamSynchronize(P.scomp));
         const int w = wr(user, x.hout, got);
@@ -318,7 +339,7 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
 int fcx_decompress_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap,
                         uint64_t *out_len) {
     if (!dctx || !in || (cap && !out)) return sfail(FCX_ERR_ARG, "fcx_decompress_host: NULL argument");
-    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX7", 4) != 0) return sfail(FCX_ERR_FORMAT, "not an FCX7 stream");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return sfail(FCX_ERR_FORMAT, "not an FCX stream");
     MemIO m{in, in_len, 0, out, cap, 0};
     const int r = fcx_decompress_stream(dctx, mem_read, mem_write, &m, in_len - FCX_HEADER_BYTES, nullptr, nullptr,
                                         nullptr);
