@@ -205,6 +205,14 @@ int fcx_dctx_device(fcx_dctx *ctx, int *device);
 int fcx_dctx_set_profiling(fcx_dctx *ctx, int enable);
 int fcx_dctx_stage_count(fcx_dctx *ctx);
 int fcx_dctx_stage(fcx_dctx *ctx, int i, const char **name, float *ms);
+/* Counters of the segment decoder (the Jacobi-synchronised symbol decode) for the last
+ * fcx_decompress_shard call, read-only: writes min(n, FCX_DSYMBOL_STATS) values in this order:
+ * Huffman settle rounds (summed over the sub-streams), Huffman sub-streams that took the serial
+ * fallback, of those per kind (flags, chars, packed distances, Golomb bytes), Golomb settle
+ * rounds, Golomb streams that took the serial fallback.  All zero when the call failed in its
+ * header pass.  FCX_ERR_ARG for a NULL ctx or out, or n < 0. */
+#define FCX_DSYMBOL_STATS 8
+int fcx_dctx_symbol_stats(fcx_dctx *ctx, uint64_t *out, int n);
 
 /* ---- -c lz78 (FCX8): the reference's second block codec ---------------------
  *   fcx_lz78_compress_block  <- uInt32 my_compress_file_lz78(void*, uInt32, uInt8*)  :3127 (called at :4106)

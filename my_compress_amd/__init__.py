@@ -95,6 +95,7 @@ def lib():
     L.fcx_dctx_stage_count.argtypes = [ctypes.c_void_p]
     L.fcx_dctx_stage.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
                                  ctypes.POINTER(ctypes.c_float)]
+    L.fcx_dctx_symbol_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     L.fcx_lz78_compress_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
                                           ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     L.fcx_lz78_compress_host.argtypes = [c_u8p, ctypes.c_uint64, ctypes.c_uint32, c_u8p, ctypes.c_uint64,
@@ -346,6 +347,18 @@ class DContext:
             _check(lib().fcx_dctx_stage(self._h, i, ctypes.byref(name), ctypes.byref(ms)), "fcx_dctx_stage")
             res.append((name.value.decode(), ms.value))
         return res
+
+    SYMBOL_STATS = ("rounds", "fallbacks", "fallbacks_flags", "fallbacks_chars", "fallbacks_p",
+                    "fallbacks_golomb_bytes", "golomb_rounds", "golomb_fallbacks")
+
+    def symbol_stats(self) -> dict:
+        """segment-decoder counters of the last decompress_shard call (fcx_dctx_symbol_stats):
+        Huffman settle rounds, serial fallbacks (total and per sub-stream kind), Golomb rounds
+        and fallbacks"""
+        n = len(self.SYMBOL_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_symbol_stats(self._h, vals, n), "fcx_dctx_symbol_stats")
+        return dict(zip(self.SYMBOL_STATS, [int(v) for v in vals]))
 
 
 def decompress_gpu(blob: bytes, cap: int = None, device: int = 0, ctx: "DContext" = None) -> bytes:

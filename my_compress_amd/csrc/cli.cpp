@@ -144,9 +144,23 @@ static int report(uint64_t got_total, uint32_t total) {
 static int decompress_host(FILE *fin, FILE *fout, uint32_t total, uint16_t nblocks) {
     std::vector<uint8_t> payload, plain(FCX_MAX_BLOCK_BYTES + 8);
     uint64_t got_total = 0;
+    // bytes left in the file bound every record length before anything is sized from it
+    const long here = ftell(fin);
+    uint64_t left = UINT64_MAX;
+    if (here >= 0 && fseek(fin, 0, SEEK_END) == 0) {
+        const long end = ftell(fin);
+        if (end >= here) left = (uint64_t)(end - here);
+        if (fseek(fin, here, SEEK_SET) != 0) return -1;
+    }
     for (uint32_t b = 0; b < nblocks; b++) {
         uint32_t sz = 0;
-        if (fread(&sz, 4, 1, fin) != 1) return -1;
+        if (left < 4 || fread(&sz, 4, 1, fin) != 1) return -1;
+        if (left != UINT64_MAX) left -= 4;
+        if (sz > left) {
+            fprintf(stderr, "block %u: record of %u bytes runs past the end of the file\n", b + 1, sz);
+            return -1;
+        }
+        if (left != UINT64_MAX) left -= sz;
         payload.resize(sz);
         if (fread(payload.data(), 1, sz, fin) != sz) return -1;
         int64_t n = fcx_decompress_block(payload.data(), sz, plain.data(), plain.size());

@@ -859,6 +859,7 @@ int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint
         c->cap_blocks = nblocks;
     }
     uint32_t *err = (uint32_t *)(c->words + 1);
+    memset(c->host_words + 4, 0, 8 * sizeof(uint64_t));   // fcx_dctx_symbol_stats: this call's counters only
     DHIP(hipMemsetAsync(c->words, 0, 128, st));
     dec_launch(d_in, in_len, nblocks, d_out, cap, c->blk, c->ds, c->symb, c->tbl, c->child, c->sym, c->glen, c->words,
                err, 0, st, nullptr);
@@ -889,6 +890,15 @@ int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint
     if (e & kDErrOutCap) return dfail(FCX_ERR_CAPACITY, "output capacity too small");
     if (e) return dfail(FCX_ERR_FORMAT, "malformed stream (decoder error bits " + std::to_string(e) + ")");
     if (out_len) *out_len = c->host_words[0];
+    return FCX_OK;
+}
+
+int fcx_dctx_symbol_stats(fcx_dctx *c, uint64_t *out, int n) {
+    if (!c || !out || n < 0) return dfail(FCX_ERR_ARG, "fcx_dctx_symbol_stats: bad argument");
+    // host_words as the last fcx_decompress_shard call read them back: [4] / [5] Huffman rounds /
+    // fallbacks, [8..11] fallbacks per stream kind, [6] / [7] Golomb rounds / fallbacks
+    static const int kWord[FCX_DSYMBOL_STATS] = {4, 5, 8, 9, 10, 11, 6, 7};
+    for (int i = 0; i < n && i < FCX_DSYMBOL_STATS; i++) out[i] = c->host_words[kWord[i]];
     return FCX_OK;
 }
 

@@ -6,7 +6,12 @@
 // the reference stores no symbol identity when a sub-stream has one distinct
 // byte (ts = 0, W = 0) and decodes it as zeros (930-984 with m = 0).
 // The GPU decoder is the next row of the scope table.
+//
+// Header fields are bounded as the GPU decoder's k_dhead bounds them (fcx_dec.hip) before
+// anything is sized from them: N <= FCX_MAX_BLOCK_BYTES, W <= 2^26 and present, pCnt <= N,
+// G <= (67 pCnt + 31) / 32 + 1.  No exception leaves the C entry point.
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "fcx.h"
@@ -40,7 +45,7 @@ bool decode_substream(Cursor &cur, uint8_t *dst, uint32_t count) {
     const uint8_t *pairs = cur.take(2 * ts);
     const uint32_t nw = cur.u32();
     const uint8_t *words = cur.take(4ull * nw);
-    if (!cur.ok) return false;
+    if (!cur.ok || nw > (1u << 26)) return false;
     // child[2*j + side]: < 256 leaf symbol, >= 256 internal node index + 256
     std::vector<uint16_t> child(2 * ts);
     const uint32_t real = ts + 1;
@@ -70,13 +75,11 @@ bool decode_substream(Cursor &cur, uint8_t *dst, uint32_t count) {
     return true;
 }
 
-}  // namespace
-
-extern "C" int64_t fcx_decompress_block(const uint8_t *in, uint32_t len, uint8_t *out, uint64_t cap) {
-    if (!in || !out) return FCX_ERR_ARG;
+int64_t decode_block(const uint8_t *in, uint32_t len, uint8_t *out, uint64_t cap) {
     Cursor cur{in, in + len};
     const uint32_t N = cur.u32();
-    if (!cur.ok) return FCX_ERR_FORMAT;
+    // a block holds <= FCX_MAX_BLOCK_BYTES bytes and a token yields at least one (k_dhead)
+    if (!cur.ok || N > FCX_MAX_BLOCK_BYTES) return FCX_ERR_FORMAT;
     const uint32_t nb = (N + 7) / 8;
     std::vector<uint8_t> flags(nb + 1, 0), chars(N + 1, 0);
     if (nb > 1) {
@@ -93,7 +96,8 @@ extern "C" int64_t fcx_decompress_block(const uint8_t *in, uint32_t len, uint8_t
     std::vector<uint8_t> pb(pbytes, 0);
     if (!decode_substream(cur, pb.data(), pbytes)) return FCX_ERR_FORMAT;
     const uint32_t G = cur.u32();
-    if (!cur.ok) return FCX_ERR_FORMAT;
+    // a Golomb code is <= 67 bits (l <= 257): more words than that cannot be valid (k_dhead)
+    if (!cur.ok || (uint64_t)G > (67ull * pcnt + 31) / 32 + 1) return FCX_ERR_FORMAT;
     std::vector<uint8_t> gb(4ull * G + 4, 0);
     if (G > 0 && !decode_substream(cur, gb.data(), 4 * G)) return FCX_ERR_FORMAT;
 
@@ -136,4 +140,17 @@ extern "C" int64_t fcx_decompress_block(const uint8_t *in, uint32_t len, uint8_t
         out[o++] = chars[t];
     }
     return (int64_t)o;
+}
+
+}  // namespace
+
+extern "C" int64_t fcx_decompress_block(const uint8_t *in, uint32_t len, uint8_t *out, uint64_t cap) {
+    if (!in || !out) return FCX_ERR_ARG;
+    try {
+        return decode_block(in, len, out, cap);
+    } catch (const std::bad_alloc &) {
+        return FCX_ERR_NOMEM;
+    } catch (...) {
+        return FCX_ERR_INTERNAL;
+    }
 }

@@ -99,6 +99,39 @@ def parse(data: bytes, finder: int = FINDER_EXHAUSTIVE):
     return [[p[i], l[i], c[i]] for i in range(N)]
 
 
+def decompress_block(payload: bytes, cap: int):
+    """one block payload -> its bytes, or None where the decoder fails"""
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n = orc().orc_decompress_block(payload, len(payload), out, cap)
+    return None if n < 0 else out.raw[:n]
+
+
+# ---- the sub-stream coders of the block codec, for tests/fcx7_craft.py ----
+def huffman_stream(src: bytes) -> bytes:
+    """[ts][bitmap][pairs][W][words] of src with the encoder's own tree; empty for empty src"""
+    out = ctypes.create_string_buffer(4 * len(src) + 2048)
+    n = orc().orc_huffman_stream(src, len(src), out)
+    return out.raw[:n]
+
+
+def combine_bits(vals, bits: int) -> bytes:
+    """low `bits` of each value, LSB-first: (bits * n) // 8 + 1 bytes"""
+    n = len(vals)
+    arr = (ctypes.c_uint32 * max(n, 1))(*vals)
+    out = ctypes.create_string_buffer((bits * n) // 8 + 1)
+    orc().orc_combine_bits(arr, n, bits, out)
+    return out.raw
+
+
+def golomb_encode(vals) -> bytes:
+    """Golomb-Rice k = 2 words of the values, as bytes (4 per word)"""
+    n = len(vals)
+    arr = (ctypes.c_uint32 * max(n, 1))(*vals)
+    words = (ctypes.c_uint32 * (sum(v >> 2 for v in vals) // 32 + n + 2))()
+    G = orc().orc_golomb_encode(arr, n, words)
+    return bytes(memoryview(words).cast("B")[:4 * G])
+
+
 def ref_compress_file(data: bytes, block: int) -> bytes:
     """the reference block encoder framed like main(); requires oracle/_ref"""
     import struct
