@@ -12,44 +12,13 @@
 
 #include "fcx.h"
 #include "fcx_device.h"
+#include "fcx_host.h"
 #include "fcx_sparse_filter.h"
-
-namespace fcx {
-// (the match units' launchers: fcx_device.h)
-void launch_classify(const uint8_t *in, const Layout &L, uint32_t *lists, uint32_t stride, uint32_t *cnt,
-                     uint8_t *tkind, hipStream_t st);
-void launch_route_mark(uint32_t *dst, const uint32_t *src, hipStream_t st);
-void launch_parse(const uint8_t *in, const Layout &L, uint32_t *m, const uint64_t *mbits, uint64_t *chain,
-                  const uint64_t *chain_pfx, const uint32_t *tinfo, const uint32_t *mtok, uint64_t *fp,
-                  uint32_t *tile_off, uint32_t *tconv, BlockInfo *binfo, uint8_t *s_flags, uint8_t *s_chars,
-                  uint8_t *s_p, uint8_t *s_golomb, uint16_t *thist, uint32_t *sdesc, uint32_t *err, hipStream_t st,
-                  hipEvent_t *ev, uint32_t emit_dbg = 0);
-void launch_entropy(const Layout &L, BlockInfo *binfo, uint8_t *s0, uint8_t *s1, uint8_t *s2, uint8_t *s3,
-                    const uint16_t *thist, uint32_t *ctab,
-                    uint8_t *ltab, uint8_t *hhdr, uint64_t *cstat, uint64_t *blk_off, uint64_t *total, uint8_t *out,
-                    uint64_t cap, uint32_t *err, const uint8_t *in, const uint32_t *sdesc, hipStream_t st, hipEvent_t *ev,
-                    hipEvent_t wait_scan, hipEvent_t rec_scan, uint32_t tree_dbg = 0);
-}  // namespace fcx
 
 using namespace fcx;
 
 namespace {
 thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-
-int hip_fail(hipError_t e, const char *what) {
-    return fail(FCX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr)                                       \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);   \
-    } while (0)
 
 inline uint32_t round16(uint64_t x) { return (uint32_t)((x + 15) & ~15ull); }
 
@@ -119,40 +88,43 @@ static const MatchUnit &match_unit(int kernel) {   // (auto: the general unit; i
 }
 constexpr uint32_t kRestGrid = 512;         // k_match_rest_<unit>'s workgroups (2 per CU: <= 128 VGPRs)
 constexpr uint64_t kRouteBytes = 4ull * kRouteWords * 8;   // route counters of kMaxGroups (= 8) groups
-constexpr uint64_t kWordBytes = 64 + kRouteBytes;          // dev_words
+constexpr uint64_t kWordBytes = kCwRouteBytes + kRouteBytes;   // dev_words (the status words of fcx_device.h)
+constexpr uint64_t kHwColdBytes = kWordBytes;              // host_words only: byte offset of the first call's counts
 
-struct fcx_ctx {
-    int device = 0;
-    uint32_t B = 0;
+// the scratch of a context, sized for cap_n shard bytes; ensure_scratch drops it as a whole
+struct CtxScratch {
     uint64_t cap_n = 0;        // shard bytes the scratch is sized for
     uint32_t cap_blocks = 0;
-    // scratch (device)
-    uint32_t *m = nullptr;
-    uint64_t *chain = nullptr;
-    uint64_t *mbits = nullptr;         // per position: m[] stored (match or unknown)
-    uint64_t *chain_pfx = nullptr;     // per 64 positions: speculative prefix counts (k_match)
-    uint32_t *tinfo = nullptr;         // per tile: flags, exit, token/match/golomb-bit totals
-    uint32_t *tile_off = nullptr;      // per tile: token/match/golomb-bit offsets (k_stitch)
-    uint32_t *mtok = nullptr;          // per tile: compact match list of the speculative chain (k_match)
-    uint32_t *tconv = nullptr;         // per tile: where the final chain joins it (k_resolve / k_stitch)
-    uint64_t *fp = nullptr;            // per tile: fast-path record (k_resolve)
-    BlockInfo *binfo = nullptr;
-    uint8_t *s[kStreams] = {nullptr, nullptr, nullptr, nullptr};
-    uint16_t *thist = nullptr;         // per tile: chars counts (k_emit)
-    uint64_t *cstat = nullptr;         // per chunk: k_encode's look-back status word
-    uint32_t *sdesc = nullptr;         // per 64 chars: run of input bytes (offset) or kCdMixed (k_emit)
-    uint32_t *ctab = nullptr;          // code table
-    uint8_t *ltab = nullptr, *hhdr = nullptr;
-    uint64_t *blk_off = nullptr;
-    uint64_t *dev_words = nullptr;     // [0] = total output bytes, [1] = error bits, [2] = lazy tiles (k_tree);
-                                       // from byte 64: the route counters, kRouteWords u32 per block group
-    uint64_t *host_words = nullptr;    // pinned: [0..1] length reads; from byte 64 the route counters of a
-                                       // recent call (copied back asynchronously after every routed call);
-                                       // from byte 64 + kRouteBytes the first call's counts (waited for)
-    uint32_t *rlist = nullptr;         // route lists: kRoutes x cap_tiles tile indices (k_classify)
-    uint8_t *tkind = nullptr;          // per tile: its unit (k_classify)
     uint64_t cap_tiles = 0;
-    bool have_hint = false;            // a routed call has run: the estimates below are set
+    DevBuf<uint32_t> m;
+    DevBuf<uint64_t> chain;
+    DevBuf<uint64_t> mbits;            // per position: m[] stored (match or unknown)
+    DevBuf<uint64_t> chain_pfx;        // per 64 positions: speculative prefix counts (k_match)
+    DevBuf<uint32_t> tinfo;            // per tile: flags, exit, token/match/golomb-bit totals
+    DevBuf<uint32_t> tile_off;         // per tile: token/match/golomb-bit offsets (k_stitch)
+    DevBuf<uint32_t> mtok;             // per tile: compact match list of the speculative chain (k_match)
+    DevBuf<uint32_t> tconv;            // per tile: where the final chain joins it (k_resolve / k_stitch)
+    DevBuf<uint64_t> fp;               // per tile: fast-path record (k_resolve)
+    DevBuf<BlockInfo> binfo;
+    DevBuf<uint8_t> s[kStreams];
+    DevBuf<uint16_t> thist;            // per tile: chars counts (k_emit)
+    DevBuf<uint64_t> cstat;            // per chunk: k_encode's look-back status word
+    DevBuf<uint32_t> sdesc;            // per 64 chars: run of input bytes (offset) or kCdMixed (k_emit)
+    DevBuf<uint32_t> ctab;             // code table
+    DevBuf<uint8_t> ltab, hhdr;
+    DevBuf<uint64_t> blk_off;
+    DevBuf<uint32_t> rlist;            // route lists: kRoutes x cap_tiles tile indices (k_classify)
+    DevBuf<uint8_t> tkind;             // per tile: its unit (k_classify)
+};
+
+struct fcx_ctx : CtxScratch {
+    int device = 0;
+    uint32_t B = 0;
+    DevBuf<uint64_t> dev_words;        // the status words (fcx_device.h), kWordBytes
+    PinnedBuf<uint64_t> host_words;    // their mirror: [kCwTotal, kCwErr] length reads; kCwLazy and the route
+                                       // counters of a recent call (copied back asynchronously after every
+                                       // routed call); from kHwColdBytes the first call's counts (waited for)
+    bool have_hint = false;           // a routed call has run: the estimates below are set
     uint64_t hint_cnt[kRoutes] = {};   // tiles per list (after the hand-ons) of a recent call ...
     uint64_t hint_valid = 0;           // ... out of its tiles with bytes
     uint64_t hint_fix = 0;             // its hand-ons plus its lazy tiles (k_tree): > 0 keeps every unit listed
@@ -171,69 +143,48 @@ struct fcx_ctx {
     uint32_t match_mode = 0;   // k_match tile-mode bits (fcx_ctx_set_match_mode)
     int kernel = kMatchAuto;   // match kernel (MatchKernel): auto = chosen per call from the block kinds
     uint32_t emit_dbg = 0;     // k_emit development exits (fcx_debug_emit_bits; output invalid)
-    hipEvent_t ev[kMaxGroups][kNumStages + 1] = {};
-    uint32_t ngroups_timed = 0;
-    bool have_times = false;
-    bool timed = false;        // last call recorded events
-    float ms[kNumStages] = {};
+    StageTimes times{kMaxGroups, kNumStages};   // a lane per block group, read on the first fcx_ctx_stage query
     Layout last{};
+
+    fcx_ctx() {
+        for (auto &e : gsync) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        for (auto &s2 : gst) (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
+    }
+    ~fcx_ctx() {
+        for (auto e : gsync)
+            if (e) (void)hipEventDestroy(e);
+        for (auto s2 : gst)
+            if (s2) (void)hipStreamDestroy(s2);
+    }
 };
+static_assert(kMaxGroups <= StageTimes::kLanes && kNumStages <= StageTimes::kStages, "StageTimes");
 
 namespace {
-void free_scratch(fcx_ctx *c) {
-    void *ptrs[] = {c->m,    c->mbits, c->chain, c->chain_pfx, c->tinfo, c->tile_off, c->mtok, c->tconv, c->fp, c->binfo,
-                    c->s[0], c->s[1],  c->s[2],      c->s[3],       c->thist,    c->cstat, c->sdesc,
-                    c->ctab, c->ltab,  c->hhdr,      c->blk_off, c->rlist, c->tkind};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    c->m = nullptr; c->mbits = c->chain = c->chain_pfx = c->fp = nullptr; c->tinfo = c->tile_off = nullptr;
-    c->mtok = c->tconv = nullptr;
-    c->binfo = nullptr;
-    for (auto &p : c->s) p = nullptr;
-    c->thist = nullptr; c->cstat = nullptr; c->sdesc = nullptr; c->ctab = nullptr;
-    c->ltab = c->hhdr = nullptr;
-    c->blk_off = nullptr;
-    c->rlist = nullptr;
-    c->tkind = nullptr;
-    c->cap_tiles = 0;
-    c->cap_n = 0;
-    c->cap_blocks = 0;
-}
-
-template <typename T>
-int dalloc(T **p, uint64_t bytes, const char *what) {
-    hipError_t e = hipMalloc((void **)p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(FCX_ERR_NOMEM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
-    return FCX_OK;
-}
-
 int ensure_scratch(fcx_ctx *c, uint64_t n) {
     if (n <= c->cap_n) return FCX_OK;
-    free_scratch(c);
+    static_cast<CtxScratch &>(*c) = CtxScratch{};   // (the old scratch goes before the new is made)
     const Layout L = make_layout(n, c->B);
     const uint64_t nb = L.nblocks, nt = (uint64_t)L.nblocks * L.tpb;
-    int r;
-    if ((r = dalloc(&c->m, 4ull * nb * c->B, "m"))) return r;
-    if ((r = dalloc(&c->chain, 8ull * nb * L.wpb, "chain"))) return r;
-    if ((r = dalloc(&c->mbits, 8ull * nb * L.wpb, "mbits"))) return r;
-    if ((r = dalloc(&c->chain_pfx, 8ull * (kTile / 64) * nt, "chain_pfx"))) return r;
-    if ((r = dalloc(&c->tinfo, 32 * nt, "tinfo"))) return r;
-    if ((r = dalloc(&c->tile_off, 12 * (nt + 1), "tile_off"))) return r;   // (+1: k_emit reads tile tix + 1's)
-    if ((r = dalloc(&c->mtok, 4ull * kTileMatches * nt, "mtok"))) return r;
-    if ((r = dalloc(&c->tconv, 4 * nt, "tconv"))) return r;
-    if ((r = dalloc(&c->fp, 96 * nt, "fp"))) return r;   // 12 u64 per tile (k_resolve record)
-    if ((r = dalloc(&c->binfo, sizeof(BlockInfo) * nb, "binfo"))) return r;
-    for (uint32_t s = 0; s < kStreams; s++)
-        if ((r = dalloc(&c->s[s], (uint64_t)L.sstride[s] * nb + 64, "stream"))) return r;
-    if ((r = dalloc(&c->thist, 2ull * 256 * nt, "thist"))) return r;
-    if ((r = dalloc(&c->cstat, 16ull * L.cpb_total * nb, "cstat"))) return r;
-    if ((r = dalloc(&c->sdesc, 4ull * ((c->B + kCharSeg - 1) / kCharSeg) * nb, "sdesc"))) return r;
-    if ((r = dalloc(&c->ctab, 4ull * 256 * kStreams * nb, "ctab"))) return r;
-    if ((r = dalloc(&c->ltab, 256ull * kStreams * nb, "ltab"))) return r;
-    if ((r = dalloc(&c->hhdr, (uint64_t)kHuffHdrStride * kStreams * nb, "hhdr"))) return r;
-    if ((r = dalloc(&c->blk_off, 8 * nb, "blk_off"))) return r;
-    if ((r = dalloc(&c->rlist, 4ull * kRoutes * nt, "route lists"))) return r;
-    if ((r = dalloc(&c->tkind, nt, "tile kinds"))) return r;
+    FCX_TRY(c->m.reserve(4ull * nb * c->B, "m"));
+    FCX_TRY(c->chain.reserve(8ull * nb * L.wpb, "chain"));
+    FCX_TRY(c->mbits.reserve(8ull * nb * L.wpb, "mbits"));
+    FCX_TRY(c->chain_pfx.reserve(8ull * (kTile / 64) * nt, "chain_pfx"));
+    FCX_TRY(c->tinfo.reserve(32 * nt, "tinfo"));
+    FCX_TRY(c->tile_off.reserve(12 * (nt + 1), "tile_off"));   // (+1: k_emit reads tile tix + 1's)
+    FCX_TRY(c->mtok.reserve(4ull * kTileMatches * nt, "mtok"));
+    FCX_TRY(c->tconv.reserve(4 * nt, "tconv"));
+    FCX_TRY(c->fp.reserve(96 * nt, "fp"));   // 12 u64 per tile (k_resolve record)
+    FCX_TRY(c->binfo.reserve(sizeof(BlockInfo) * nb, "binfo"));
+    for (uint32_t s = 0; s < kStreams; s++) FCX_TRY(c->s[s].reserve((uint64_t)L.sstride[s] * nb + 64, "stream"));
+    FCX_TRY(c->thist.reserve(2ull * 256 * nt, "thist"));
+    FCX_TRY(c->cstat.reserve(16ull * L.cpb_total * nb, "cstat"));
+    FCX_TRY(c->sdesc.reserve(4ull * ((c->B + kCharSeg - 1) / kCharSeg) * nb, "sdesc"));
+    FCX_TRY(c->ctab.reserve(4ull * 256 * kStreams * nb, "ctab"));
+    FCX_TRY(c->ltab.reserve(256ull * kStreams * nb, "ltab"));
+    FCX_TRY(c->hhdr.reserve((uint64_t)kHuffHdrStride * kStreams * nb, "hhdr"));
+    FCX_TRY(c->blk_off.reserve(8 * nb, "blk_off"));
+    FCX_TRY(c->rlist.reserve(4ull * kRoutes * nt, "route lists"));
+    FCX_TRY(c->tkind.reserve(nt, "tile kinds"));
     c->cap_tiles = nt;
     c->cap_n = (uint64_t)L.nblocks * c->B;
     c->cap_blocks = L.nblocks;
@@ -281,23 +232,18 @@ int fcx_ctx_create(fcx_ctx **out, int device, uint32_t block_bytes, uint64_t max
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) return fail(FCX_ERR_HIP, "no HIP device: the compress path is GPU-only");
     if (device < 0 || device >= ndev) return fail(FCX_ERR_ARG, "bad device index");
-    HIP_TRY(hipSetDevice(device));
-    fcx_ctx *c = new fcx_ctx();
+    FCX_HIP(hipSetDevice(device));
+    std::unique_ptr<fcx_ctx, Calls<fcx_ctx_destroy>> c(new fcx_ctx());
     c->device = device;
     c->B = block_bytes;
     static_assert(kMaxGroups == 8, "kRouteBytes");
-    e = hipHostMalloc((void **)&c->host_words, kWordBytes + kRouteBytes, hipHostMallocDefault);
-    if (e != hipSuccess) { delete c; return hip_fail(e, "hipHostMalloc"); }
-    memset(c->host_words, 0, kWordBytes + kRouteBytes);
-    e = hipMalloc((void **)&c->dev_words, kWordBytes);
-    if (e != hipSuccess) { (void)hipHostFree(c->host_words); delete c; return hip_fail(e, "hipMalloc"); }
-    for (uint32_t g = 0; g < kMaxGroups; g++)
-        for (int i = 0; i <= kNumStages; i++) (void)hipEventCreate(&c->ev[g][i]);
-    for (auto &e2 : c->gsync) (void)hipEventCreateWithFlags(&e2, hipEventDisableTiming);
-    for (auto &s2 : c->gst) (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-    int r = ensure_scratch(c, max_shard_bytes ? max_shard_bytes : block_bytes);
-    if (r) { fcx_ctx_destroy(c); return r; }
-    *out = c;
+    if ((e = c->host_words.alloc(kHwColdBytes + kRouteBytes)) != hipSuccess)
+        return fail(FCX_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    memset(c->host_words, 0, kHwColdBytes + kRouteBytes);
+    if ((e = c->dev_words.alloc(kWordBytes)) != hipSuccess)
+        return fail(FCX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+    FCX_TRY(ensure_scratch(c.get(), max_shard_bytes ? max_shard_bytes : block_bytes));
+    *out = c.release();
     return FCX_OK;
 }
 
@@ -305,30 +251,28 @@ void fcx_ctx_destroy(fcx_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    free_scratch(c);
-    if (c->dev_words) (void)hipFree(c->dev_words);
-    if (c->host_words) (void)hipHostFree(c->host_words);
-    for (uint32_t g = 0; g < kMaxGroups; g++)
-        for (int i = 0; i <= kNumStages; i++)
-            if (c->ev[g][i]) (void)hipEventDestroy(c->ev[g][i]);
-    for (auto e2 : c->gsync)
-        if (e2) (void)hipEventDestroy(e2);
-    for (auto s2 : c->gst)
-        if (s2) (void)hipStreamDestroy(s2);
     delete c;
 }
 
-const uint64_t *fcx_ctx_device_out_len(fcx_ctx *c) { return c ? c->dev_words : nullptr; }
+const uint64_t *fcx_ctx_device_out_len(fcx_ctx *c) { return c ? c->dev_words.p : nullptr; }
+
+namespace {
+// the verdict of a call's error bits (host_words after a length read)
+int check_err_bits(const fcx_ctx *c) {
+    const uint32_t e = (uint32_t)c->host_words[kCwErr];
+    if (e & kErrCapacity) return fail(FCX_ERR_CAPACITY, "output capacity too small (see fcx_shard_bound)");
+    if (e) return fail(FCX_ERR_INTERNAL, "device invariant violated (error bits " + std::to_string(e) + ")");
+    return FCX_OK;
+}
+}  // namespace
 
 int fcx_ctx_read_out_len(fcx_ctx *c, uint64_t *out_len) {
     if (!c || !out_len) return fail(FCX_ERR_ARG, "fcx_ctx_read_out_len: NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(c->host_words, c->dev_words, 16, hipMemcpyDeviceToHost));
-    const uint32_t e = (uint32_t)c->host_words[1];
-    if (e & 4u) return fail(FCX_ERR_CAPACITY, "output capacity too small (see fcx_shard_bound)");
-    if (e) return fail(FCX_ERR_INTERNAL, "device invariant violated (error bits " + std::to_string(e) + ")");
-    *out_len = c->host_words[0];
+    FCX_HIP(hipSetDevice(c->device));
+    FCX_HIP(hipDeviceSynchronize());
+    FCX_HIP(hipMemcpy(c->host_words, c->dev_words, kCwHeadBytes, hipMemcpyDeviceToHost));
+    FCX_TRY(check_err_bits(c));
+    *out_len = c->host_words[kCwTotal];
     return FCX_OK;
 }
 
@@ -357,28 +301,14 @@ int fcx_ctx_set_match_mode(fcx_ctx *c, int mode) {
     return FCX_OK;
 }
 
-int fcx_ctx_stage_count(fcx_ctx *c) { return c && c->timed ? kNumStages : 0; }
+int fcx_ctx_stage_count(fcx_ctx *c) { return c ? c->times.n : 0; }
 
+// per stage: the sum over the call's block groups of that stage's span on the group's stream (with
+// groups > 1 the spans include what the other stream ran meanwhile)
 int fcx_ctx_stage(fcx_ctx *c, int i, const char **name, float *ms) {
     if (!c || i < 0 || i >= kNumStages) return fail(FCX_ERR_ARG, "bad stage");
-    if (!c->timed) return fail(FCX_ERR_ARG, "last call was not profiled");
-    if (!c->have_times) {
-        // per stage: the sum over the call's block groups of that stage's span on the group's
-        // stream (with groups > 1 the spans include what the other stream ran meanwhile)
-        for (uint32_t g = 0; g < c->ngroups_timed; g++) HIP_TRY(hipEventSynchronize(c->ev[g][kNumStages]));
-        for (int k = 0; k < kNumStages; k++) {
-            c->ms[k] = 0;
-            for (uint32_t g = 0; g < c->ngroups_timed; g++) {
-                float v = 0;
-                HIP_TRY(hipEventElapsedTime(&v, c->ev[g][k], c->ev[g][k + 1]));
-                c->ms[k] += v;
-            }
-        }
-        c->have_times = true;
-    }
-    if (name) *name = kStageNames[i];
-    if (ms) *ms = c->ms[i];
-    return FCX_OK;
+    if (!c->times.n) return fail(FCX_ERR_ARG, "last call was not profiled");
+    return c->times.stage(i, name, ms);
 }
 
 int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap,
@@ -386,20 +316,19 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     if (!c || !d_out || (n && !d_in)) return fail(FCX_ERR_ARG, "fcx_compress_shard: NULL argument");
     if (((uintptr_t)d_out & 15) != 0) return fail(FCX_ERR_ARG, "d_out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(c->device));
+    FCX_HIP(hipSetDevice(c->device));
     if (n == 0) {
-        HIP_TRY(hipMemsetAsync(c->dev_words, 0, 16, st));
+        FCX_HIP(hipMemsetAsync(c->dev_words, 0, kCwHeadBytes, st));
         if (out_len) *out_len = 0;
         return FCX_OK;
     }
     if (n / c->B >= 65536 * 2048ull) return fail(FCX_ERR_ARG, "shard too large");
-    int r = ensure_scratch(c, n);
-    if (r) return r;
+    FCX_TRY(ensure_scratch(c, n));
     const Layout L = make_layout(n, c->B);
     c->last = L;
-    c->have_times = false;
-    uint64_t *total = c->dev_words;
-    uint32_t *err = (uint32_t *)(c->dev_words + 1);
+    uint64_t *total = c->dev_words + kCwTotal;
+    uint32_t *err = (uint32_t *)(c->dev_words + kCwErr);
+    uint32_t *route_cnt = (uint32_t *)((uint8_t *)c->dev_words.p + kCwRouteBytes);   // kRouteWords per group
     // block groups: automatic = one.  Measured on 128 MiB - 1 GiB rand / text / runs shards, 2-8
     // groups were 0-7 % slower than one: every kernel of the sequence already fills the chip,
     // so overlapping them only interleaves the same work
@@ -408,15 +337,15 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     G = std::min(std::max(G, 1u), std::min(kMaxGroups, std::max(1u, L.nblocks / 64)));
     const uint32_t per = (L.nblocks + G - 1) / G;
     G = (L.nblocks + per - 1) / per;
-    c->timed = c->profiling;
-    c->ngroups_timed = c->profiling ? G : 0;
+    c->times.reset();
+    if (c->profiling) c->times.publish(kStageNames, kNumStages, (int)G);
 
     // match search: unrouted when a unit is forced (fcx_ctx_set_match_mode), else routed per tile
     // (fcx_route.hip): the estimates of each unit's share come from the route counters of a recent
     // call (landing asynchronously: any values are a valid estimate, they only size the grids)
     const bool routed = c->kernel == kMatchAuto;
     if (routed && c->have_hint) {
-        const uint32_t *hr = (const uint32_t *)((const uint8_t *)c->host_words + 64);
+        const uint32_t *hr = (const uint32_t *)((const uint8_t *)c->host_words.p + kCwRouteBytes);
         uint64_t cnt[kRoutes] = {}, valid = 0, fix = 0;
         for (uint32_t g = 0; g < kMaxGroups; g++) {
             for (uint32_t u = 0; u < kRoutes; u++) cnt[u] += __atomic_load_n(&hr[kRouteWords * g + u], __ATOMIC_RELAXED);
@@ -424,7 +353,7 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
             fix += __atomic_load_n(&hr[kRouteWords * g + kRouteNoFilter], __ATOMIC_RELAXED) -
                    __atomic_load_n(&hr[kRouteWords * g + kRcNfFiled], __ATOMIC_RELAXED);
         }
-        fix += (uint32_t)__atomic_load_n(&c->host_words[2], __ATOMIC_RELAXED);   // lazy tiles (k_tree)
+        fix += (uint32_t)__atomic_load_n(&c->host_words[kCwLazy], __ATOMIC_RELAXED);   // lazy tiles (k_tree)
         if (valid) {
             for (uint32_t u = 0; u < kRoutes; u++) c->hint_cnt[u] = cnt[u];
             c->hint_valid = valid;
@@ -436,41 +365,41 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     c->last_groups = G;
     c->last_kernel = routed ? kMatchGeneral : c->kernel;
     uint64_t cold_cnt[kRoutes] = {}, cold_valid = 0;
-    HIP_TRY(hipMemsetAsync(c->dev_words, 0, kWordBytes, st));
+    FCX_HIP(hipMemsetAsync(c->dev_words, 0, kWordBytes, st));
     if (G > 1) {
-        HIP_TRY(hipEventRecord(c->gsync[0], st));
-        for (auto s2 : c->gst) HIP_TRY(hipStreamWaitEvent(s2, c->gsync[0], 0));
+        FCX_HIP(hipEventRecord(c->gsync[0], st));
+        for (auto s2 : c->gst) FCX_HIP(hipStreamWaitEvent(s2, c->gsync[0], 0));
     }
     for (uint32_t g = 0; g < G; g++) {
         hipStream_t sg = G > 1 ? c->gst[g & 1] : st;
-        hipEvent_t *ev = c->profiling ? c->ev[g] : nullptr;
+        hipEvent_t *ev = c->profiling ? c->times.lane(g) : nullptr;
         const uint64_t b0 = (uint64_t)g * per;
         const uint32_t gb = (uint32_t)std::min<uint64_t>(per, L.nblocks - b0);
         const Layout Lg = G > 1 ? make_layout(std::min<uint64_t>((uint64_t)gb * c->B, n - b0 * c->B), c->B) : L;
         const uint64_t t0 = b0 * L.tpb;   // first tile of the group
         uint8_t *sg_s[kStreams];
         for (uint32_t q = 0; q < kStreams; q++) sg_s[q] = c->s[q] + b0 * L.sstride[q];
-        if (ev) HIP_TRY(hipEventRecord(ev[0], sg));   // (the memset above is not timed per group)
+        if (ev) FCX_HIP(hipEventRecord(ev[0], sg));   // (the memset above is not timed per group)
         const uint8_t *gin = d_in + b0 * c->B;
         const MatchArgs ma{gin, Lg, c->m + b0 * c->B, c->mbits + b0 * L.wpb, c->chain + b0 * L.wpb,
                            c->chain_pfx + t0 * (kTile / 64), c->tinfo + 8 * t0, c->mtok + t0 * kTileMatches};
         if (!routed) {
-            if (ev) HIP_TRY(hipEventRecord(ev[1], sg));
+            if (ev) FCX_HIP(hipEventRecord(ev[1], sg));
             match_unit(c->kernel).launch(ma, sg, c->match_mode, nullptr, 0);
         } else {
             // classify the group's tiles into the unit lists, then each unit over its list with a grid
             // from the estimate (the first call waits for its own counts), k_match_rest for the rest
-            uint32_t *rc = (uint32_t *)((uint8_t *)c->dev_words + 64) + kRouteWords * g;
+            uint32_t *rc = route_cnt + kRouteWords * g;
             uint32_t *lists = c->rlist + t0;
             const uint32_t stride = (uint32_t)c->cap_tiles, ntg = Lg.nblocks * Lg.tpb;
             auto list_of = [&](uint32_t u) { return lists + (uint64_t)u * stride; };
             launch_classify(gin, Lg, lists, stride, rc, c->tkind + t0, sg);
-            if (ev) HIP_TRY(hipEventRecord(ev[1], sg));
+            if (ev) FCX_HIP(hipEventRecord(ev[1], sg));
             uint64_t est[kRoutes];
             if (!c->have_hint) {
-                uint32_t *cold = (uint32_t *)((uint8_t *)c->host_words + kWordBytes);
-                HIP_TRY(hipMemcpyAsync(cold, rc, 4 * kRouteWords, hipMemcpyDeviceToHost, sg));
-                HIP_TRY(hipStreamSynchronize(sg));
+                uint32_t *cold = (uint32_t *)((uint8_t *)c->host_words.p + kHwColdBytes);
+                FCX_HIP(hipMemcpyAsync(cold, rc, 4 * kRouteWords, hipMemcpyDeviceToHost, sg));
+                FCX_HIP(hipStreamSynchronize(sg));
                 for (uint32_t u = 0; u < kRoutes; u++) { est[u] = cold[u]; cold_cnt[u] += cold[u]; }
                 cold_valid += cold[kRcValid];
             } else {
@@ -513,14 +442,14 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
                 kUnits[u].rest(ma, rest, rts[u], kRestGrid, sg);
             }
         }
-        if (ev) HIP_TRY(hipEventRecord(ev[2], sg));
+        if (ev) FCX_HIP(hipEventRecord(ev[2], sg));
         launch_parse(gin, Lg, ma.m, ma.mbits, ma.chain, ma.chain_pfx, ma.tinfo, ma.mtok, c->fp + 12 * t0,
                      c->tile_off + 3 * t0, c->tconv + t0, c->binfo + b0, sg_s[0], sg_s[1], sg_s[2], sg_s[3],
                      c->thist + t0 * 256, c->sdesc + b0 * ((c->B + kCharSeg - 1) / kCharSeg), err, sg, ev ? ev + 3 : nullptr,
                      c->emit_dbg);
         if (c->emit_dbg & 0xFFFFu) {   // (development: k_emit's timing exits leave invalid streams; stop here)
             if (ev)
-                for (int q = 5; q <= kNumStages; q++) HIP_TRY(hipEventRecord(ev[q], sg));
+                for (int q = 5; q <= kNumStages; q++) FCX_HIP(hipEventRecord(ev[q], sg));
             continue;
         }
         launch_entropy(Lg, c->binfo + b0, sg_s[0], sg_s[1], sg_s[2], sg_s[3], c->thist + t0 * 256,
@@ -532,27 +461,25 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     }
     if (G > 1) {
         for (uint32_t q = 0; q < 2; q++) {
-            HIP_TRY(hipEventRecord(c->gsync[1 + q], c->gst[q]));
-            HIP_TRY(hipStreamWaitEvent(st, c->gsync[1 + q], 0));
+            FCX_HIP(hipEventRecord(c->gsync[1 + q], c->gst[q]));
+            FCX_HIP(hipStreamWaitEvent(st, c->gsync[1 + q], 0));
         }
     }
-    HIP_TRY(hipGetLastError());
+    FCX_HIP(hipGetLastError());
     if (routed && !c->have_hint && cold_valid) {
         for (uint32_t u = 0; u < kRoutes; u++) c->hint_cnt[u] = cold_cnt[u];
         c->hint_valid = cold_valid;
     }
     if (routed) {   // the lazy tiles and route counters back for the next calls' estimates (asynchronous)
-        HIP_TRY(hipMemcpyAsync((uint8_t *)c->host_words + 16, (uint8_t *)c->dev_words + 16, 48 + kRouteBytes,
+        FCX_HIP(hipMemcpyAsync(c->host_words + kCwLazy, c->dev_words + kCwLazy, kWordBytes - 8 * kCwLazy,
                                hipMemcpyDeviceToHost, st));
         c->have_hint = true;
     }
     if (out_len) {
-        HIP_TRY(hipMemcpyAsync(c->host_words, c->dev_words, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const uint32_t e = (uint32_t)c->host_words[1];
-        if (e & 4u) return fail(FCX_ERR_CAPACITY, "output capacity too small (see fcx_shard_bound)");
-        if (e) return fail(FCX_ERR_INTERNAL, "device invariant violated (error bits " + std::to_string(e) + ")");
-        *out_len = c->host_words[0];
+        FCX_HIP(hipMemcpyAsync(c->host_words, c->dev_words, kCwHeadBytes, hipMemcpyDeviceToHost, st));
+        FCX_HIP(hipStreamSynchronize(st));
+        FCX_TRY(check_err_bits(c));
+        *out_len = c->host_words[kCwTotal];
     }
     return FCX_OK;
 }
@@ -569,9 +496,9 @@ int fcx_ctx_stats(fcx_ctx *c, uint64_t *tokens, uint64_t *matches, uint64_t *laz
     if (!c) return fail(FCX_ERR_ARG, "NULL ctx");
     const uint32_t nb = c->last.nblocks;
     std::vector<BlockInfo> bi(nb);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (nb) HIP_TRY(hipMemcpy(bi.data(), c->binfo, sizeof(BlockInfo) * nb, hipMemcpyDeviceToHost));
+    FCX_HIP(hipSetDevice(c->device));
+    FCX_HIP(hipDeviceSynchronize());
+    if (nb) FCX_HIP(hipMemcpy(bi.data(), c->binfo, sizeof(BlockInfo) * nb, hipMemcpyDeviceToHost));
     uint64_t t = 0, mt = 0, le = 0, lt = 0;
     for (auto &x : bi) { t += x.ntok; mt += x.nmatch; le += x.lazy_evals; lt += x.lazy_tiles; }
     if (tokens) *tokens = t;
@@ -600,10 +527,10 @@ int fcx_ctx_route_stats(fcx_ctx *c, uint64_t *out, int n) {
     if (!c || !out || n < 0) return fail(FCX_ERR_ARG, "fcx_ctx_route_stats: bad argument");
     uint64_t v[FCX_ROUTE_STATS] = {};
     if (c->last_routed) {
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipDeviceSynchronize());
+        FCX_HIP(hipSetDevice(c->device));
+        FCX_HIP(hipDeviceSynchronize());
         uint32_t rc[kRouteWords * kMaxGroups];
-        HIP_TRY(hipMemcpy(rc, (uint8_t *)c->dev_words + 64, sizeof(rc), hipMemcpyDeviceToHost));
+        FCX_HIP(hipMemcpy(rc, (uint8_t *)c->dev_words.p + kCwRouteBytes, sizeof(rc), hipMemcpyDeviceToHost));
         for (uint32_t g = 0; g < c->last_groups; g++) {
             const uint32_t *r = rc + kRouteWords * g;
             for (uint32_t u = 0; u < kSearchUnits; u++) {
@@ -625,12 +552,11 @@ int fcx_ctx_route_stats(fcx_ctx *c, uint64_t *out, int n) {
 // per-phase timing (tools/matchphase.py); the context's scratch is left invalid
 int fcx_debug_match(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t dbg, void *stream) {
     if (!c || !d_in || n == 0) return fail(FCX_ERR_ARG, "fcx_debug_match: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int r = ensure_scratch(c, n);
-    if (r) return r;
+    FCX_HIP(hipSetDevice(c->device));
+    FCX_TRY(ensure_scratch(c, n));
     const MatchArgs ma{d_in, make_layout(n, c->B), c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok};
     match_unit(c->kernel).launch(ma, (hipStream_t)stream, dbg, nullptr, 0);
-    HIP_TRY(hipGetLastError());
+    FCX_HIP(hipGetLastError());
     return FCX_OK;
 }
 
@@ -694,24 +620,23 @@ uint32_t fcx_compress_block(const void *in, uint32_t len, uint8_t *out) {
         return 17;
     }
     if (len > FCX_MAX_BLOCK_BYTES) { fail(FCX_ERR_ARG, "block larger than 1 MiB"); return 0; }
-    struct Holder {
-        fcx_ctx *c = nullptr;
-        std::vector<uint8_t> buf;
-        ~Holder() { fcx_ctx_destroy(c); }
-    };
-    thread_local Holder h;
-    if (!h.c) {
+    // a context per host thread, on the device that was current at the thread's first call
+    thread_local std::unique_ptr<fcx_ctx, Calls<fcx_ctx_destroy>> ctx;
+    thread_local std::vector<uint8_t> buf;
+    if (!ctx) {
         int dev = 0;
         (void)hipGetDevice(&dev);
-        if (fcx_ctx_create(&h.c, dev, FCX_MAX_BLOCK_BYTES, FCX_MAX_BLOCK_BYTES)) return 0;
+        fcx_ctx *c = nullptr;
+        if (fcx_ctx_create(&c, dev, FCX_MAX_BLOCK_BYTES, FCX_MAX_BLOCK_BYTES)) return 0;
+        ctx.reset(c);
     }
-    h.buf.resize(fcx_shard_bound(len, FCX_MAX_BLOCK_BYTES));
+    buf.resize(fcx_shard_bound(len, FCX_MAX_BLOCK_BYTES));
     uint64_t got = 0;
-    if (fcx_compress_host(h.c, (const uint8_t *)in, len, h.buf.data(), h.buf.size(), &got)) return 0;
+    if (fcx_compress_host(ctx.get(), (const uint8_t *)in, len, buf.data(), buf.size(), &got)) return 0;
     if (got < 4) { fail(FCX_ERR_INTERNAL, "short record"); return 0; }
     uint32_t plen;
-    memcpy(&plen, h.buf.data(), 4);
-    memcpy(out, h.buf.data() + 4, plen);
+    memcpy(&plen, buf.data(), 4);
+    memcpy(out, buf.data() + 4, plen);
     return plen;
 }
 

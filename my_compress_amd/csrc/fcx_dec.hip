@@ -45,7 +45,6 @@
 #include "fcx_dec_shared.h"
 
 namespace fcx {
-void set_last_error(const std::string &m);
 
 constexpr uint32_t kDLzThreads = 1024;
 constexpr uint32_t kDLzTile = 8192;              // output bytes resolved per LDS step
@@ -215,7 +214,7 @@ __global__ void k_dscan(uint32_t nblocks, DBlock *blk, DStream *ds, const uint64
         if (tid == 0) { carry[0] += tot[0]; carry[1] += tot[1]; }
         __syncthreads();
     }
-    if (tid == 0) { totals[0] = carry[0]; totals[1] = carry[1]; }   // the host sizes the scratch from these
+    if (tid == 0) { totals[0] = carry[0]; totals[1] = carry[1]; }   // (kDwSymBytes, kDwGolombVals) the host sizes the scratch from these
 }
 
 // ---------------------------------------------------------------------------
@@ -399,7 +398,7 @@ __global__ __launch_bounds__(kDSymThreads) void k_dgolomb(uint32_t nblocks, DBlo
         uint64_t bit0;
         const BitBuf src = make_bits(sym + s.dst, nbytes, bit0);
         got = seg_decode<true>(src, bit0, (uint32_t)(8 * nbytes), pcnt, nullptr, nullptr, nullptr,
-                               glen + B.glen_off, st, cnt, flag, stats + 2);
+                               glen + B.glen_off, st, cnt, flag, stats + kSsGolomb);
     }
     if (tid == 0) {
         B.glen_got = got;
@@ -469,7 +468,7 @@ __global__ __launch_bounds__(256) void k_dlen(uint32_t nblocks, DBlock *blk, con
     }
 }
 
-// output offsets of the blocks; total into words[0]; capacity check
+// output offsets of the blocks; total into words[kDwTotal]; capacity check
 __global__ void k_dscan_out(uint32_t nblocks, DBlock *blk, uint64_t cap, uint64_t *words, uint32_t *err) {
     __shared__ uint64_t sh[16];
     __shared__ uint64_t carry;
@@ -497,7 +496,7 @@ __global__ void k_dscan_out(uint32_t nblocks, DBlock *blk, uint64_t cap, uint64_
         __syncthreads();
     }
     if (tid == 0) {
-        words[0] = carry;
+        words[kDwTotal] = carry;
         if (carry > cap) atomicOr(err, kDErrOutCap);
     }
 }
@@ -701,7 +700,7 @@ void dec_launch(const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t 
     if (phase == 0) {
         hipLaunchKernelGGL(k_dindex, dim3(1), dim3(1), 0, st, d_in, in_len, nblocks, blk, err);
         hipLaunchKernelGGL(k_dhead, dim3((nblocks + 255) / 256), dim3(256), 0, st, d_in, nblocks, blk, ds, symb, err);
-        hipLaunchKernelGGL(k_dscan, dim3(1), dim3(1024), 0, st, nblocks, blk, ds, symb, words + 2);
+        hipLaunchKernelGGL(k_dscan, dim3(1), dim3(1024), 0, st, nblocks, blk, ds, symb, words + kDwSymBytes);
         return;
     }
     auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], st); };
@@ -709,9 +708,9 @@ void dec_launch(const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t 
     hipLaunchKernelGGL(k_dtable, dim3(4 * nblocks), dim3(64), 0, st, d_in, nblocks, ds, tbl, child, err, (uint32_t *)nullptr);
     mark(1);
     hipLaunchKernelGGL(k_dsyms, dim3(4 * nblocks), dim3(kDSymThreads), 0, st, d_in, in_len, nblocks, ds, tbl, child, sym, err,
-                       words + 4);
+                       words + kDwStats);
     mark(2);
-    hipLaunchKernelGGL(k_dgolomb, dim3(nblocks), dim3(kDSymThreads), 0, st, nblocks, blk, ds, sym, glen, err, words + 4);
+    hipLaunchKernelGGL(k_dgolomb, dim3(nblocks), dim3(kDSymThreads), 0, st, nblocks, blk, ds, sym, glen, err, words + kDwStats);
     mark(3);
     hipLaunchKernelGGL(k_dlen, dim3(nblocks), dim3(256), 0, st, nblocks, blk, sym, glen, err);
     hipLaunchKernelGGL(k_dscan_out, dim3(1), dim3(1024), 0, st, nblocks, blk, cap, words, err);
@@ -739,54 +738,24 @@ void dec_launch_syms8(const uint8_t *d_in, uint64_t in_len, uint32_t nstreams, c
 using namespace fcx;
 
 namespace {
-int dfail(int code, const std::string &m) {
-    set_last_error(m);   // fcx_last_error() (fcx_capi.hip)
-    return code;
-}
-#define DHIP(expr)                                                                             \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return dfail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 const char *kDStageNames[] = {"tables", "symbols", "golomb", "lengths", "lz"};
-// the FCX8 stages (fcx_lz78_dec.hip records them)
-const char *kD78StageNames[] = {"header", "index", "tables", "symbols", "links", "expand"};
-static_assert(sizeof(kD78StageNames) / sizeof(kD78StageNames[0]) == kD78Stages, "FCX8 stage names");
-}  // namespace
-
-namespace {
-template <typename T>
-int dgrow(T **p, uint64_t &have, uint64_t need, const char *what) {
-    if (need <= have && *p) return FCX_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    hipError_t e = hipMalloc((void **)p, need ? need : 16);
-    if (e != hipSuccess) return dfail(FCX_ERR_NOMEM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
-    have = need;
-    return FCX_OK;
-}
+static_assert(sizeof(kDStageNames) / sizeof(kDStageNames[0]) == kDStages, "FCX7 stage names");
 }  // namespace
 
 extern "C" {
 
 int fcx_dctx_create(fcx_dctx **out, int device) {
-    if (!out) return dfail(FCX_ERR_ARG, "fcx_dctx_create: NULL");
+    if (!out) return fail(FCX_ERR_ARG, "fcx_dctx_create: NULL");
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return dfail(FCX_ERR_HIP, "no HIP device: the GPU decoder needs one");
-    if (device < 0 || device >= ndev) return dfail(FCX_ERR_ARG, "bad device index");
-    DHIP(hipSetDevice(device));
-    fcx_dctx *c = new fcx_dctx();
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FCX_ERR_HIP, "no HIP device: the GPU decoder needs one");
+    if (device < 0 || device >= ndev) return fail(FCX_ERR_ARG, "bad device index");
+    FCX_HIP(hipSetDevice(device));
+    std::unique_ptr<fcx_dctx, Calls<fcx_dctx_destroy>> c(new fcx_dctx());
     c->device = device;
-    if (hipHostMalloc((void **)&c->host_words, 128, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&c->words, 128) != hipSuccess) {
-        fcx_dctx_destroy(c);
-        return dfail(FCX_ERR_NOMEM, "fcx_dctx_create: allocation failed");
-    }
-    for (auto &e : c->ev) (void)hipEventCreate(&e);
-    for (auto &e : c->ev78) (void)hipEventCreate(&e);
-    *out = c;
+    if (c->d7.host_words.alloc(8 * kDwWords) != hipSuccess || c->d7.words.alloc(8 * kDwWords) != hipSuccess)
+        return fail(FCX_ERR_NOMEM, "fcx_dctx_create: allocation failed");
+    *out = c.release();
     return FCX_OK;
 }
 
@@ -794,118 +763,92 @@ void fcx_dctx_destroy(fcx_dctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {c->blk, c->ds, c->symb, c->tbl, c->child, c->sym, c->glen, c->words};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->lz78 && c->lz78_free) c->lz78_free(c->lz78);
-    if (c->host_words) (void)hipHostFree(c->host_words);
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev78)
-        if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
 int fcx_dctx_set_profiling(fcx_dctx *c, int enable) {
-    if (!c) return dfail(FCX_ERR_ARG, "NULL ctx");
+    if (!c) return fail(FCX_ERR_ARG, "NULL ctx");
     c->profiling = enable != 0;
     return FCX_OK;
 }
 
-int fcx_dctx_stage_count(fcx_dctx *c) { return !c ? 0 : c->timed78 ? kD78Stages : c->timed ? kDStages : 0; }
+int fcx_dctx_stage_count(fcx_dctx *c) { return c ? c->times.n : 0; }
 
 int fcx_dctx_stage(fcx_dctx *c, int i, const char **name, float *ms) {
-    if (c && c->timed78) {   // the last call was fcx_lz78_decompress_shard: ms summed over its batches
-        if (i < 0 || i >= kD78Stages) return dfail(FCX_ERR_ARG, "bad stage");
-        if (name) *name = kD78StageNames[i];
-        if (ms) *ms = c->ms78[i];
-        return FCX_OK;
-    }
-    if (!c || i < 0 || i >= kDStages || !c->timed) return dfail(FCX_ERR_ARG, "bad stage / not profiled");
-    DHIP(hipEventSynchronize(c->ev[kDStages]));
-    float v = 0;
-    DHIP(hipEventElapsedTime(&v, c->ev[i], c->ev[i + 1]));
-    if (name) *name = kDStageNames[i];
-    if (ms) *ms = v;
-    return FCX_OK;
+    if (!c || i < 0 || i >= c->times.n)   // (only an FCX8 call's table rules out "not profiled")
+        return fail(FCX_ERR_ARG, c && c->times.n == kD78Stages ? "bad stage" : "bad stage / not profiled");
+    return c->times.stage(i, name, ms);
 }
 
 int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
                          uint64_t cap, uint64_t *out_len, void *stream) {
-    if (!c || (in_len && !d_in) || (cap && !d_out)) return dfail(FCX_ERR_ARG, "fcx_decompress_shard: NULL argument");
+    if (!c || (in_len && !d_in) || (cap && !d_out)) return fail(FCX_ERR_ARG, "fcx_decompress_shard: NULL argument");
     hipStream_t st = (hipStream_t)stream;
-    DHIP(hipSetDevice(c->device));
-    c->timed = false;
-    c->timed78 = false;
+    FCX_HIP(hipSetDevice(c->device));
+    c->times.reset();
     if (nblocks == 0) {
         if (out_len) *out_len = 0;
         return FCX_OK;
     }
-    if (nblocks > c->cap_blocks) {
-        uint64_t h = 0;
-        int r;
-        if (c->blk) (void)hipFree(c->blk);
-        if (c->ds) (void)hipFree(c->ds);
-        if (c->symb) (void)hipFree(c->symb);
-        if (c->tbl) (void)hipFree(c->tbl);
-        if (c->child) (void)hipFree(c->child);
-        c->blk = nullptr; c->ds = nullptr; c->symb = nullptr; c->tbl = nullptr; c->child = nullptr;
-        c->cap_blocks = 0;
-        if ((r = dgrow(&c->blk, h = 0, sizeof(DBlock) * (uint64_t)nblocks, "blocks"))) return r;
-        if ((r = dgrow(&c->ds, h = 0, sizeof(DStream) * 4ull * nblocks, "streams"))) return r;
-        if ((r = dgrow(&c->symb, h = 0, 8ull * nblocks, "symb"))) return r;
-        if ((r = dgrow(&c->tbl, h = 0, 2048ull * 4 * nblocks, "tables"))) return r;
-        if ((r = dgrow(&c->child, h = 0, 1024ull * 4 * nblocks, "children"))) return r;
-        c->cap_blocks = nblocks;
+    Dec7 &D = c->d7;
+    if (nblocks > D.cap_blocks) {
+        static_cast<Dec7Blocks &>(D) = Dec7Blocks{};   // (the old scratch goes before the new is made)
+        FCX_TRY(D.blk.reserve(sizeof(DBlock) * (uint64_t)nblocks, "blocks"));
+        FCX_TRY(D.ds.reserve(sizeof(DStream) * 4ull * nblocks, "streams"));
+        FCX_TRY(D.symb.reserve(8ull * nblocks, "symb"));
+        FCX_TRY(D.tbl.reserve(2048ull * 4 * nblocks, "tables"));
+        FCX_TRY(D.child.reserve(1024ull * 4 * nblocks, "children"));
+        D.cap_blocks = nblocks;
     }
-    uint32_t *err = (uint32_t *)(c->words + 1);
-    memset(c->host_words + 4, 0, 8 * sizeof(uint64_t));   // fcx_dctx_symbol_stats: this call's counters only
-    DHIP(hipMemsetAsync(c->words, 0, 128, st));
-    dec_launch(d_in, in_len, nblocks, d_out, cap, c->blk, c->ds, c->symb, c->tbl, c->child, c->sym, c->glen, c->words,
-               err, 0, st, nullptr);
+    uint64_t *hw = D.host_words;
+    uint32_t *err = (uint32_t *)(D.words + kDwErr);
+    memset(hw + kDwStats, 0, kSsWords * sizeof(uint64_t));   // fcx_dctx_symbol_stats: this call's counters only
+    FCX_HIP(hipMemsetAsync(D.words, 0, 8 * kDwWords, st));
+    dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.symb, D.tbl, D.child, D.sym, D.glen, D.words, err, 0, st,
+               nullptr);
     // k_dscan left the scratch totals next to the error bits
-    DHIP(hipMemcpyAsync(c->host_words, c->words, 32, hipMemcpyDeviceToHost, st));
-    DHIP(hipStreamSynchronize(st));
-    if ((uint32_t)c->host_words[1] & (kDErrRecord | kDErrHeader))
-        return dfail(FCX_ERR_FORMAT, "malformed block records / headers");
-    int r;
-    if ((r = dgrow(&c->sym, c->sym_cap, c->host_words[2] + 64, "symbols"))) return r;
-    if ((r = dgrow(&c->glen, c->glen_cap, 4 * c->host_words[3] + 64, "golomb values"))) return r;
-    hipEvent_t *ev = c->profiling ? c->ev : nullptr;
-    c->timed = ev != nullptr;
-    dec_launch(d_in, in_len, nblocks, d_out, cap, c->blk, c->ds, c->symb, c->tbl, c->child, c->sym, c->glen, c->words,
-               err, 1, st, ev);
-    DHIP(hipGetLastError());
-    DHIP(hipMemcpyAsync(c->host_words, c->words, 128, hipMemcpyDeviceToHost, st));
-    DHIP(hipStreamSynchronize(st));
+    FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * (kDwGolombVals + 1), hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    if ((uint32_t)hw[kDwErr] & (kDErrRecord | kDErrHeader)) return fail(FCX_ERR_FORMAT, "malformed block records / headers");
+    FCX_TRY(D.sym.reserve(hw[kDwSymBytes] + 64, "symbols"));
+    FCX_TRY(D.glen.reserve(4 * hw[kDwGolombVals] + 64, "golomb values"));
+    if (c->profiling) c->times.publish(kDStageNames, kDStages, 1);
+    dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.symb, D.tbl, D.child, D.sym, D.glen, D.words, err, 1, st,
+               c->profiling ? c->times.lane() : nullptr);
+    FCX_HIP(hipGetLastError());
+    FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * kDwWords, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
     static const bool dbg = getenv("FCX_DEC_DEBUG") != nullptr;
-    if (dbg)
+    if (dbg) {
+        const uint64_t *s = hw + kDwStats;
         fprintf(stderr, "fcx decode: symbol streams rounds %llu fallbacks %llu (flags %llu chars %llu p %llu golomb %llu)"
                 " | golomb rounds %llu fallbacks %llu\n",
-                (unsigned long long)c->host_words[4], (unsigned long long)c->host_words[5],
-                (unsigned long long)c->host_words[8], (unsigned long long)c->host_words[9],
-                (unsigned long long)c->host_words[10], (unsigned long long)c->host_words[11],
-                (unsigned long long)c->host_words[6], (unsigned long long)c->host_words[7]);
-    const uint32_t e = (uint32_t)c->host_words[1];
-    if (e & kDErrOutCap) return dfail(FCX_ERR_CAPACITY, "output capacity too small");
-    if (e) return dfail(FCX_ERR_FORMAT, "malformed stream (decoder error bits " + std::to_string(e) + ")");
-    if (out_len) *out_len = c->host_words[0];
+                (unsigned long long)s[kSsRounds], (unsigned long long)s[kSsFallbacks],
+                (unsigned long long)s[kSsKind], (unsigned long long)s[kSsKind + 1],
+                (unsigned long long)s[kSsKind + 2], (unsigned long long)s[kSsKind + 3],
+                (unsigned long long)s[kSsGolomb + kSsRounds], (unsigned long long)s[kSsGolomb + kSsFallbacks]);
+    }
+    const uint32_t e = (uint32_t)hw[kDwErr];
+    if (e & kDErrOutCap) return fail(FCX_ERR_CAPACITY, "output capacity too small");
+    if (e) return fail(FCX_ERR_FORMAT, "malformed stream (decoder error bits " + std::to_string(e) + ")");
+    if (out_len) *out_len = hw[kDwTotal];
     return FCX_OK;
 }
 
 int fcx_dctx_symbol_stats(fcx_dctx *c, uint64_t *out, int n) {
-    if (!c || !out || n < 0) return dfail(FCX_ERR_ARG, "fcx_dctx_symbol_stats: bad argument");
-    // host_words as the last fcx_decompress_shard call read them back: [4] / [5] Huffman rounds /
-    // fallbacks, [8..11] fallbacks per stream kind, [6] / [7] Golomb rounds / fallbacks
-    static const int kWord[FCX_DSYMBOL_STATS] = {4, 5, 8, 9, 10, 11, 6, 7};
-    for (int i = 0; i < n && i < FCX_DSYMBOL_STATS; i++) out[i] = c->host_words[kWord[i]];
+    if (!c || !out || n < 0) return fail(FCX_ERR_ARG, "fcx_dctx_symbol_stats: bad argument");
+    // the statistics block as the last fcx_decompress_shard call read it back, in the order of fcx.h
+    static const uint32_t kWord[FCX_DSYMBOL_STATS] = {kSsRounds, kSsFallbacks, kSsKind, kSsKind + 1, kSsKind + 2, kSsKind + 3,
+                                                      kSsGolomb + kSsRounds, kSsGolomb + kSsFallbacks};
+    for (int i = 0; i < n && i < FCX_DSYMBOL_STATS; i++) out[i] = c->d7.host_words[kDwStats + kWord[i]];
     return FCX_OK;
 }
 
 int fcx_dctx_device(fcx_dctx *c, int *device) {
-    if (!c) return dfail(FCX_ERR_ARG, "NULL ctx");
+    if (!c) return fail(FCX_ERR_ARG, "NULL ctx");
     if (device) *device = c->device;
     return FCX_OK;
 }
 
 }  // extern "C"
+

@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "fcx_host.h"
+
 namespace fcx {
 
 // device error bits of the decoders
@@ -185,6 +187,11 @@ __device__ inline bool code_step(BitBuf &bb, uint32_t &pos, uint32_t nbits, cons
 constexpr uint32_t kDMaxRounds = 12;
 constexpr uint32_t kDMinSegBits = 256;
 constexpr uint32_t kDRetryScale = 16;   // an unsettled stream retries with segments this much longer
+// its statistics block, u64 each (where a decoder keeps the block: its status-word table)
+constexpr uint32_t kSsRounds = 0, kSsFallbacks = 1;   // Jacobi rounds, serial fallbacks
+constexpr uint32_t kSsGolomb = 2;                     // the same pair for the golomb walk (k_dgolomb's stats)
+constexpr uint32_t kSsKind = 4;                       // Huffman fallbacks per sub-stream kind: flags, chars, p, golomb
+constexpr uint32_t kSsWords = 8;
 
 template <int MODE>
 __device__ uint32_t seg_decode(const BitBuf &src, uint64_t sb, uint32_t nbits, uint32_t count, const uint16_t *T,
@@ -247,9 +254,9 @@ __device__ uint32_t seg_decode(const BitBuf &src, uint64_t sb, uint32_t nbits, u
         if (tid >= active) n = 0;
     }
     if (tid == 0 && stats) {   // Jacobi rounds, serial fallbacks
-        atomicAdd((unsigned long long *)stats, (unsigned long long)rounds);
-        if (!settled) atomicAdd((unsigned long long *)stats + 1, 1ull);
-        if (!settled && MODE == kCodeHuff) atomicAdd((unsigned long long *)stats + 4 + (blockIdx.x & 3), 1ull);
+        atomicAdd((unsigned long long *)stats + kSsRounds, (unsigned long long)rounds);
+        if (!settled) atomicAdd((unsigned long long *)stats + kSsFallbacks, 1ull);
+        if (!settled && MODE == kCodeHuff) atomicAdd((unsigned long long *)stats + kSsKind + (blockIdx.x & 3), 1ull);
     }
     // exclusive scan of the per-lane counts
     uint32_t inc = n;
@@ -321,6 +328,15 @@ __device__ inline uint32_t block_xscan(uint32_t v, uint32_t *sh, uint32_t *tot) 
 
 struct DBlock;
 
+// ---- status words of an FCX7 decode (fcx_dctx's d7.words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kDwTotal = 0;       // decoded bytes (k_dscan_out)
+constexpr uint32_t kDwErr = 1;         // error bits (kDErr*), a u32
+constexpr uint32_t kDwSymBytes = 2;    // symbol scratch bytes, and right behind them ...
+constexpr uint32_t kDwGolombVals = 3;  // ... the golomb values (k_dscan's totals[0..1]): they size the scratch
+constexpr uint32_t kDwStats = 4;       // the segment decoder's statistics block (kSs* above)
+constexpr uint32_t kDwWords = 16;      // (128 bytes)
+static_assert(kDwStats + kSsWords <= kDwWords, "FCX7 status words");
+
 // The 8-bit Huffman sub-streams of ds[0, nstreams) (nstreams a multiple of 4; unused entries raw with
 // count 0): decode tables (k_dtable) and symbols into sym + ds[q].dst (k_dsyms), zeros past a
 // stream's end.  A bad tree sets kDErrTree in *err and, when badq is given, lowers *badq to the
@@ -334,30 +350,40 @@ void dec_launch_syms8(const uint8_t *d_in, uint64_t in_len, uint32_t nstreams, c
 constexpr int kDStages = 5;       // FCX7 stages
 constexpr int kD78Stages = 6;     // FCX8 stages (fcx_lz78_dec.hip)
 
+// fcx_lz78_decompress_shard whose messages number the records from rec_base (the stream path's
+// groups of a longer run; fcx_lz78_dec.hip)
+int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
+                             uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
+
+// FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
+struct Dec7Blocks {
+    uint32_t cap_blocks = 0;
+    DevBuf<DBlock> blk;
+    DevBuf<DStream> ds;
+    DevBuf<uint64_t> symb;
+    DevBuf<uint16_t> tbl, child;
+};
+// ... and per decoded symbol, each grown when a call needs more; the status words (kDw*)
+struct Dec7 : Dec7Blocks {
+    DevBuf<uint8_t> sym;
+    DevBuf<uint32_t> glen;
+    DevBuf<uint64_t> words;
+    PinnedBuf<uint64_t> host_words;
+};
+// FCX8 scratch (fcx_lz78_dec.hip), made by the first FCX8 call
+struct Scratch78;
+void free_scratch78(Scratch78 *s);
+
 }  // namespace fcx
 
-// the decoder context of include/fcx.h: FCX7 scratch (fcx_dec.hip) and FCX8 scratch (fcx_lz78_dec.hip)
+// the decoder context of include/fcx.h
 struct fcx_dctx {
     int device = 0;
-    uint32_t cap_blocks = 0;
-    uint64_t sym_cap = 0, glen_cap = 0;
-    fcx::DBlock *blk = nullptr;
-    fcx::DStream *ds = nullptr;
-    uint64_t *symb = nullptr;
-    uint16_t *tbl = nullptr, *child = nullptr;
-    uint8_t *sym = nullptr;
-    uint32_t *glen = nullptr;
-    uint64_t *words = nullptr;        // [0] total out, [1] error bits, [2] symbol bytes, [3] golomb values,
-                                      // [4..7] Jacobi rounds / serial fallbacks (symbols, golomb)
-    uint64_t *host_words = nullptr;
-    bool profiling = false, timed = false;
-    hipEvent_t ev[fcx::kDStages + 1] = {};
-    // FCX8 (fcx_lz78_decompress_shard): its scratch, and the stage times of the last profiled call
-    void *lz78 = nullptr;
-    void (*lz78_free)(void *) = nullptr;
-    bool timed78 = false;
-    float ms78[fcx::kD78Stages] = {};
-    hipEvent_t ev78[fcx::kD78Stages + 1] = {};
+    bool profiling = false;
+    fcx::Dec7 d7;
+    std::unique_ptr<fcx::Scratch78, fcx::Calls<fcx::free_scratch78>> d78;
+    // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
+    fcx::StageTimes times{1, fcx::kD78Stages};
 };
 
 #endif  // FCX_DEC_SHARED_H

@@ -55,8 +55,20 @@ constexpr uint32_t kRmSpan = 512;                // run-mode tiles keep m[] rows
 constexpr uint32_t kTileMatches = kTile / 4;     // compact match list slots per tile (a match covers >= 4)
 constexpr uint32_t kConvAll = 0xFFFFu;           // tile conv record: k_emit takes every m from m[]
 constexpr uint32_t kCharSeg = 64;                    // chars per segment descriptor (one k_encode lane's symbols)
-constexpr uint32_t kErrScratch = 8u;                 // device error bit: inconsistent per-tile scratch (k_emit)
 constexpr uint32_t kCdMixed = 0xFFFFFFFFu;       // chars segment descriptor: not a run of input bytes
+
+// device error bits of a compress call: a Huffman code past 32 bits (k_tree), the output past its
+// capacity (k_scan_blocks), inconsistent per-tile scratch (k_emit)
+constexpr uint32_t kErrCodeLen = 1u, kErrCapacity = 4u, kErrScratch = 8u;
+
+// ---- status words of a compress call --------------------------------------------------------
+// fcx_ctx's dev_words, u64 each, zeroed before every call; host_words mirrors them
+constexpr uint32_t kCwTotal = 0;     // output bytes (the kernels' total)
+constexpr uint32_t kCwErr = 1;       // error bits, a u32 (the kernels' err)
+constexpr uint32_t kCwLazy = 2;      // lazy tiles, a u32: k_tree adds them at err + kErrToLazy
+constexpr uint32_t kErrToLazy = 2 * (kCwLazy - kCwErr);   // (in u32 steps)
+constexpr uint32_t kCwHeadBytes = 16;    // [kCwTotal, kCwErr]: what a length read copies back
+constexpr uint32_t kCwRouteBytes = 64;   // byte offset of the route counters: kRouteWords u32 per block group
 
 // per-block results of the parse/emit stage
 struct BlockInfo {
@@ -125,6 +137,21 @@ RestLaunch launch_match_rest_sparse, launch_match_rest_runs, launch_match_rest_k
 // the uniform unit (fcx_match_uniform.hip; it writes no m and no mtok)
 void launch_match_uniform(const MatchArgs &a, const uint32_t *list, const uint32_t *cnt, uint32_t *runs_list,
                           uint32_t *runs_cnt, uint8_t *tkind, uint32_t grid, hipStream_t st);
+// the other stages of a compress call: fcx_route.hip, fcx_parse.hip, fcx_entropy.hip (ev: the stage
+// events of a profiled call, or null)
+void launch_classify(const uint8_t *in, const Layout &L, uint32_t *lists, uint32_t stride, uint32_t *cnt,
+                     uint8_t *tkind, hipStream_t st);
+void launch_route_mark(uint32_t *dst, const uint32_t *src, hipStream_t st);
+void launch_parse(const uint8_t *in, const Layout &L, uint32_t *m, const uint64_t *mbits, uint64_t *chain,
+                  const uint64_t *chain_pfx, const uint32_t *tinfo, const uint32_t *mtok, uint64_t *fp,
+                  uint32_t *tile_off, uint32_t *tconv, BlockInfo *binfo, uint8_t *s_flags, uint8_t *s_chars,
+                  uint8_t *s_p, uint8_t *s_golomb, uint16_t *thist, uint32_t *sdesc, uint32_t *err, hipStream_t st,
+                  hipEvent_t *ev, uint32_t emit_dbg = 0);
+void launch_entropy(const Layout &L, BlockInfo *binfo, uint8_t *s0, uint8_t *s1, uint8_t *s2, uint8_t *s3,
+                    const uint16_t *thist, uint32_t *ctab, uint8_t *ltab, uint8_t *hhdr, uint64_t *cstat,
+                    uint64_t *blk_off, uint64_t *total, uint8_t *out, uint64_t cap, uint32_t *err, const uint8_t *in,
+                    const uint32_t *sdesc, hipStream_t st, hipEvent_t *ev, hipEvent_t wait_scan, hipEvent_t rec_scan,
+                    uint32_t tree_dbg = 0);
 
 // ---- wave64 helpers --------------------------------------------------------
 __device__ inline uint32_t lane_id() { return __lane_id(); }

@@ -32,32 +32,17 @@
 #include <vector>
 
 #include "fcx.h"
+#include "fcx_device.h"   // the compress status words and error bits a peer's result mirrors
+#include "fcx_host.h"
 
-namespace fcx {
-void set_last_error(const std::string &m);
-}
+using namespace fcx;
 
 namespace {
 
-int dfail(int code, const std::string &msg) {
-    fcx::set_last_error(msg);
-    return code;
-}
-
-#define DHIP(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return dfail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define DNCCL(expr)                                                                             \
     do {                                                                                        \
         ncclResult_t r_ = (expr);                                                               \
-        if (r_ != ncclSuccess) return dfail(FCX_ERR_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
-    } while (0)
-#define DTRY(expr)                                                                              \
-    do {                                                                                        \
-        int rc_ = (expr);                                                                       \
-        if (rc_) return rc_;                                                                    \
+        if (r_ != ncclSuccess) return fail(FCX_ERR_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
 // ---- transport seam ------------------------------------------------------------------------
@@ -299,7 +284,7 @@ struct LoopTransport final : Transport {
         return FCX_OK;
     }
     int group_end() override {
-        if (depth <= 0) return dfail(FCX_ERR_ARG, "loopback transport: group_end without group_start");
+        if (depth <= 0) return fail(FCX_ERR_ARG, "loopback transport: group_end without group_start");
         if (--depth) return FCX_OK;
         return flush();
     }
@@ -309,13 +294,13 @@ struct LoopTransport final : Transport {
         return depth ? FCX_OK : flush();
     }
     int send(const void *buf, uint64_t bytes, int peer, hipStream_t st) override {
-        if (peer < 0 || peer >= hub->nranks || peer == rank) return dfail(FCX_ERR_ARG, "loopback transport: bad peer");
+        if (peer < 0 || peer >= hub->nranks || peer == rank) return fail(FCX_ERR_ARG, "loopback transport: bad peer");
         auto o = std::make_unique<LoopOp>();
         o->kind = kSend; o->peer = peer; o->sbuf = buf; o->bytes = bytes; o->st = st;
         return add(std::move(o));
     }
     int recv(void *buf, uint64_t bytes, int peer, hipStream_t st) override {
-        if (peer < 0 || peer >= hub->nranks || peer == rank) return dfail(FCX_ERR_ARG, "loopback transport: bad peer");
+        if (peer < 0 || peer >= hub->nranks || peer == rank) return fail(FCX_ERR_ARG, "loopback transport: bad peer");
         auto o = std::make_unique<LoopOp>();
         o->kind = kRecv; o->peer = peer; o->rbuf = buf; o->bytes = bytes; o->st = st;
         return add(std::move(o));
@@ -342,15 +327,15 @@ struct LoopTransport final : Transport {
         std::vector<std::unique_ptr<LoopOp>> ops;
         ops.swap(pending);
         if (ops.empty()) return FCX_OK;
-        DHIP(hipSetDevice(hub->device));
+        FCX_HIP(hipSetDevice(hub->device));
         std::unique_lock<std::mutex> lk(hub->mu);
-        if (hub->aborted) return dfail(FCX_ERR_RCCL, hub->abort_msg);
+        if (hub->aborted) return fail(FCX_ERR_RCCL, hub->abort_msg);
         for (size_t i = 0; i < ops.size(); i++) {
             ops[i]->posted = hub->event();
             if (!ops[i]->posted || hipEventRecord(ops[i]->posted, ops[i]->st) != hipSuccess) {
                 for (size_t j = 0; j <= i; j++)   // nothing was posted: every event taken goes back
                     if (ops[j]->posted) hub->retire(ops[j]->posted);
-                return dfail(FCX_ERR_HIP, "loopback transport: event record");
+                return fail(FCX_ERR_HIP, "loopback transport: event record");
             }
         }
         for (auto &o : ops) hub->post(o.get());
@@ -375,7 +360,7 @@ struct LoopTransport final : Transport {
                     delete o->done;
                 }
             }
-            return dfail(FCX_ERR_RCCL, hub->abort_msg);
+            return fail(FCX_ERR_RCCL, hub->abort_msg);
         }
         int rc = FCX_OK;
         std::string msg;
@@ -393,7 +378,7 @@ struct LoopTransport final : Transport {
                 delete o->done;
             }
         }
-        return rc ? dfail(rc, msg) : FCX_OK;
+        return rc ? fail(rc, msg) : FCX_OK;
     }
 };
 
@@ -441,19 +426,19 @@ int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, ui
                  uint64_t *total, int mode, hipStream_t st, int status = FCX_OK) {
     const int n = d->nranks, rank = d->base_rank + li;
     Transport &t = *d->tr[li];
-    DHIP(hipSetDevice(d->devices[li]));
+    FCX_HIP(hipSetDevice(d->devices[li]));
     uint64_t *ds = d->d_sizes[li];
     const bool receives = mode == FCX_DIST_ALLGATHER || rank == 0;
     const uint64_t mine[2] = {status ? kFailed : seg_len, receives ? cap : kFailed};
-    DHIP(hipMemcpyAsync(ds + 2 * rank, mine, sizeof(mine), hipMemcpyHostToDevice, st));
-    DTRY(t.allgather(ds + 2 * rank, ds, sizeof(mine), st));
+    FCX_HIP(hipMemcpyAsync(ds + 2 * rank, mine, sizeof(mine), hipMemcpyHostToDevice, st));
+    FCX_TRY(t.allgather(ds + 2 * rank, ds, sizeof(mine), st));
     std::vector<uint64_t> words(2 * (size_t)n), sizes(n), offs(n, 0);
-    DHIP(hipMemcpyAsync(words.data(), ds, words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    DHIP(hipStreamSynchronize(st));
+    FCX_HIP(hipMemcpyAsync(words.data(), ds, words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
     if (status) return status;   // (this rank's own message is already set)
     for (int r = 0; r < n; r++) {
         if (words[2 * r] == kFailed)
-            return dfail(FCX_ERR_RCCL, "fcx_dist_concat: rank " + std::to_string(r) + " failed; no segment exchanged");
+            return fail(FCX_ERR_RCCL, "fcx_dist_concat: rank " + std::to_string(r) + " failed; no segment exchanged");
         sizes[r] = words[2 * r];
     }
     for (int r = 1; r < n; r++) offs[r] = offs[r - 1] + sizes[r - 1];
@@ -461,14 +446,14 @@ int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, ui
     *total = tot;
     for (int r = 0; r < n; r++)   // every receiving rank's capacity, judged identically everywhere
         if (words[2 * r + 1] != kFailed && tot > words[2 * r + 1])
-            return dfail(FCX_ERR_CAPACITY, "fcx_dist_concat: output capacity of rank " + std::to_string(r) +
+            return fail(FCX_ERR_CAPACITY, "fcx_dist_concat: output capacity of rank " + std::to_string(r) +
                                                " too small (" + std::to_string(tot) + " B)");
     // own segment to its offset (skipped when it already lives there); the exchanged size
     // is what every peer expects, so it is the one sent and received
     const uint64_t own = sizes[rank];
     if (receives && own && d_seg != d_out + offs[rank])
-        DHIP(hipMemcpyAsync(d_out + offs[rank], d_seg, own, hipMemcpyDeviceToDevice, st));
-    DTRY(t.group_start());
+        FCX_HIP(hipMemcpyAsync(d_out + offs[rank], d_seg, own, hipMemcpyDeviceToDevice, st));
+    FCX_TRY(t.group_start());
     int rc = FCX_OK;
     if (mode == FCX_DIST_GATHER) {
         if (rank == 0) {
@@ -484,34 +469,34 @@ int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, ui
     const int rc2 = t.group_end();
     if (rc) return rc;
     if (rc2) return rc2;
-    DHIP(hipStreamSynchronize(st));
-    if (own != seg_len) return dfail(FCX_ERR_INTERNAL, "fcx_dist_concat: size exchange mismatch");
+    FCX_HIP(hipStreamSynchronize(st));
+    if (own != seg_len) return fail(FCX_ERR_INTERNAL, "fcx_dist_concat: size exchange mismatch");
     return FCX_OK;
 }
 
 // fcx_dist_compress_gather's stream, length words, control words and events (sized for
 // FCX_DIST_MAX_SUB sub-batches of every rank), and rank 0's staging buffer of >= `stage` bytes
 int ensure_gather(fcx_dist *d, uint64_t stage) {
-    DHIP(hipSetDevice(d->devices[0]));
+    FCX_HIP(hipSetDevice(d->devices[0]));
     const size_t words = 2ull * FCX_DIST_MAX_SUB * (size_t)d->nranks;
     if (!d->cst) {
-        DHIP(hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking));
-        DHIP(hipMalloc((void **)&d->d_words, words * sizeof(uint64_t)));
-        DHIP(hipHostMalloc((void **)&d->h_words, words * sizeof(uint64_t), hipHostMallocDefault));
-        DHIP(hipMalloc((void **)&d->d_ctl, 4 * sizeof(uint64_t)));
-        DHIP(hipHostMalloc((void **)&d->h_ctl, 4 * sizeof(uint64_t), hipHostMallocDefault));
+        FCX_HIP(hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking));
+        FCX_HIP(hipMalloc((void **)&d->d_words, words * sizeof(uint64_t)));
+        FCX_HIP(hipHostMalloc((void **)&d->h_words, words * sizeof(uint64_t), hipHostMallocDefault));
+        FCX_HIP(hipMalloc((void **)&d->d_ctl, 4 * sizeof(uint64_t)));
+        FCX_HIP(hipHostMalloc((void **)&d->h_ctl, 4 * sizeof(uint64_t), hipHostMallocDefault));
         const uint64_t ctl[4] = {kFailed, 1, 0, 0};
-        DHIP(hipMemcpy(d->d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+        FCX_HIP(hipMemcpy(d->d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice));
         d->ev.assign(FCX_DIST_MAX_SUB, nullptr);
-        for (auto &e : d->ev) DHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : d->copy_ev) DHIP(hipEventCreate(&e));
+        for (auto &e : d->ev) FCX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : d->copy_ev) FCX_HIP(hipEventCreate(&e));
     }
     if (stage > d->stage_cap) {
-        if (d->d_stage) DHIP(hipFree(d->d_stage));
+        if (d->d_stage) FCX_HIP(hipFree(d->d_stage));
         d->d_stage = nullptr;
         d->stage_cap = 0;
         if (hipMalloc((void **)&d->d_stage, stage) != hipSuccess)
-            return dfail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: staging buffer of " + std::to_string(stage) + " B");
+            return fail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: staging buffer of " + std::to_string(stage) + " B");
         d->stage_cap = stage;
     }
     return FCX_OK;
@@ -590,13 +575,13 @@ int ensure_local(fcx_dist *d, uint32_t block, uint64_t per, uint64_t round) {
     for (size_t i = 0; i < nd; i++) {   // one device at a time
         int r = FCX_OK;
         if (hipSetDevice(d->devices[i]) != hipSuccess || hipStreamCreate(&d->st[i]) != hipSuccess)
-            r = dfail(FCX_ERR_HIP, "fcx_dist_compress_host: stream");
+            r = fail(FCX_ERR_HIP, "fcx_dist_compress_host: stream");
         if (!r) r = fcx_ctx_create(&d->ctx[i], d->devices[i], block, per);
         d->dincap[i] = per;
         d->dcap[i] = fcx_shard_bound(i == 0 ? round : per, block);
         if (!r && (hipMalloc((void **)&d->din[i], per) != hipSuccess ||
                    hipMalloc((void **)&d->dout[i], d->dcap[i]) != hipSuccess))
-            r = dfail(FCX_ERR_NOMEM, "fcx_dist_compress_host: device buffers");
+            r = fail(FCX_ERR_NOMEM, "fcx_dist_compress_host: device buffers");
         if (r) { release_local(d); return r; }
     }
     return FCX_OK;
@@ -605,8 +590,8 @@ int ensure_local(fcx_dist *d, uint32_t block, uint64_t per, uint64_t round) {
 int make_dist(fcx_dist **out, fcx_dist *d) {
     d->d_sizes.resize(d->devices.size(), nullptr);
     for (size_t i = 0; i < d->devices.size(); i++) {
-        DHIP(hipSetDevice(d->devices[i]));
-        DHIP(hipMalloc((void **)&d->d_sizes[i], 2 * sizeof(uint64_t) * (size_t)d->nranks));
+        FCX_HIP(hipSetDevice(d->devices[i]));
+        FCX_HIP(hipMalloc((void **)&d->d_sizes[i], 2 * sizeof(uint64_t) * (size_t)d->nranks));
     }
     *out = d;
     return FCX_OK;
@@ -615,8 +600,8 @@ int make_dist(fcx_dist **out, fcx_dist *d) {
 int need_device(int device) {
     int have = 0;
     if (hipGetDeviceCount(&have) != hipSuccess || have == 0)
-        return dfail(FCX_ERR_HIP, "no HIP device: the compress path is GPU-only");
-    if (device < 0 || device >= have) return dfail(FCX_ERR_ARG, "bad device index");
+        return fail(FCX_ERR_HIP, "no HIP device: the compress path is GPU-only");
+    if (device < 0 || device >= have) return fail(FCX_ERR_ARG, "bad device index");
     return FCX_OK;
 }
 
@@ -632,7 +617,7 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
         bound[r] = pieces_bound(rank_bytes[r], B, nsub);
         stage += bound[r];
     }
-    DTRY(ensure_gather(d, stage));
+    FCX_TRY(ensure_gather(d, stage));
     uint64_t *dw = d->d_words, *hw = d->h_words;
     // own range straight into d_out at offset 0 (a failure is reported after the peers' pieces
     // are drained, so no peer is left in a send), the peers' pieces into the staging regions on
@@ -643,14 +628,14 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
     std::string peer_err;
     for (uint32_t s = 0; s < nsub && N > 1; s++) {
         uint64_t *ws = dw + 2ull * s * N, *hs = hw + 2ull * s * N;
-        DTRY(t.group_start());
+        FCX_TRY(t.group_start());
         int rc = FCX_OK;
         for (int r = 1; r < N && !rc; r++) rc = t.recv(ws + 2 * r, 2 * sizeof(uint64_t), r, d->cst);
         const int rc2 = t.group_end();
-        DTRY(rc);
-        DTRY(rc2);
-        DHIP(hipMemcpyAsync(hs, ws, 2ull * N * sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
-        DHIP(hipStreamSynchronize(d->cst));
+        FCX_TRY(rc);
+        FCX_TRY(rc2);
+        FCX_HIP(hipMemcpyAsync(hs, ws, 2ull * N * sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
+        FCX_HIP(hipStreamSynchronize(d->cst));
         // a piece beyond its peer's staging bound (the ranks disagree on rank_bytes; a peer checks
         // its pieces against the same bound otherwise) is still received -- into the drain buffer,
         // so the peer's send completes and the protocol runs on to the failing verdict
@@ -660,14 +645,14 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
             if (!err && len != kFailed && len && fill[r] + len > bound[r]) drain = std::max(drain, len);
         }
         if (drain > d->drain_cap) {
-            if (d->d_drain) DHIP(hipFree(d->d_drain));
+            if (d->d_drain) FCX_HIP(hipFree(d->d_drain));
             d->d_drain = nullptr;
             d->drain_cap = 0;
             if (hipMalloc((void **)&d->d_drain, drain) != hipSuccess)
-                return dfail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: drain buffer of " + std::to_string(drain) + " B");
+                return fail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: drain buffer of " + std::to_string(drain) + " B");
             d->drain_cap = drain;
         }
-        DTRY(t.group_start());
+        FCX_TRY(t.group_start());
         for (int r = 1; r < N && !rc; r++) {
             const uint64_t len = hs[2 * r], err = hs[2 * r + 1];
             if (err || len == kFailed) {
@@ -684,10 +669,10 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
             fill[r] += len;
         }
         const int rc3 = t.group_end();
-        DTRY(rc);
-        DTRY(rc3);
+        FCX_TRY(rc);
+        FCX_TRY(rc3);
     }
-    DHIP(hipStreamSynchronize(d->cst));
+    FCX_HIP(hipStreamSynchronize(d->cst));
     uint64_t own = 0;
     if (!own_rc) {
         own_rc = fcx_ctx_read_out_len(c, &own);
@@ -707,28 +692,28 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
     }
     if (N > 1) {   // the job's verdict to every peer, so every rank returns the same outcome
         d->h_ctl[2] = (uint64_t)(int64_t)verdict;
-        DHIP(hipMemcpyAsync(d->d_ctl + 2, d->h_ctl + 2, sizeof(uint64_t), hipMemcpyHostToDevice, d->cst));
-        DTRY(t.group_start());
+        FCX_HIP(hipMemcpyAsync(d->d_ctl + 2, d->h_ctl + 2, sizeof(uint64_t), hipMemcpyHostToDevice, d->cst));
+        FCX_TRY(t.group_start());
         int rc = FCX_OK;
         for (int r = 1; r < N && !rc; r++) rc = t.send(d->d_ctl + 2, sizeof(uint64_t), r, d->cst);
         const int rc2 = t.group_end();
-        DTRY(rc);
-        DTRY(rc2);
+        FCX_TRY(rc);
+        FCX_TRY(rc2);
     }
     if (verdict) {
-        DHIP(hipStreamSynchronize(d->cst));
-        DHIP(hipStreamSynchronize(st));
-        return dfail(verdict, msg);
+        FCX_HIP(hipStreamSynchronize(d->cst));
+        FCX_HIP(hipStreamSynchronize(st));
+        return fail(verdict, msg);
     }
     off = own;
-    DHIP(hipEventRecord(d->copy_ev[0], st));
+    FCX_HIP(hipEventRecord(d->copy_ev[0], st));
     for (int r = 1; r < N; r++) {   // the peers' bytes behind the own segment, in rank order
-        if (fill[r]) DHIP(hipMemcpyAsync(d_out + off, d->d_stage + soff[r], fill[r], hipMemcpyDeviceToDevice, st));
+        if (fill[r]) FCX_HIP(hipMemcpyAsync(d_out + off, d->d_stage + soff[r], fill[r], hipMemcpyDeviceToDevice, st));
         off += fill[r];
     }
-    DHIP(hipEventRecord(d->copy_ev[1], st));
-    DHIP(hipStreamSynchronize(d->cst));
-    DHIP(hipStreamSynchronize(st));
+    FCX_HIP(hipEventRecord(d->copy_ev[1], st));
+    FCX_HIP(hipStreamSynchronize(d->cst));
+    FCX_HIP(hipStreamSynchronize(st));
     if (hipEventElapsedTime(&d->copy_ms, d->copy_ev[0], d->copy_ev[1]) != hipSuccess) d->copy_ms = -1.f;
     *total = off;
     return FCX_OK;
@@ -742,7 +727,7 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
 int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t nsub, uint32_t B,
                 uint8_t *d_out, uint64_t cap, uint64_t *total, hipStream_t st) {
     Transport &t = *d->tr[0];
-    DTRY(ensure_gather(d, 0));
+    FCX_TRY(ensure_gather(d, 0));
     uint64_t *dw = d->d_words, *hw = d->h_words;
     std::vector<uint64_t> ro(nsub, 0), pb(nsub, 0), lens(nsub, 0);
     int status = FCX_OK;
@@ -755,7 +740,7 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
         ro[s] = o;
         pb[s] = round16(fcx_shard_bound(hi - lo, B));
         if (status == FCX_OK && o + pb[s] > cap) {
-            status = dfail(FCX_ERR_CAPACITY, "fcx_dist_compress_gather: peer output capacity too small (see fcx_dist_gather_bound)");
+            status = fail(FCX_ERR_CAPACITY, "fcx_dist_compress_gather: peer output capacity too small (see fcx_dist_gather_bound)");
             msg = fcx_last_error();
         }
         if (status == FCX_OK) {
@@ -763,9 +748,9 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
             if (status) msg = fcx_last_error();
         }
         if (status == FCX_OK) {
-            DHIP(hipMemcpyAsync(dw + 2 * s, fcx_ctx_device_out_len(c), 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-            DHIP(hipMemcpyAsync(hw + 2 * s, dw + 2 * s, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            DHIP(hipEventRecord(d->ev[s], st));
+            FCX_HIP(hipMemcpyAsync(dw + 2 * s, fcx_ctx_device_out_len(c), kCwHeadBytes, hipMemcpyDeviceToDevice, st));   // [kCwTotal, kCwErr]
+            FCX_HIP(hipMemcpyAsync(hw + 2 * s, dw + 2 * s, kCwHeadBytes, hipMemcpyDeviceToHost, st));
+            FCX_HIP(hipEventRecord(d->ev[s], st));
             enq = s + 1;
         }
         o += pb[s];
@@ -778,41 +763,41 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
                 failed = true;
             } else if (hipEventSynchronize(d->ev[s]) != hipSuccess) {
                 failed = true;
-                if (status == FCX_OK) { status = dfail(FCX_ERR_HIP, "fcx_dist_compress_gather: compress failed"); msg = fcx_last_error(); }
-            } else if (hw[2 * s + 1]) {
+                if (status == FCX_OK) { status = fail(FCX_ERR_HIP, "fcx_dist_compress_gather: compress failed"); msg = fcx_last_error(); }
+            } else if (hw[2 * s + kCwErr]) {
                 failed = true;
-                status = dfail(hw[2 * s + 1] & 4u ? FCX_ERR_CAPACITY : FCX_ERR_INTERNAL,
-                               "fcx_dist_compress_gather: device error bits " + std::to_string(hw[2 * s + 1]));
+                status = fail(hw[2 * s + kCwErr] & kErrCapacity ? FCX_ERR_CAPACITY : FCX_ERR_INTERNAL,
+                               "fcx_dist_compress_gather: device error bits " + std::to_string(hw[2 * s + kCwErr]));
                 msg = fcx_last_error();
-            } else if (hw[2 * s] > pb[s]) {
+            } else if (hw[2 * s + kCwTotal] > pb[s]) {
                 failed = true;
-                status = dfail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: piece longer than its bound");
+                status = fail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: piece longer than its bound");
                 msg = fcx_last_error();
             } else if ((int)s == d->fail_piece) {
                 failed = true;
-                status = dfail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: injected failure (fcx_dist_debug_fail)");
+                status = fail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: injected failure (fcx_dist_debug_fail)");
                 msg = fcx_last_error();
             }
         }
         if (failed) {   // this and every later round: the constant failure words
-            DTRY(t.send(d->d_ctl, 2 * sizeof(uint64_t), 0, d->cst));
+            FCX_TRY(t.send(d->d_ctl, 2 * sizeof(uint64_t), 0, d->cst));
             continue;
         }
         lens[s] = hw[2 * s];
-        DHIP(hipStreamWaitEvent(d->cst, d->ev[s], 0));
-        DTRY(t.send(dw + 2 * s, 2 * sizeof(uint64_t), 0, d->cst));
-        if (lens[s]) DTRY(t.send(d_out + ro[s], lens[s], 0, d->cst));
+        FCX_HIP(hipStreamWaitEvent(d->cst, d->ev[s], 0));
+        FCX_TRY(t.send(dw + 2 * s, 2 * sizeof(uint64_t), 0, d->cst));
+        if (lens[s]) FCX_TRY(t.send(d_out + ro[s], lens[s], 0, d->cst));
         sent += lens[s];
     }
     // the job's verdict from rank 0
-    DTRY(t.recv(d->d_ctl + 2, sizeof(uint64_t), 0, d->cst));
-    DHIP(hipMemcpyAsync(d->h_ctl + 2, d->d_ctl + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
-    DHIP(hipStreamSynchronize(d->cst));
-    DHIP(hipStreamSynchronize(st));
-    if (status) return dfail(status, msg);
+    FCX_TRY(t.recv(d->d_ctl + 2, sizeof(uint64_t), 0, d->cst));
+    FCX_HIP(hipMemcpyAsync(d->h_ctl + 2, d->d_ctl + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
+    FCX_HIP(hipStreamSynchronize(d->cst));
+    FCX_HIP(hipStreamSynchronize(st));
+    if (status) return fail(status, msg);
     const int64_t verdict = (int64_t)d->h_ctl[2];
     if (verdict)
-        return dfail(verdict < 0 && verdict >= FCX_ERR_RCCL ? (int)verdict : FCX_ERR_RCCL,
+        return fail(verdict < 0 && verdict >= FCX_ERR_RCCL ? (int)verdict : FCX_ERR_RCCL,
                      "fcx_dist_compress_gather: rank 0 reports the job failed (code " + std::to_string(verdict) + ")");
     *total = sent;
     return FCX_OK;
@@ -858,23 +843,23 @@ uint64_t fcx_dist_gather_bound(uint64_t n, uint32_t block_bytes, uint32_t nsub) 
 int fcx_dist_compress_gather(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const uint64_t *rank_bytes,
                              uint32_t nsub, uint8_t *d_out, uint64_t cap, uint64_t *total, void *stream) {
     if (!d || !c || !rank_bytes || !total || !d_out || (n && !d_in) || nsub < 1 || nsub > FCX_DIST_MAX_SUB)
-        return dfail(FCX_ERR_ARG, "fcx_dist_compress_gather: bad argument");
+        return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: bad argument");
     if (d->tr.size() != 1)
-        return dfail(FCX_ERR_ARG, "fcx_dist_compress_gather: one rank per handle (fcx_dist_init_rank / fcx_dist_init_loop)");
+        return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: one rank per handle (fcx_dist_init_rank / fcx_dist_init_loop)");
     const int rank = d->base_rank;
-    if (rank_bytes[rank] != n) return dfail(FCX_ERR_ARG, "fcx_dist_compress_gather: rank_bytes[rank] != n");
+    if (rank_bytes[rank] != n) return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: rank_bytes[rank] != n");
     int dev = 0;
     uint32_t B = 0;
-    DTRY(fcx_ctx_info(c, &dev, &B, nullptr));
-    if (dev != d->devices[0]) return dfail(FCX_ERR_ARG, "fcx_dist_compress_gather: context on another device");
+    FCX_TRY(fcx_ctx_info(c, &dev, &B, nullptr));
+    if (dev != d->devices[0]) return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: context on another device");
     *total = 0;
-    DHIP(hipSetDevice(dev));
+    FCX_HIP(hipSetDevice(dev));
     if (rank == 0) return gather_root(d, c, d_in, n, rank_bytes, nsub, B, d_out, cap, total, (hipStream_t)stream);
     return gather_peer(d, c, d_in, n, nsub, B, d_out, cap, total, (hipStream_t)stream);
 }
 
 int fcx_dist_unique_id(uint8_t *id) {
-    if (!id) return dfail(FCX_ERR_ARG, "fcx_dist_unique_id: NULL");
+    if (!id) return fail(FCX_ERR_ARG, "fcx_dist_unique_id: NULL");
     ncclUniqueId u;
     DNCCL(ncclGetUniqueId(&u));
     memcpy(id, u.internal, FCX_DIST_ID_BYTES);
@@ -882,9 +867,9 @@ int fcx_dist_unique_id(uint8_t *id) {
 }
 
 int fcx_dist_init_rank(fcx_dist **out, int nranks, int rank, const uint8_t *id, int device) {
-    if (!out || !id || nranks <= 0 || rank < 0 || rank >= nranks) return dfail(FCX_ERR_ARG, "fcx_dist_init_rank: bad argument");
+    if (!out || !id || nranks <= 0 || rank < 0 || rank >= nranks) return fail(FCX_ERR_ARG, "fcx_dist_init_rank: bad argument");
     *out = nullptr;
-    DHIP(hipSetDevice(device));
+    FCX_HIP(hipSetDevice(device));
     ncclUniqueId u;
     memcpy(u.internal, id, FCX_DIST_ID_BYTES);
     ncclComm_t comm;
@@ -900,9 +885,9 @@ int fcx_dist_init_rank(fcx_dist **out, int nranks, int rank, const uint8_t *id, 
 }
 
 int fcx_dist_init_local(fcx_dist **out, int ndev, const int *devices) {
-    if (!out || ndev <= 0 || !devices) return dfail(FCX_ERR_ARG, "fcx_dist_init_local: bad argument");
+    if (!out || ndev <= 0 || !devices) return fail(FCX_ERR_ARG, "fcx_dist_init_local: bad argument");
     *out = nullptr;
-    for (int i = 0; i < ndev; i++) DTRY(need_device(devices[i]));
+    for (int i = 0; i < ndev; i++) FCX_TRY(need_device(devices[i]));
     std::vector<ncclComm_t> comms(ndev);
     DNCCL(ncclCommInitAll(comms.data(), ndev, devices));
     fcx_dist *d = new fcx_dist();
@@ -916,10 +901,10 @@ int fcx_dist_init_local(fcx_dist **out, int ndev, const int *devices) {
 }
 
 int fcx_loop_create(fcx_loop **out, int nranks, int device, uint32_t timeout_ms) {
-    if (!out || nranks <= 0) return dfail(FCX_ERR_ARG, "fcx_loop_create: bad argument");
+    if (!out || nranks <= 0) return fail(FCX_ERR_ARG, "fcx_loop_create: bad argument");
     *out = nullptr;
-    DTRY(need_device(device));
-    DHIP(hipSetDevice(device));
+    FCX_TRY(need_device(device));
+    FCX_HIP(hipSetDevice(device));
     fcx_loop *h = new fcx_loop();
     h->nranks = nranks;
     h->device = device;
@@ -929,7 +914,7 @@ int fcx_loop_create(fcx_loop **out, int nranks, int device, uint32_t timeout_ms)
     h->coll_seq.assign(nranks, 0);
     if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
         delete h;
-        return dfail(FCX_ERR_HIP, "fcx_loop_create: stream");
+        return fail(FCX_ERR_HIP, "fcx_loop_create: stream");
     }
     *out = h;
     return FCX_OK;
@@ -940,7 +925,7 @@ void fcx_loop_destroy(fcx_loop *h) {
 }
 
 int fcx_dist_init_loop(fcx_dist **out, fcx_loop *h, int rank) {
-    if (!out || !h || rank < 0 || rank >= h->nranks) return dfail(FCX_ERR_ARG, "fcx_dist_init_loop: bad argument");
+    if (!out || !h || rank < 0 || rank >= h->nranks) return fail(FCX_ERR_ARG, "fcx_dist_init_loop: bad argument");
     *out = nullptr;
     {
         std::lock_guard<std::mutex> lk(h->mu);
@@ -957,10 +942,10 @@ int fcx_dist_init_loop(fcx_dist **out, fcx_loop *h, int rank) {
 }
 
 int fcx_dist_init_loop_local(fcx_dist **out, int nranks, int device, uint32_t timeout_ms) {
-    if (!out || nranks <= 0) return dfail(FCX_ERR_ARG, "fcx_dist_init_loop_local: bad argument");
+    if (!out || nranks <= 0) return fail(FCX_ERR_ARG, "fcx_dist_init_loop_local: bad argument");
     *out = nullptr;
     fcx_loop *h = nullptr;
-    DTRY(fcx_loop_create(&h, nranks, device, timeout_ms));
+    FCX_TRY(fcx_loop_create(&h, nranks, device, timeout_ms));
     fcx_dist *d = new fcx_dist();
     d->nranks = nranks;
     d->base_rank = 0;
@@ -979,13 +964,13 @@ int fcx_dist_init_loop_local(fcx_dist **out, int nranks, int device, uint32_t ti
 const char *fcx_dist_transport(fcx_dist *d) { return d && !d->tr.empty() ? d->tr[0]->name() : ""; }
 
 int fcx_dist_gather_copy_ms(fcx_dist *d, float *ms) {
-    if (!d || !ms) return dfail(FCX_ERR_ARG, "fcx_dist_gather_copy_ms: NULL argument");
+    if (!d || !ms) return fail(FCX_ERR_ARG, "fcx_dist_gather_copy_ms: NULL argument");
     *ms = d->copy_ms;
     return FCX_OK;
 }
 
 int fcx_dist_debug_fail(fcx_dist *d, int piece) {
-    if (!d) return dfail(FCX_ERR_ARG, "NULL dist");
+    if (!d) return fail(FCX_ERR_ARG, "NULL dist");
     d->fail_piece = piece;
     return FCX_OK;
 }
@@ -1006,7 +991,7 @@ void fcx_dist_destroy(fcx_dist *d) {
 }
 
 int fcx_dist_size(fcx_dist *d, int *nranks, int *nlocal) {
-    if (!d) return dfail(FCX_ERR_ARG, "NULL dist");
+    if (!d) return fail(FCX_ERR_ARG, "NULL dist");
     if (nranks) *nranks = d->nranks;
     if (nlocal) *nlocal = (int)d->tr.size();
     return FCX_OK;
@@ -1016,17 +1001,17 @@ int fcx_dist_concat(fcx_dist *d, int local, const uint8_t *d_seg, uint64_t seg_l
                     uint64_t *total, int mode, void *stream) {
     if (!d || !total || local < 0 || local >= (int)d->tr.size() || (seg_len && !d_seg) ||
         (mode != FCX_DIST_GATHER && mode != FCX_DIST_ALLGATHER))
-        return dfail(FCX_ERR_ARG, "fcx_dist_concat: bad argument");
-    if (d->tr.size() > 1) return dfail(FCX_ERR_ARG, "fcx_dist_concat: a multi-device process uses fcx_dist_compress_host");
+        return fail(FCX_ERR_ARG, "fcx_dist_concat: bad argument");
+    if (d->tr.size() > 1) return fail(FCX_ERR_ARG, "fcx_dist_concat: a multi-device process uses fcx_dist_compress_host");
     return concat_local(d, local, d_seg, seg_len, d_out, cap, total, mode, (hipStream_t)stream);
 }
 
 int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t block_bytes, uint64_t round_bytes,
                            uint8_t *out, uint64_t cap, uint64_t *out_len) {
     if (!d || (n && !in) || !out || !out_len || block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return dfail(FCX_ERR_ARG, "fcx_dist_compress_host: bad argument");
+        return fail(FCX_ERR_ARG, "fcx_dist_compress_host: bad argument");
     if (d->base_rank != 0 || (int)d->tr.size() != d->nranks)
-        return dfail(FCX_ERR_ARG, "fcx_dist_compress_host: needs every rank in this process (fcx_dist_init_local)");
+        return fail(FCX_ERR_ARG, "fcx_dist_compress_host: needs every rank in this process (fcx_dist_init_local)");
     *out_len = 0;
     if (n == 0) return FCX_OK;
     const int nd = d->nranks;
@@ -1055,9 +1040,9 @@ int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t 
             const uint64_t hi = b1 * block_bytes < rn ? b1 * block_bytes : rn;
             int r = FCX_OK;
             uint64_t seg = 0, tot = 0;
-            if (hipSetDevice(d->devices[i]) != hipSuccess) r = dfail(FCX_ERR_HIP, "hipSetDevice");
+            if (hipSetDevice(d->devices[i]) != hipSuccess) r = fail(FCX_ERR_HIP, "hipSetDevice");
             if (!r && hi > lo && hipMemcpyAsync(din[i], in + done_in + lo, hi - lo, hipMemcpyHostToDevice, st[i]) != hipSuccess)
-                r = dfail(FCX_ERR_HIP, "fcx_dist_compress_host: H2D");
+                r = fail(FCX_ERR_HIP, "fcx_dist_compress_host: H2D");
             if (!r && hi > lo) r = fcx_compress_shard(ctx[i], din[i], hi - lo, dout[i], dcap[i], &seg, st[i]);
             // every rank enters the exchange, failed or not (a failure is published there)
             r = concat_local(d, i, dout[i], seg, dout[0], dcap[0], &tot, FCX_DIST_GATHER, st[i], r);
@@ -1071,12 +1056,12 @@ int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t 
         for (auto &t : th) t.join();
         for (int i = 0; i < nd; i++)
             if (rc[i]) {
-                return dfail(rc[i], "device " + std::to_string(d->devices[i]) + ": " + err[i]);
+                return fail(rc[i], "device " + std::to_string(d->devices[i]) + ": " + err[i]);
             }
-        if (done_out + total > cap) return dfail(FCX_ERR_CAPACITY, "fcx_dist_compress_host: output capacity too small");
+        if (done_out + total > cap) return fail(FCX_ERR_CAPACITY, "fcx_dist_compress_host: output capacity too small");
         (void)hipSetDevice(d->devices[0]);
         if (hipMemcpy(out + done_out, dout[0], total, hipMemcpyDeviceToHost) != hipSuccess)
-            return dfail(FCX_ERR_HIP, "fcx_dist_compress_host: D2H");
+            return fail(FCX_ERR_HIP, "fcx_dist_compress_host: D2H");
         done_out += total;
         done_in += rn;
     }

@@ -34,8 +34,6 @@
 
 namespace fcx {
 
-constexpr uint32_t kErrCodeLen = 1u, kErrCapacity = 4u;
-
 __device__ inline bool stream_active(const BlockInfo &bi, uint32_t s) {
     if (s == 0) return bi.slen[0] > 1;   // flags are Huffman-coded only when > 1 byte
     if (s == 3) return bi.gbits > 0;     // no golomb words -> nothing written (989-990)
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(kTreeT) void k_tree(Layout L, const uint16_t *__res
     asm volatile("" ::"s"(lazy_tiles), "s"(slen0), "s"(gbits));
     // the call's lazy tiles (k_stitch walked them serially), for the routing of later calls
     // (fcx_capi.hip: a unit that left tiles lazy is launched over its list, where hand-ons work)
-    if (s == 0 && tid == 0 && lazy_tiles) atomicAdd(err + 2, lazy_tiles);
+    if (s == 0 && tid == 0 && lazy_tiles) atomicAdd(err + kErrToLazy, lazy_tiles);
     if (s == 0 ? slen0 <= 1 : s == 3 ? gbits == 0 : false) {   // (stream_active)
         if (tid == 0) { bi.hdrlen[s] = 0; bi.nwords[s] = 0; }
         return;

@@ -1,0 +1,148 @@
+// fcx_host.h — the host layer the C ABI files share (no device code): the last-error helpers,
+// owned device / pinned memory, the stage-time recorder of the profiled paths and the deleter of
+// per-thread and lazily made objects.  DESIGN.md, "host layer".
+#ifndef FCX_HOST_H
+#define FCX_HOST_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <utility>
+
+#include "fcx.h"
+
+namespace fcx {
+
+// ---- errors: the text goes to fcx_last_error() (fcx_capi.hip), the code to the caller ----------
+void set_last_error(const std::string &m);
+inline int fail(int code, const std::string &msg) {
+    set_last_error(msg);
+    return code;
+}
+#define FCX_HIP(expr)                                                                                         \
+    do {                                                                                                      \
+        hipError_t e_ = (expr);                                                                               \
+        if (e_ != hipSuccess) return fcx::fail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+#define FCX_TRY(expr)          \
+    do {                       \
+        int rc_ = (expr);      \
+        if (rc_) return rc_;   \
+    } while (0)
+
+// ---- owned memory: device (hipMalloc) or pinned host (hipHostMalloc) ---------------------------
+// Frees what it holds when it goes; movable, so a struct of them is dropped as a whole by assigning
+// a fresh one.  Sizes are bytes; a request of 0 allocates 16.
+template <typename T, bool kPinned>
+struct Buf {
+    T *p = nullptr;
+    uint64_t bytes = 0;   // as requested
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            bytes = std::exchange(o.bytes, 0);
+        }
+        return *this;
+    }
+    ~Buf() { release(); }
+    void release() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+    // drops what it holds, then allocates: for the callers that report a failure as FCX_ERR_HIP
+    hipError_t alloc(uint64_t n) {
+        release();
+        const uint64_t req = n ? n : 16;
+        const hipError_t e = kPinned ? hipHostMalloc((void **)&p, req, hipHostMallocDefault) : hipMalloc((void **)&p, req);
+        if (e != hipSuccess) p = nullptr;
+        else bytes = n;
+        return e;
+    }
+    // holds >= n bytes afterwards; allocates anew (contents lost) only when it holds fewer
+    int reserve(uint64_t n, const char *what) {
+        if (p && n <= bytes) return FCX_OK;
+        const hipError_t e = alloc(n);
+        if (e == hipSuccess) return FCX_OK;
+        return fail(FCX_ERR_NOMEM, std::string(kPinned ? "hipHostMalloc " : "hipMalloc ") + what + ": " + hipGetErrorString(e));
+    }
+    operator T *() const { return p; }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
+
+// unique_ptr deleter that calls Fn: contexts a host thread keeps for itself
+// (thread_local std::unique_ptr<fcx_dctx, Calls<fcx_dctx_destroy>>, gone at thread exit) and parts
+// whose type is complete in one file only
+template <auto Fn>
+struct Calls {
+    template <typename T> void operator()(T *p) const { Fn(p); }
+};
+
+// ---- stage times of a profiled call ------------------------------------------------------------
+// Stage k runs between events k and k + 1 of a lane (compress: one lane per block group; the
+// launchers record into lane(g) themselves).  A call starts with reset() and makes its table
+// visible to the *_stage queries with publish(): at once with the lanes still to read (lazy: the
+// first query waits for them and sums stage k over the lanes), or at its end after add() has
+// summed the spans itself (eager: FCX8 reuses one lane's events per batch).
+struct StageTimes {
+    static constexpr int kLanes = 8, kStages = 11;
+    hipEvent_t ev[kLanes][kStages + 1] = {};
+    const char *const *names = nullptr;
+    int n = 0;         // stages of the published table; 0: the last call was not profiled
+    int pending = 0;   // lanes not read yet
+    float ms[kStages] = {};
+
+    StageTimes(int lanes, int stages) {
+        for (int g = 0; g < lanes; g++)
+            for (int i = 0; i <= stages; i++) (void)hipEventCreate(&ev[g][i]);
+    }
+    StageTimes(const StageTimes &) = delete;
+    StageTimes &operator=(const StageTimes &) = delete;
+    ~StageTimes() {
+        for (auto &lane : ev)
+            for (hipEvent_t e : lane)
+                if (e) (void)hipEventDestroy(e);
+    }
+    void reset() {
+        n = pending = 0;
+        for (float &v : ms) v = 0;
+    }
+    void publish(const char *const *table, int stages, int lanes = 0) {
+        names = table;
+        n = stages;
+        pending = lanes;
+    }
+    hipEvent_t *lane(int g = 0) { return ev[g]; }
+    void mark(int i, hipStream_t st) { (void)hipEventRecord(ev[0][i], st); }
+    // ms[k] += the span of stage k on lane g, first <= k < last, once event `last` has passed
+    int add(int first, int last, int g = 0) {
+        FCX_HIP(hipEventSynchronize(ev[g][last]));
+        for (int k = first; k < last; k++) {
+            float v = 0;
+            FCX_HIP(hipEventElapsedTime(&v, ev[g][k], ev[g][k + 1]));
+            ms[k] += v;
+        }
+        return FCX_OK;
+    }
+    // stage i of the published table (0 <= i < n)
+    int stage(int i, const char **name, float *out) {
+        if (pending) {
+            for (float &v : ms) v = 0;
+            for (int g = 0; g < pending; g++) FCX_TRY(add(0, n, g));
+            pending = 0;
+        }
+        if (name) *name = names[i];
+        if (out) *out = ms[i];
+        return FCX_OK;
+    }
+};
+
+}  // namespace fcx
+
+#endif  // FCX_HOST_H

@@ -33,8 +33,13 @@
 #include <algorithm>
 
 #include "fcx.h"
+#include "fcx_host.h"
 
 namespace fcx78 {
+
+// device error bits of a compress call: a Huffman code past 32 bits (a record's err, summed up by
+// k78_scan), the output past its capacity (k78_scan)
+constexpr uint32_t kErr78CodeLen = 1u, kErr78Capacity = 2u;
 
 constexpr uint32_t kTileTok = 8192;   // tokens per pack tile (256 lanes x 32)
 constexpr uint32_t kSortCap = 8192;   // bitonic sort capacity (>= the max group count 4097 of a 1 MiB block)
@@ -462,7 +467,7 @@ __global__ __launch_bounds__(1024) void k78_scan(Scratch S, uint64_t cap, uint32
     for (uint32_t b = b0; b < b1; b++) {
         const Rec78 &R = S.rec[b];
         if (R.N) sum += R.rec;
-        if (R.N && R.err) atomicOr(err, 1u);
+        if (R.N && R.err) atomicOr(err, kErr78CodeLen);
     }
     part[tid] = sum;
     __syncthreads();
@@ -481,7 +486,7 @@ __global__ __launch_bounds__(1024) void k78_scan(Scratch S, uint64_t cap, uint32
     __syncthreads();
     if (tid == 1023) {
         *S.total = base + part[1023];
-        if (base + part[1023] > cap) atomicOr(err, 2u);
+        if (base + part[1023] > cap) atomicOr(err, kErr78Capacity);
     }
 }
 
@@ -622,21 +627,9 @@ __global__ __launch_bounds__(256) void k78_write(Scratch S, uint8_t *__restrict_
 }  // namespace fcx78
 
 using namespace fcx78;
+using namespace fcx;
 
-namespace fcx {
-void set_last_error(const std::string &m);   // fcx_capi.hip (fcx_last_error)
-}
 namespace {
-int fail78(int code, const std::string &m) {
-    fcx::set_last_error(m);
-    return code;
-}
-#define H78(expr)                                                                               \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail78(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct Alloc78 {
     Scratch S{};
     void *mem = nullptr;
@@ -687,7 +680,7 @@ int setup(Alloc78 &A, Cache78 &C, uint32_t B, uint32_t nb) {
         if (C.mem) (void)hipFree(C.mem);
         C.mem = nullptr;
         C.bytes = 0;
-        H78(hipMalloc(&C.mem, tot));
+        FCX_HIP(hipMalloc(&C.mem, tot));
         C.bytes = tot;
     }
     A.mem = C.mem;
@@ -730,9 +723,9 @@ extern "C" {
 
 int fcx_lz78_compress_shard(const uint8_t *d_in, uint64_t n, uint32_t block_bytes, uint8_t *d_out, uint64_t cap,
                             uint64_t *out_len, void *stream) {
-    if (!d_out || !out_len || (n && !d_in)) return fail78(FCX_ERR_ARG, "fcx_lz78_compress_shard: NULL argument");
+    if (!d_out || !out_len || (n && !d_in)) return fail(FCX_ERR_ARG, "fcx_lz78_compress_shard: NULL argument");
     if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail78(FCX_ERR_ARG, "fcx_lz78_compress_shard: block_bytes must be in [1, 1 MiB]");
+        return fail(FCX_ERR_ARG, "fcx_lz78_compress_shard: block_bytes must be in [1, 1 MiB]");
     *out_len = 0;
     if (n == 0) return FCX_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -748,29 +741,25 @@ int fcx_lz78_compress_shard(const uint8_t *d_in, uint64_t n, uint32_t block_byte
     const uint32_t batch = (uint32_t)std::max<uint64_t>(
         1, std::min<uint64_t>(std::min<uint64_t>(nblk, kBatchBytes / block_bytes), by_budget));
     Cache78 *C = cache_for_current_device();
-    if (!C) return fail78(FCX_ERR_HIP, "fcx_lz78_compress_shard: no current HIP device");
+    if (!C) return fail(FCX_ERR_HIP, "fcx_lz78_compress_shard: no current HIP device");
     std::lock_guard<std::mutex> lock(C->mu);
     Alloc78 A;
     if (int rc = setup(A, *C, block_bytes, batch)) return rc;
     Scratch S = A.S;
-    uint32_t *d_err = nullptr;
-    H78(hipMalloc(&d_err, 4));
-    struct ErrFree {
-        uint32_t *p;
-        ~ErrFree() { (void)hipFree(p); }
-    } ef{d_err};
-    H78(hipMemsetAsync(d_err, 0, 4, st));
-    H78(hipMemsetAsync(S.total, 0, 8, st));
+    DevBuf<uint32_t> d_err;
+    FCX_HIP(d_err.alloc(4));
+    FCX_HIP(hipMemsetAsync(d_err, 0, 4, st));
+    FCX_HIP(hipMemsetAsync(S.total, 0, 8, st));
     for (uint64_t b0 = 0; b0 < nblk; b0 += batch) {
         S.nb = (uint32_t)std::min<uint64_t>(batch, nblk - b0);
         const uint32_t nb = S.nb;
-        H78(hipMemsetAsync(S.slot, 0, ((uint64_t)nb << S.cap_log2) * 8, st));
-        if (S.dense1) H78(hipMemsetAsync(S.d1, 0, ((uint64_t)nb << 16) * 4, st));
-        H78(hipMemsetAsync(S.bm, 0, (uint64_t)nb * S.bmw * 4, st));
-        H78(hipMemsetAsync(S.gcnt, 0, (uint64_t)nb * S.Gmax * 4, st));
-        H78(hipMemsetAsync(S.chist, 0, (uint64_t)nb * 256 * 4, st));
-        H78(hipMemsetAsync(S.gstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
-        H78(hipMemsetAsync(S.cstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
+        FCX_HIP(hipMemsetAsync(S.slot, 0, ((uint64_t)nb << S.cap_log2) * 8, st));
+        if (S.dense1) FCX_HIP(hipMemsetAsync(S.d1, 0, ((uint64_t)nb << 16) * 4, st));
+        FCX_HIP(hipMemsetAsync(S.bm, 0, (uint64_t)nb * S.bmw * 4, st));
+        FCX_HIP(hipMemsetAsync(S.gcnt, 0, (uint64_t)nb * S.Gmax * 4, st));
+        FCX_HIP(hipMemsetAsync(S.chist, 0, (uint64_t)nb * 256 * 4, st));
+        FCX_HIP(hipMemsetAsync(S.gstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
+        FCX_HIP(hipMemsetAsync(S.cstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
         const dim3 tok_grid(S.tiles, nb);
         if (S.dense1) k78_parse<true><<<nb, 64, 0, st>>>(d_in, n, S, b0);
         else k78_parse<false><<<nb, 64, 0, st>>>(d_in, n, S, b0);
@@ -783,24 +772,24 @@ int fcx_lz78_compress_shard(const uint8_t *d_in, uint64_t n, uint32_t block_byte
         k78_tilescan<<<(nb + 63) / 64, 64, 0, st>>>(S);
         k78_pack<<<tok_grid, 256, 0, st>>>(S);
         k78_write<<<dim3(64, nb), 256, 0, st>>>(S, d_out, d_err);
-        H78(hipGetLastError());
+        FCX_HIP(hipGetLastError());
     }
     uint32_t herr = 0;
     uint64_t total = 0;
-    H78(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, st));
-    H78(hipMemcpyAsync(&total, S.total, 8, hipMemcpyDeviceToHost, st));
-    H78(hipStreamSynchronize(st));
-    if (herr & 2) return fail78(FCX_ERR_CAPACITY, "fcx_lz78_compress_shard: output capacity exceeded");
-    if (herr & 1) return fail78(FCX_ERR_INTERNAL, "fcx_lz78_compress_shard: Huffman code longer than 32 bits");
+    FCX_HIP(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipMemcpyAsync(&total, S.total, 8, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    if (herr & kErr78Capacity) return fail(FCX_ERR_CAPACITY, "fcx_lz78_compress_shard: output capacity exceeded");
+    if (herr & kErr78CodeLen) return fail(FCX_ERR_INTERNAL, "fcx_lz78_compress_shard: Huffman code longer than 32 bits");
     *out_len = total;
     return FCX_OK;
 }
 
 int fcx_lz78_release(void) {
     Cache78 *C = cache_for_current_device();
-    if (!C) return fail78(FCX_ERR_HIP, "fcx_lz78_release: no current HIP device");
+    if (!C) return fail(FCX_ERR_HIP, "fcx_lz78_release: no current HIP device");
     std::lock_guard<std::mutex> lock(C->mu);
-    if (C->mem) H78(hipFree(C->mem));
+    if (C->mem) FCX_HIP(hipFree(C->mem));
     C->mem = nullptr;
     C->bytes = 0;
     return FCX_OK;
@@ -808,10 +797,10 @@ int fcx_lz78_release(void) {
 
 int fcx_lz78_compress_host(const uint8_t *in, uint64_t n, uint32_t block_bytes, uint8_t *out, uint64_t cap,
                            uint64_t *out_len) {
-    if (!in || !out || !out_len) return fail78(FCX_ERR_ARG, "fcx_lz78_compress_host: NULL argument");
-    if (cap < FCX_HEADER_BYTES) return fail78(FCX_ERR_CAPACITY, "fcx_lz78_compress_host: capacity below the header");
+    if (!in || !out || !out_len) return fail(FCX_ERR_ARG, "fcx_lz78_compress_host: NULL argument");
+    if (cap < FCX_HEADER_BYTES) return fail(FCX_ERR_CAPACITY, "fcx_lz78_compress_host: capacity below the header");
     if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail78(FCX_ERR_ARG, "fcx_lz78_compress_host: block_bytes must be in [1, 1 MiB]");
+        return fail(FCX_ERR_ARG, "fcx_lz78_compress_host: block_bytes must be in [1, 1 MiB]");
     const uint64_t nblk = (n + block_bytes - 1) / block_bytes;
     memcpy(out, "FCX8", 4);   // stCmpFileHead (101-109) with the lz78 tag (4079-4086)
     const uint32_t tot32 = (uint32_t)n;
@@ -820,43 +809,29 @@ int fcx_lz78_compress_host(const uint8_t *in, uint64_t n, uint32_t block_bytes, 
     memcpy(out + 8, &nb16, 2);
     *out_len = FCX_HEADER_BYTES;
     if (n == 0) return FCX_OK;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    H78(hipMalloc(&d_in, n));
-    struct F {
-        uint8_t **a, **b;
-        ~F() {
-            if (*a) (void)hipFree(*a);
-            if (*b) (void)hipFree(*b);
-        }
-    } f{&d_in, &d_out};
+    DevBuf<uint8_t> d_in, d_out;
+    FCX_HIP(d_in.alloc(n));
     const uint64_t dcap = cap - FCX_HEADER_BYTES;
-    H78(hipMalloc(&d_out, dcap ? dcap : 16));
-    H78(hipMemcpy(d_in, in, n, hipMemcpyHostToDevice));
+    FCX_HIP(d_out.alloc(dcap));
+    FCX_HIP(hipMemcpy(d_in, in, n, hipMemcpyHostToDevice));
     uint64_t len = 0;
     if (int rc = fcx_lz78_compress_shard(d_in, n, block_bytes, d_out, dcap, &len, nullptr)) return rc;
-    H78(hipMemcpy(out + FCX_HEADER_BYTES, d_out, len, hipMemcpyDeviceToHost));
+    FCX_HIP(hipMemcpy(out + FCX_HEADER_BYTES, d_out, len, hipMemcpyDeviceToHost));
     *out_len = FCX_HEADER_BYTES + len;
     return FCX_OK;
 }
 
 uint32_t fcx_lz78_compress_block(const void *in, uint32_t len, uint8_t *out) {
     if (!in || !out || len == 0 || len > FCX_MAX_BLOCK_BYTES) return 0;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
+    DevBuf<uint8_t> d_in, d_out;
     const uint64_t cap = 10ull * len + 4096;
-    if (hipMalloc(&d_in, len) != hipSuccess) return 0;
-    if (hipMalloc(&d_out, cap) != hipSuccess) {
-        (void)hipFree(d_in);
-        return 0;
-    }
     uint64_t got = 0;
-    uint32_t ret = 0;
-    if (hipMemcpy(d_in, in, len, hipMemcpyHostToDevice) == hipSuccess &&
+    if (d_in.alloc(len) == hipSuccess && d_out.alloc(cap) == hipSuccess &&
+        hipMemcpy(d_in, in, len, hipMemcpyHostToDevice) == hipSuccess &&
         fcx_lz78_compress_shard(d_in, len, len, d_out, cap, &got, nullptr) == FCX_OK && got >= 4 &&
         hipMemcpy(out, d_out + 4, got - 4, hipMemcpyDeviceToHost) == hipSuccess)
-        ret = (uint32_t)(got - 4);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return ret;
+        return (uint32_t)(got - 4);
+    return 0;
 }
 
 }  // extern "C"

@@ -39,10 +39,6 @@
 #include "fcx.h"
 #include "fcx_dec_shared.h"
 
-namespace fcx {
-void set_last_error(const std::string &m);
-}
-
 namespace fcx78d {
 using namespace fcx;
 
@@ -66,10 +62,16 @@ struct DRec {
     uint32_t out_len, ok, pad;
 };
 
-// words (u64): [0] running output bytes, [1] error bits, [2] token slots of the batch, [3] pindex
-// entries of the batch, [4] first bad record (1-based, u32), [5] first bad char stream of the batch
-// (u32), [8..] segment decoder statistics
+// ---- status words of an FCX8 decode (Scratch78's words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kW8Total = 0;       // running output bytes (k78d_scan_out)
+constexpr uint32_t kW8Err = 1;         // error bits (kDErr*), a u32
+constexpr uint32_t kW8Tokens = 2;      // token slots of the batch (k78d_scan): they size the scratch, as do ...
+constexpr uint32_t kW8Pindex = 3;      // ... its pindex entries
+constexpr uint32_t kW8BadRec = 4;      // first bad record (1-based, u32; kNone: none)
+constexpr uint32_t kW8BadStream = 5;   // first bad char stream of the batch (u32; kNone: none)
+constexpr uint32_t kW8Stats = 8;       // the segment decoder's statistics block (kSs*, fcx_dec_shared.h)
 constexpr uint32_t kWords = 32;
+static_assert(kW8BadStream == kW8BadRec + 1 && kW8Stats + kSsWords <= kWords, "FCX8 status words");
 
 // the error word as one value for the whole workgroup (lanes that read it apart could part at a barrier)
 __device__ inline bool wg_err(const uint32_t *err) { return __syncthreads_or(threadIdx.x == 0 && *err != 0); }
@@ -238,8 +240,8 @@ __global__ __launch_bounds__(kBatch) void k78d_scan(uint32_t nb, DRec *rec, DStr
         ds[b] = s;
     }
     if (b == 0) {
-        words[2] = tt;
-        words[3] = tp;
+        words[kW8Tokens] = tt;
+        words[kW8Pindex] = tp;
     }
 }
 
@@ -448,13 +450,13 @@ __global__ __launch_bounds__(kBatch) void k78d_scan_out(uint32_t nb, DRec *rec, 
     off[b] = b < nb ? rec[b].out_len : 0;
     __syncthreads();
     if (b == 0) {
-        uint64_t o = words[0];
+        uint64_t o = words[kW8Total];
         for (uint32_t i = 0; i < nb; i++) {
             const uint64_t l = off[i];
             off[i] = o;
             o += l;
         }
-        words[0] = o;
+        words[kW8Total] = o;
         if (o > cap) atomicOr(err, kDErrOutCap);
     }
     __syncthreads();
@@ -519,107 +521,77 @@ __global__ __launch_bounds__(256) void k78d_expand_long(const DRec *rec, const u
     }
 }
 
+}  // namespace fcx78d
+
 // ---------------------------------------------------------------------------
+namespace fcx {
+using namespace fcx78d;
+
 struct Scratch78 {
-    uint64_t *roff = nullptr;
-    uint32_t *rlen = nullptr;
-    uint64_t rec_cap = 0;           // records roff / rlen hold
-    DRec *rec = nullptr;            // kBatch
-    DStream *ds = nullptr;          // kBatch
-    uint16_t *ctbl = nullptr, *cchild = nullptr;   // char tables, kBatch x (1024, 512)
-    uint32_t *gtbl = nullptr;       // kBatch x 1024
-    uint16_t *gchild = nullptr;     // kBatch x 2 kGmax
-    uint64_t *words = nullptr, *host_words = nullptr;
-    uint64_t tok_cap = 0, pix_cap = 0;
-    uint8_t *chr = nullptr;         // per token slot: 1 B
-    uint16_t *grp = nullptr;        //                 2 B
-    uint32_t *par = nullptr, *pstart = nullptr, *skip = nullptr;   // 3 x 4 B (pstart: + 1 per record)
-    uint32_t *pindex = nullptr;     // per used index: 4 B
+    DevBuf<uint64_t> roff;          // per record of the call
+    DevBuf<uint32_t> rlen;
+    DevBuf<DRec> rec;               // kBatch
+    DevBuf<DStream> ds;             // kBatch
+    DevBuf<uint16_t> ctbl, cchild;  // char tables, kBatch x (1024, 512)
+    DevBuf<uint32_t> gtbl;          // kBatch x 1024
+    DevBuf<uint16_t> gchild;        // kBatch x 2 kGmax
+    DevBuf<uint64_t> words;         // the status words (kW8*)
+    PinnedBuf<uint64_t> host_words; // (made last: set = the fixed-size parts above are)
+    DevBuf<uint8_t> chr;            // per token slot of the largest batch so far: 1 B
+    DevBuf<uint16_t> grp;           //                 2 B
+    DevBuf<uint32_t> par, pstart, skip;   // 3 x 4 B (pstart: + 1 per record)
+    DevBuf<uint32_t> pindex;        // per used index of the largest batch so far: 4 B
 };
+void free_scratch78(Scratch78 *s) { delete s; }
 
-void free78(void *v) {
-    Scratch78 *s = (Scratch78 *)v;
-    void *ptrs[] = {s->roff, s->rlen, s->rec, s->ds, s->ctbl, s->cchild, s->gtbl, s->gchild, s->words,
-                    s->chr, s->grp, s->par, s->pstart, s->skip, s->pindex};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (s->host_words) (void)hipHostFree(s->host_words);
-    delete s;
-}
+static const char *kD78StageNames[] = {"header", "index", "tables", "symbols", "links", "expand"};
+static_assert(sizeof(kD78StageNames) / sizeof(kD78StageNames[0]) == kD78Stages, "FCX8 stage names");
 
-int fail(int code, const std::string &m) {
-    set_last_error(m);
-    return code;
-}
-#define H78D(expr)                                                                                   \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return fail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
+// n elements and the slack the kernels' wide loads may touch
 template <typename T>
-int grow(T **p, uint64_t n, const char *what) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T) + 64);
-    if (e != hipSuccess) return fail(FCX_ERR_NOMEM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
-    return FCX_OK;
-}
+static int grow(DevBuf<T> &b, uint64_t n, const char *what) { return b.reserve(n * sizeof(T) + 64, what); }
 
-int verdict(const Scratch78 *S, uint64_t rec_base, uint32_t batch0) {
-    const uint32_t e = (uint32_t)S->host_words[1];
+static int verdict(const Scratch78 *S, uint64_t rec_base, uint32_t batch0) {
+    const uint32_t e = (uint32_t)S->host_words[kW8Err];
     if (!e) return FCX_OK;
     if (e & ~kDErrOutCap) {
-        uint64_t k = (uint32_t)S->host_words[4];
-        const uint32_t q = (uint32_t)S->host_words[5];   // a char tree: its stream's place in the batch
+        uint64_t k = (uint32_t)S->host_words[kW8BadRec];
+        const uint32_t q = (uint32_t)S->host_words[kW8BadStream];   // a char tree: its stream's place in the batch
         if (q != kNone) k = std::min<uint64_t>(k, (uint64_t)batch0 + q + 1);
         return fail(FCX_ERR_FORMAT, "fcx_lz78: malformed record " + std::to_string(rec_base + k));
     }
     return fail(FCX_ERR_CAPACITY, "fcx_lz78: decoded output exceeds capacity");
 }
 
-}  // namespace fcx78d
-
-using namespace fcx78d;
-
-namespace fcx {
-// fcx_lz78_decompress_shard for records rec_base + 1.. of a longer run (the stream path's groups):
-// the record numbers of its messages count from rec_base
 int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
                              uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base) {
-    H78D(hipSetDevice(c->device));
-    c->timed = false;
-    c->timed78 = false;
+    FCX_HIP(hipSetDevice(c->device));
+    StageTimes &T = c->times;
+    T.reset();
     *out_len = 0;
     if (nblocks == 0) return FCX_OK;
-    Scratch78 *S = (Scratch78 *)c->lz78;
-    if (!S) {
-        S = new Scratch78();
-        c->lz78 = S;
-        c->lz78_free = free78;
-        int r;
-        if ((r = grow(&S->rec, kBatch, "records"))) return r;
-        if ((r = grow(&S->ds, kBatch, "streams"))) return r;
-        if ((r = grow(&S->ctbl, 1024ull * kBatch, "char tables"))) return r;
-        if ((r = grow(&S->cchild, 512ull * kBatch, "char trees"))) return r;
-        if ((r = grow(&S->gtbl, 1024ull * kBatch, "group tables"))) return r;
-        if ((r = grow(&S->gchild, 2ull * kGmax * kBatch, "group trees"))) return r;
-        if ((r = grow(&S->words, kWords, "words"))) return r;
-        H78D(hipHostMalloc((void **)&S->host_words, 8 * kWords, hipHostMallocDefault));
+    if (!c->d78) c->d78.reset(new Scratch78());
+    Scratch78 *S = c->d78.get();
+    if (!S->host_words) {
+        FCX_TRY(grow(S->rec, kBatch, "records"));
+        FCX_TRY(grow(S->ds, kBatch, "streams"));
+        FCX_TRY(grow(S->ctbl, 1024ull * kBatch, "char tables"));
+        FCX_TRY(grow(S->cchild, 512ull * kBatch, "char trees"));
+        FCX_TRY(grow(S->gtbl, 1024ull * kBatch, "group tables"));
+        FCX_TRY(grow(S->gchild, 2ull * kGmax * kBatch, "group trees"));
+        FCX_TRY(grow(S->words, kWords, "words"));
+        FCX_HIP(S->host_words.alloc(8 * kWords));
     }
-    int r;
-    if (nblocks > S->rec_cap) {
-        S->rec_cap = 0;
-        if ((r = grow(&S->roff, nblocks, "record offsets"))) return r;
-        if ((r = grow(&S->rlen, nblocks, "record lengths"))) return r;
-        S->rec_cap = nblocks;
-    }
-    uint32_t *err = (uint32_t *)(S->words + 1), *badrec = (uint32_t *)(S->words + 4), *badq = (uint32_t *)(S->words + 5);
-    H78D(hipMemsetAsync(S->words, 0, 8 * kWords, st));
-    H78D(hipMemsetAsync(S->words + 4, 0xFF, 16, st));
+    FCX_TRY(grow(S->roff, nblocks, "record offsets"));
+    FCX_TRY(grow(S->rlen, nblocks, "record lengths"));
+    const uint64_t *hw = S->host_words;
+    uint32_t *err = (uint32_t *)(S->words + kW8Err), *badrec = (uint32_t *)(S->words + kW8BadRec),
+             *badq = (uint32_t *)(S->words + kW8BadStream);
+    uint64_t *stats = S->words + kW8Stats;
+    FCX_HIP(hipMemsetAsync(S->words, 0, 8 * kWords, st));
+    FCX_HIP(hipMemsetAsync(badrec, 0xFF, 16, st));   // (kW8BadRec and kW8BadStream: kNone)
     const bool prof = c->profiling;
-    float ms[kD78Stages] = {};
-    auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev78[i], st); };
+    auto mark = [&](int i) { if (prof) T.mark(i, st); };
     mark(0);
     hipLaunchKernelGGL(k78d_index, dim3(1), dim3(1), 0, st, d_in, in_len, nblocks, S->roff, S->rlen, err, badrec);
     for (uint32_t r0 = 0; r0 < nblocks; r0 += kBatch) {
@@ -629,39 +601,27 @@ int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, 
         hipLaunchKernelGGL(k78d_scan, dim3(1), dim3(kBatch), 0, st, nb, S->rec, S->ds, nds, S->words);
         mark(1);
         // the batch's token and index counts size the scratch; the error bits of the batch before
-        H78D(hipMemcpyAsync(S->host_words, S->words, 8 * kWords, hipMemcpyDeviceToHost, st));
-        H78D(hipStreamSynchronize(st));
-        if ((r = verdict(S, rec_base, r0 ? r0 - kBatch : 0))) return r;
-        if (prof) {
-            float v = 0;
-            H78D(hipEventElapsedTime(&v, c->ev78[0], c->ev78[1]));
-            ms[0] += v;
-        }
-        const uint64_t ntok = S->host_words[2], npix = S->host_words[3];
-        if (ntok > S->tok_cap) {
-            S->tok_cap = 0;
-            if ((r = grow(&S->chr, ntok, "chars"))) return r;
-            if ((r = grow(&S->grp, ntok, "groups"))) return r;
-            if ((r = grow(&S->par, ntok, "parents"))) return r;
-            if ((r = grow(&S->pstart, ntok + kBatch, "phrase starts"))) return r;
-            if ((r = grow(&S->skip, ntok, "skips"))) return r;
-            S->tok_cap = ntok;
-        }
-        if (npix > S->pix_cap) {
-            S->pix_cap = 0;
-            if ((r = grow(&S->pindex, npix, "index table"))) return r;
-            S->pix_cap = npix;
-        }
-        if (r0) H78D(hipMemsetAsync(S->words + 5, 0xFF, 8, st));   // (the batch before had no bad char tree)
+        FCX_HIP(hipMemcpyAsync(S->host_words, S->words, 8 * kWords, hipMemcpyDeviceToHost, st));
+        FCX_HIP(hipStreamSynchronize(st));
+        FCX_TRY(verdict(S, rec_base, r0 ? r0 - kBatch : 0));
+        if (prof) FCX_TRY(T.add(0, 1));
+        const uint64_t ntok = hw[kW8Tokens], npix = hw[kW8Pindex];
+        FCX_TRY(grow(S->chr, ntok, "chars"));
+        FCX_TRY(grow(S->grp, ntok, "groups"));
+        FCX_TRY(grow(S->par, ntok, "parents"));
+        FCX_TRY(grow(S->pstart, ntok + kBatch, "phrase starts"));
+        FCX_TRY(grow(S->skip, ntok, "skips"));
+        FCX_TRY(grow(S->pindex, npix, "index table"));
+        if (r0) FCX_HIP(hipMemsetAsync(badq, 0xFF, 8, st));   // (the batch before had no bad char tree)
         mark(1);
         hipLaunchKernelGGL(k78d_pindex, dim3(nb), dim3(1024), 0, st, d_in, S->rec, S->pindex, err);
         mark(2);
         hipLaunchKernelGGL(k78d_gtable, dim3(nb), dim3(256), 0, st, d_in, S->rec, r0, S->gtbl, S->gchild, err, badrec);
         dec_launch_tables8(d_in, nds, S->ds, S->ctbl, S->cchild, err, badq, st);
         mark(3);
-        dec_launch_syms8(d_in, in_len, nds, S->ds, S->ctbl, S->cchild, S->chr, err, S->words + 8, st);
+        dec_launch_syms8(d_in, in_len, nds, S->ds, S->ctbl, S->cchild, S->chr, err, stats, st);
         hipLaunchKernelGGL(k78d_groups, dim3(nb), dim3(kDSymThreads), 0, st, d_in, in_len, S->rec, S->gtbl, S->gchild,
-                           S->grp, err, S->words + 8);
+                           S->grp, err, stats);
         mark(4);
         hipLaunchKernelGGL(k78d_links, dim3(nb), dim3(1024), 0, st, d_in, S->rec, r0, S->pindex, S->grp, S->chr, S->par,
                            S->pstart, err, badrec);
@@ -671,62 +631,39 @@ int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, 
                            err);
         hipLaunchKernelGGL(k78d_expand_long, dim3(8, nb), dim3(256), 0, st, S->rec, S->pstart, S->skip, d_out, err);
         mark(6);
-        H78D(hipGetLastError());
-        if (prof) {
-            H78D(hipEventSynchronize(c->ev78[6]));
-            for (int i = 1; i < kD78Stages; i++) {
-                float v = 0;
-                H78D(hipEventElapsedTime(&v, c->ev78[i], c->ev78[i + 1]));
-                ms[i] += v;
-            }
-        }
+        FCX_HIP(hipGetLastError());
+        if (prof) FCX_TRY(T.add(1, kD78Stages));
     }
-    H78D(hipMemcpyAsync(S->host_words, S->words, 8 * kWords, hipMemcpyDeviceToHost, st));
-    H78D(hipStreamSynchronize(st));
-    if ((r = verdict(S, rec_base, (nblocks - 1) / kBatch * kBatch))) return r;
-    if (prof) {
-        memcpy(c->ms78, ms, sizeof(ms));
-        c->timed78 = true;
-    }
-    *out_len = S->host_words[0];
+    FCX_HIP(hipMemcpyAsync(S->host_words, S->words, 8 * kWords, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    FCX_TRY(verdict(S, rec_base, (nblocks - 1) / kBatch * kBatch));
+    if (prof) T.publish(kD78StageNames, kD78Stages);
+    *out_len = hw[kW8Total];
     return FCX_OK;
 }
 }  // namespace fcx
 
+using namespace fcx;
+
 namespace {
 // fcx_lz78_decompress_block / _host: a decoder context per host thread on the current device
-thread_local fcx_dctx *g_dctx = nullptr;
-struct DctxFree {
-    ~DctxFree() {
-        if (g_dctx) fcx_dctx_destroy(g_dctx);
-        g_dctx = nullptr;
-    }
-};
-thread_local DctxFree g_dctx_free;
+thread_local std::unique_ptr<fcx_dctx, Calls<fcx_dctx_destroy>> g_dctx;
 
 int thread_dctx(fcx_dctx **out) {
-    (void)&g_dctx_free;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fail(FCX_ERR_HIP, "no HIP device: the GPU decoder needs one");
     if (g_dctx && g_dctx->device != dev) {
-        fcx_dctx_destroy(g_dctx);
-        g_dctx = nullptr;
+        g_dctx.reset();
         (void)hipSetDevice(dev);
     }
     if (!g_dctx) {
-        const int r = fcx_dctx_create(&g_dctx, dev);
-        if (r) return r;
+        fcx_dctx *c = nullptr;
+        FCX_TRY(fcx_dctx_create(&c, dev));
+        g_dctx.reset(c);
     }
-    *out = g_dctx;
+    *out = g_dctx.get();
     return FCX_OK;
 }
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
 }  // namespace
 
 extern "C" {
@@ -736,23 +673,22 @@ uint32_t fcx_lz78_decode_batch_records(void) { return kBatch; }
 int fcx_lz78_decompress_shard(fcx_dctx *ctx, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
                               uint64_t cap, uint64_t *out_len, void *stream) {
     if (!ctx || !d_in || !d_out || !out_len) return fail(FCX_ERR_ARG, "fcx_lz78_decompress_shard: NULL argument");
-    return fcx::lz78_decompress_shard_at(ctx, d_in, in_len, nblocks, d_out, cap, out_len, (hipStream_t)stream, 0);
+    return lz78_decompress_shard_at(ctx, d_in, in_len, nblocks, d_out, cap, out_len, (hipStream_t)stream, 0);
 }
 
 int64_t fcx_lz78_decompress_block(const uint8_t *in, uint32_t len, uint8_t *out, uint64_t cap) {
     if (!in || !out) return fail(FCX_ERR_ARG, "fcx_lz78_decompress_block: NULL argument");
     fcx_dctx *c = nullptr;
-    if (int r = thread_dctx(&c)) return r;
+    FCX_TRY(thread_dctx(&c));
     const uint64_t dcap = std::min<uint64_t>(cap, kCapBlock);
-    DevBuf din, dout;
-    H78D(hipMalloc(&din.p, 4ull + len));
-    H78D(hipMalloc(&dout.p, dcap + 16));
-    H78D(hipMemcpy(din.p, &len, 4, hipMemcpyHostToDevice));
-    H78D(hipMemcpy((uint8_t *)din.p + 4, in, len, hipMemcpyHostToDevice));
+    DevBuf<uint8_t> din, dout;
+    FCX_HIP(din.alloc(4ull + len));
+    FCX_HIP(dout.alloc(dcap + 16));
+    FCX_HIP(hipMemcpy(din, &len, 4, hipMemcpyHostToDevice));
+    FCX_HIP(hipMemcpy(din + 4, in, len, hipMemcpyHostToDevice));
     uint64_t n = 0;
-    if (int r = fcx_lz78_decompress_shard(c, (const uint8_t *)din.p, 4ull + len, 1, (uint8_t *)dout.p, dcap, &n, nullptr))
-        return r;
-    H78D(hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
+    FCX_TRY(fcx_lz78_decompress_shard(c, din, 4ull + len, 1, dout, dcap, &n, nullptr));
+    FCX_HIP(hipMemcpy(out, dout, n, hipMemcpyDeviceToHost));
     return (int64_t)n;
 }
 
@@ -779,9 +715,10 @@ int fcx_lz78_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, u
     // on the size, like the reference.
     if (nblk == 0) return FCX_OK;
     fcx_dctx *c = nullptr;
-    if (int r = thread_dctx(&c)) return r;
+    FCX_TRY(thread_dctx(&c));
     uint8_t scratch = 0;
     return fcx_decompress_host(c, in, q, cap ? out : &scratch, cap, out_len);
 }
 
 }  // extern "C"
+

@@ -15,30 +15,18 @@
 #include <vector>
 
 #include "fcx.h"
+#include "fcx_dec_shared.h"   // lz78_decompress_shard_at
+#include "fcx_device.h"       // the compress status words a slot's hlen mirrors
+#include "fcx_host.h"
 
-namespace fcx {
-void set_last_error(const std::string &m);
-// fcx_lz78_decompress_shard whose messages number the records from rec_base (fcx_lz78_dec.hip)
-int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
-                             uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
-}
+using namespace fcx;
 
 namespace {
 
-int sfail(int code, const std::string &m) {
-    fcx::set_last_error(m);
-    return code;
-}
-
-#define SHIP(expr)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return sfail(FCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct Slot {
-    uint8_t *hin = nullptr, *hout = nullptr, *din = nullptr, *dout = nullptr;
-    uint64_t *hlen = nullptr;   // pinned copy of the device length / error words
+    PinnedBuf<uint8_t> hin, hout;
+    DevBuf<uint8_t> din, dout;
+    PinnedBuf<uint64_t> hlen;   // pinned copy of the device length / error words ([kCwTotal, kCwErr])
     uint64_t n = 0;             // input bytes in this slot
     hipEvent_t h2d = nullptr, comp = nullptr, d2h = nullptr;
 };
@@ -49,15 +37,9 @@ struct Pipeline {
     int device = -1;
     uint64_t in_bytes = 0, out_bytes = 0;
     ~Pipeline() {
-        for (auto &x : s) {
-            if (x.hin) (void)hipHostFree(x.hin);
-            if (x.hout) (void)hipHostFree(x.hout);
-            if (x.hlen) (void)hipHostFree(x.hlen);
-            if (x.din) (void)hipFree(x.din);
-            if (x.dout) (void)hipFree(x.dout);
+        for (auto &x : s)
             for (hipEvent_t e : {x.h2d, x.comp, x.d2h})
                 if (e) (void)hipEventDestroy(e);
-        }
         for (hipStream_t q : {sin, scomp, sout})
             if (q) (void)hipStreamDestroy(q);
     }
@@ -65,21 +47,21 @@ struct Pipeline {
         device = dev;
         in_bytes = in_b;
         out_bytes = out_b;
-        SHIP(hipStreamCreateWithFlags(&sin, hipStreamNonBlocking));
-        SHIP(hipStreamCreateWithFlags(&scomp, hipStreamNonBlocking));
-        SHIP(hipStreamCreateWithFlags(&sout, hipStreamNonBlocking));
+        FCX_HIP(hipStreamCreateWithFlags(&sin, hipStreamNonBlocking));
+        FCX_HIP(hipStreamCreateWithFlags(&scomp, hipStreamNonBlocking));
+        FCX_HIP(hipStreamCreateWithFlags(&sout, hipStreamNonBlocking));
         for (auto &x : s) {
-            SHIP(hipHostMalloc((void **)&x.hin, in_bytes ? in_bytes : 16, hipHostMallocDefault));
-            SHIP(hipHostMalloc((void **)&x.hout, out_bytes ? out_bytes : 16, hipHostMallocDefault));
-            SHIP(hipHostMalloc((void **)&x.hlen, 16, hipHostMallocDefault));
-            SHIP(hipMalloc((void **)&x.din, in_bytes ? in_bytes : 16));
-            SHIP(hipMalloc((void **)&x.dout, out_bytes ? out_bytes : 16));
-            SHIP(hipEventCreateWithFlags(&x.h2d, hipEventDisableTiming));
-            SHIP(hipEventCreateWithFlags(&x.comp, hipEventDisableTiming));
-            SHIP(hipEventCreateWithFlags(&x.d2h, hipEventDisableTiming));
-            SHIP(hipEventRecord(x.comp, scomp));   // slots start free
-            SHIP(hipEventRecord(x.d2h, sout));
-            SHIP(hipEventRecord(x.h2d, sin));
+            FCX_HIP(x.hin.alloc(in_bytes));
+            FCX_HIP(x.hout.alloc(out_bytes));
+            FCX_HIP(x.hlen.alloc(kCwHeadBytes));
+            FCX_HIP(x.din.alloc(in_bytes));
+            FCX_HIP(x.dout.alloc(out_bytes));
+            FCX_HIP(hipEventCreateWithFlags(&x.h2d, hipEventDisableTiming));
+            FCX_HIP(hipEventCreateWithFlags(&x.comp, hipEventDisableTiming));
+            FCX_HIP(hipEventCreateWithFlags(&x.d2h, hipEventDisableTiming));
+            FCX_HIP(hipEventRecord(x.comp, scomp));   // slots start free
+            FCX_HIP(hipEventRecord(x.d2h, sout));
+            FCX_HIP(hipEventRecord(x.h2d, sin));
         }
         return FCX_OK;
     }
@@ -87,27 +69,21 @@ struct Pipeline {
 
 // pinned/device slots are kept per host thread (one set for each direction) and
 // reused while they are large enough: per-block calls do not re-pin memory
-thread_local Pipeline *g_pipe[2] = {nullptr, nullptr};
-struct PipeFree {
-    ~PipeFree() { for (auto &p : g_pipe) { delete p; p = nullptr; } }
-};
-thread_local PipeFree g_pipe_free;
+thread_local std::unique_ptr<Pipeline> g_pipe[2];
 
 int get_pipe(int which, int dev, uint64_t in_b, uint64_t out_b, Pipeline **out) {
-    (void)&g_pipe_free;
-    Pipeline *&p = g_pipe[which];
+    std::unique_ptr<Pipeline> &p = g_pipe[which];
     if (p && (p->device != dev || p->in_bytes < in_b || p->out_bytes < out_b)) {
         (void)hipDeviceSynchronize();
-        delete p;
-        p = nullptr;
+        p.reset();
     }
     if (!p) {
-        p = new Pipeline();
+        p.reset(new Pipeline());
         const int r = p->init(dev, in_b, out_b);
-        if (r) { delete p; p = nullptr; return r; }
+        if (r) { p.reset(); return r; }
     }
     for (auto &x : p->s) x.n = 0;
-    *out = p;
+    *out = p.get();
     return FCX_OK;
 }
 
@@ -169,11 +145,11 @@ extern "C" {
 
 int fcx_compress_stream(fcx_ctx *ctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t shard_bytes,
                         uint64_t *total_in, uint64_t *total_out, uint64_t *nblocks) {
-    if (!ctx || !rd || !wr) return sfail(FCX_ERR_ARG, "fcx_compress_stream: NULL argument");
+    if (!ctx || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_compress_stream: NULL argument");
     uint32_t B = 0;
     int dev = 0;
     if (fcx_ctx_info(ctx, &dev, &B, nullptr)) return FCX_ERR_ARG;
-    SHIP(hipSetDevice(dev));
+    FCX_HIP(hipSetDevice(dev));
     const uint64_t shard = shard_bytes >= B ? shard_bytes / B * B : B;
     const uint64_t cap = fcx_shard_bound(shard, B);
     Pipeline *PP = nullptr;
@@ -187,19 +163,19 @@ int fcx_compress_stream(fcx_ctx *ctx, fcx_read_fn rd, fcx_write_fn wr, void *use
     // waited for and the records written (finish)
     uint64_t olen_pending = 0;
     auto drain_start = [&](Slot &x) -> int {
-        SHIP(hipEventSynchronize(x.comp));
-        const uint32_t e = (uint32_t)x.hlen[1];
-        if (e & 4u) return sfail(FCX_ERR_CAPACITY, "shard output capacity");
-        if (e) return sfail(FCX_ERR_INTERNAL, "device invariant violated (error bits " + std::to_string(e) + ")");
-        olen_pending = x.hlen[0];
-        SHIP(hipMemcpyAsync(x.hout, x.dout, olen_pending, hipMemcpyDeviceToHost, P.sout));
-        SHIP(hipEventRecord(x.d2h, P.sout));
+        FCX_HIP(hipEventSynchronize(x.comp));
+        const uint32_t e = (uint32_t)x.hlen[kCwErr];
+        if (e & kErrCapacity) return fail(FCX_ERR_CAPACITY, "shard output capacity");
+        if (e) return fail(FCX_ERR_INTERNAL, "device invariant violated (error bits " + std::to_string(e) + ")");
+        olen_pending = x.hlen[kCwTotal];
+        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, olen_pending, hipMemcpyDeviceToHost, P.sout));
+        FCX_HIP(hipEventRecord(x.d2h, P.sout));
         return FCX_OK;
     };
     auto drain_finish = [&](Slot &x) -> int {
-        SHIP(hipEventSynchronize(x.d2h));
+        FCX_HIP(hipEventSynchronize(x.d2h));
         const int w = wr(user, x.hout, olen_pending);
-        if (w) return sfail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
+        if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
         tout += olen_pending;
         x.n = 0;
         return FCX_OK;
@@ -209,20 +185,20 @@ int fcx_compress_stream(fcx_ctx *ctx, fcx_read_fn rd, fcx_write_fn wr, void *use
         return rr ? rr : drain_finish(x);
     };
     int64_t got = read_full(rd, user, P.s[0].hin, shard);
-    if (got < 0) return sfail(FCX_ERR_ARG, "read callback failed");
+    if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
     for (uint32_t k = 0; got > 0; k++) {
         Slot &x = P.s[k & 1], &y = P.s[(k + 1) & 1];
         x.n = (uint64_t)got;
         tin += x.n;
         tblocks += (x.n + B - 1) / B;
-        SHIP(hipStreamWaitEvent(P.sin, x.comp, 0));     // x.din free again (shard k-2 compressed)
-        SHIP(hipMemcpyAsync(x.din, x.hin, x.n, hipMemcpyHostToDevice, P.sin));
-        SHIP(hipEventRecord(x.h2d, P.sin));
-        SHIP(hipStreamWaitEvent(P.scomp, x.h2d, 0));
-        SHIP(hipStreamWaitEvent(P.scomp, x.d2h, 0));   // x.dout free again
+        FCX_HIP(hipStreamWaitEvent(P.sin, x.comp, 0));     // x.din free again (shard k-2 compressed)
+        FCX_HIP(hipMemcpyAsync(x.din, x.hin, x.n, hipMemcpyHostToDevice, P.sin));
+        FCX_HIP(hipEventRecord(x.h2d, P.sin));
+        FCX_HIP(hipStreamWaitEvent(P.scomp, x.h2d, 0));
+        FCX_HIP(hipStreamWaitEvent(P.scomp, x.d2h, 0));   // x.dout free again
         if ((r = fcx_compress_shard(ctx, x.din, x.n, x.dout, cap, nullptr, P.scomp))) return r;
-        SHIP(hipMemcpyAsync(x.hlen, dlen, 16, hipMemcpyDeviceToHost, P.scomp));
-        SHIP(hipEventRecord(x.comp, P.scomp));
+        FCX_HIP(hipMemcpyAsync(x.hlen, dlen, kCwHeadBytes, hipMemcpyDeviceToHost, P.scomp));
+        FCX_HIP(hipEventRecord(x.comp, P.scomp));
         // while the GPU works on slot x: read the next shard into y (its H2D is long done)
         // and write y's finished records
         const bool last = x.n < shard;
@@ -230,9 +206,9 @@ int fcx_compress_stream(fcx_ctx *ctx, fcx_read_fn rd, fcx_write_fn wr, void *use
         const bool ydrain = y.n != 0;
         if (ydrain) { if ((r = drain_start(y))) return r; }
         if (!last) {   // (y.hin: its H2D is long done; y's records go out through y.hout meanwhile)
-            SHIP(hipEventSynchronize(y.h2d));
+            FCX_HIP(hipEventSynchronize(y.h2d));
             got = read_full(rd, user, y.hin, shard);
-            if (got < 0) return sfail(FCX_ERR_ARG, "read callback failed");
+            if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
         }
         if (ydrain) { if ((r = drain_finish(y))) return r; }
     }
@@ -245,7 +221,7 @@ int fcx_compress_stream(fcx_ctx *ctx, fcx_read_fn rd, fcx_write_fn wr, void *use
 }
 
 int fcx_compress_host(fcx_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len) {
-    if (!ctx || (!in && n) || !out) return sfail(FCX_ERR_ARG, "fcx_compress_host: NULL argument");
+    if (!ctx || (!in && n) || !out) return fail(FCX_ERR_ARG, "fcx_compress_host: NULL argument");
     uint64_t shard = 0;
     if (fcx_ctx_info(ctx, nullptr, nullptr, &shard)) return FCX_ERR_ARG;
     MemIO m{in, n, 0, out, cap, 0};
@@ -257,9 +233,9 @@ int fcx_compress_host(fcx_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out,
 
 int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
                           uint32_t *hdr_total, uint64_t *total_out, uint64_t *nblocks) {
-    if (!dctx || !rd || !wr) return sfail(FCX_ERR_ARG, "fcx_decompress_stream: NULL argument");
+    if (!dctx || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_decompress_stream: NULL argument");
     uint8_t hdr[FCX_HEADER_BYTES];
-    if (read_full(rd, user, hdr, sizeof(hdr)) != (int64_t)sizeof(hdr)) return sfail(FCX_ERR_FORMAT, "short header");
+    if (read_full(rd, user, hdr, sizeof(hdr)) != (int64_t)sizeof(hdr)) return fail(FCX_ERR_FORMAT, "short header");
     uint32_t total = 0;
     uint16_t counted = 0;
     char kind = 0;
@@ -268,7 +244,7 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
     const bool lz78 = kind != '7';   // as main() (4140-4159): anything but '7' selects LZ78
     int dev = 0;
     if (fcx_dctx_device(dctx, &dev)) return FCX_ERR_ARG;
-    SHIP(hipSetDevice(dev));
+    FCX_HIP(hipSetDevice(dev));
     // groups of whole records: up to kGroup blocks (<= 1 MiB decoded each, + 8 for FCX8) per device
     // call (max_in, when known, bounds the staging: small inputs do not pin a whole group).  An FCX7
     // record is <= 2 len + 4096 bytes and a group's staging holds kGroup of them; an FCX8 record may
@@ -301,32 +277,32 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
             if (!have_len) {
                 const int64_t g = read_full(rd, user, (uint8_t *)&len, 4);
                 if (g == 0 && !lz78) { eof = true; break; }
-                if (g != 4) return sfail(FCX_ERR_FORMAT, "truncated block record");
-                if (len > len_max) return sfail(FCX_ERR_FORMAT, "block record too long");
+                if (g != 4) return fail(FCX_ERR_FORMAT, "truncated block record");
+                if (len > len_max) return fail(FCX_ERR_FORMAT, "block record too long");
             }
             have_len = false;
             if (used + 4 + (uint64_t)len > in_cap) {
-                if (!lz78 || nb == 0) return sfail(FCX_ERR_FORMAT, "truncated block record");
+                if (!lz78 || nb == 0) return fail(FCX_ERR_FORMAT, "truncated block record");
                 have_len = true;   // opens the next group
                 break;
             }
             memcpy(x.hin + used, &len, 4);
             if (read_full(rd, user, x.hin + used + 4, len) != (int64_t)len)
-                return sfail(FCX_ERR_FORMAT, "truncated block record");
+                return fail(FCX_ERR_FORMAT, "truncated block record");
             used += 4 + (uint64_t)len;
             nb++;
             left--;
         }
         if (nb == 0) break;
-        SHIP(hipMemcpyAsync(x.din, x.hin, used, hipMemcpyHostToDevice, P.scomp));
+        FCX_HIP(hipMemcpyAsync(x.din, x.hin, used, hipMemcpyHostToDevice, P.scomp));
         uint64_t got = 0;
         if (lz78) r = fcx::lz78_decompress_shard_at(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp, tblocks);
         else r = fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp);
         if (r) return r;
-        SHIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, P.scomp));
-        SHIP(hipStreamSynchronize(P.scomp));
+        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, P.scomp));
+        FCX_HIP(hipStreamSynchronize(P.scomp));
         const int w = wr(user, x.hout, got);
-        if (w) return sfail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
+        if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
         tout += got;
         tblocks += nb;
     }
@@ -338,8 +314,8 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
 
 int fcx_decompress_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap,
                         uint64_t *out_len) {
-    if (!dctx || !in || (cap && !out)) return sfail(FCX_ERR_ARG, "fcx_decompress_host: NULL argument");
-    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return sfail(FCX_ERR_FORMAT, "not an FCX stream");
+    if (!dctx || !in || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_decompress_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
     MemIO m{in, in_len, 0, out, cap, 0};
     const int r = fcx_decompress_stream(dctx, mem_read, mem_write, &m, in_len - FCX_HEADER_BYTES, nullptr, nullptr,
                                         nullptr);
