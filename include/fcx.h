@@ -247,8 +247,20 @@ int fcx_lz78_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, u
  * `stream`; records are decoded in batches of fcx_lz78_decode_batch_records(), with scratch (in
  * the context, grown on demand) per token of the batch in flight, and the stream is synchronised
  * once per batch (to size that scratch) and at the end.  FCX_ERR_ARG for a NULL ctx, d_in, d_out
- * or out_len (before the device is touched); FCX_ERR_FORMAT "malformed record k" (1-based) for
- * the first bad record; FCX_ERR_CAPACITY when the decoded bytes exceed cap. */
+ * or out_len (before the device is touched); FCX_ERR_FORMAT "malformed record k" (1-based);
+ * FCX_ERR_CAPACITY when the decoded bytes exceed cap.
+ * The record named is the first one that fails the earliest stage that fails: the framing of the
+ * whole run is checked first, then, batch after batch, the headers, the trees, the links and
+ * sizes, and a stage is not run once an earlier one failed.  It is the first bad record of the
+ * run unless a record before it in the same batch fails a later stage.
+ * Domain: the streams the reference's encoder can write for a block of <= 1 MiB.  FCX_ERR_FORMAT
+ * also for these streams, which the reference decoder would take: wcnt above 1 MiB + 10 used
+ * indices; more than 4100 groups; N above 1 MiB + 8 tokens; a decoded size above 1 MiB + 8 bytes
+ * counted before the tail-zero rule takes its byte (a parent chain deeper than 1447); a group code
+ * of more than 32 bits; a group tree in which a node has two parents or none, the root is a child,
+ * or a child id is >= 2G - 1, whether a code walks there or not; a char tree outside the domain of
+ * fcx_decompress_shard (two parents, no parent, a child that does not precede its parent, a code
+ * of more than 32 bits). */
 int fcx_lz78_decompress_shard(fcx_dctx *ctx, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks,
                               uint8_t *d_out, uint64_t cap, uint64_t *out_len, void *stream);
 /* records per internal batch of fcx_lz78_decompress_shard */

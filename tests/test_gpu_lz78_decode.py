@@ -17,6 +17,7 @@ import pytest
 import inputs
 import my_compress_amd as mc
 import oracle
+from fcx8_craft import parse   # noqa: F401  (the payload layout; test_gpu_decode_crafted.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -131,38 +132,6 @@ def test_run_spans_three_batches(dctx, cuda):
     cap = len(data) + 64
     assert shard(dctx, cuda, recs, n, cap) == oracle.lz78_decompress_file(blob, cap)
     check_stages(dctx)
-
-
-# ---- the payload layout my_decompress_file_lz78 reads (3478-3600) ----
-def parse(p: bytes) -> dict:
-    """field offsets of one payload: wcnt, bitmap, G, [tree, N, W, words], N, gpos, char header"""
-    f = {"wcnt": struct.unpack_from("<I", p, 0)[0]}
-    q, seen = 4, 0
-    while True:   # the bitmap ends with the byte of its wcnt-th set bit
-        seen += bin(p[q]).count("1")
-        q += 1
-        if seen >= f["wcnt"]:
-            break
-    f["G"] = G = struct.unpack_from("<I", p, q)[0]
-    q += 4
-    if G > 1:
-        f["tree"] = q
-        q += 8 * (G - 1)
-        f["N"], f["W"] = struct.unpack_from("<II", p, q)
-        f["W_off"] = q + 4
-        q += 8 + 4 * f["W"]
-    else:
-        f["N"] = struct.unpack_from("<I", p, q)[0]
-        q += 4
-    f["gpos"] = q
-    q += f["N"]
-    f["ts"] = ts = p[q]
-    f["cbm"] = q + 1
-    f["cpairs"] = q + 1 + (2 * ts + 7) // 8
-    f["nw_off"] = f["cpairs"] + 2 * ts
-    f["nw"] = struct.unpack_from("<I", p, f["nw_off"])[0]
-    assert f["nw_off"] + 4 + 4 * f["nw"] == len(p)
-    return f
 
 
 def patch_u32(p: bytes, off: int, v: int) -> bytes:
