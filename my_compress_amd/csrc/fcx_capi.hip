@@ -22,8 +22,6 @@ thread_local std::string g_err;
 
 inline uint32_t round16(uint64_t x) { return (uint32_t)((x + 15) & ~15ull); }
 
-constexpr uint32_t kMaxGroups = 8;   // block groups of a pipelined fcx_compress_shard
-
 const char *kStageNames[] = {"route",        "match",       "stitch", "emit",   "hist",   "tree",
                              "block_layout", "scan_blocks", "zero",   "encode", "headers"};
 constexpr int kNumStages = 11;
@@ -87,7 +85,7 @@ static const MatchUnit &match_unit(int kernel) {   // (auto: the general unit; i
     return kUnits[kSearchUnits];
 }
 constexpr uint32_t kRestGrid = 512;         // k_match_rest_<unit>'s workgroups (2 per CU: <= 128 VGPRs)
-constexpr uint64_t kRouteBytes = 4ull * kRouteWords * 8;   // route counters of kMaxGroups (= 8) groups
+constexpr uint64_t kRouteBytes = 4ull * kRouteWords;       // the route counters of a call
 constexpr uint64_t kWordBytes = kCwRouteBytes + kRouteBytes;   // dev_words (the status words of fcx_device.h)
 constexpr uint64_t kHwColdBytes = kWordBytes;              // host_words only: byte offset of the first call's counts
 
@@ -124,40 +122,19 @@ struct fcx_ctx : CtxScratch {
     PinnedBuf<uint64_t> host_words;    // their mirror: [kCwTotal, kCwErr] length reads; kCwLazy and the route
                                        // counters of a recent call (copied back asynchronously after every
                                        // routed call); from kHwColdBytes the first call's counts (waited for)
-    bool have_hint = false;           // a routed call has run: the estimates below are set
-    uint64_t hint_cnt[kRoutes] = {};   // tiles per list (after the hand-ons) of a recent call ...
-    uint64_t hint_valid = 0;           // ... out of its tiles with bytes
-    uint64_t hint_fix = 0;             // its hand-ons plus its lazy tiles (k_tree): > 0 keeps every unit listed
-    uint32_t last_grid[kMaxGroups][kRoutes] = {};   // the last call's unit grids per group
-    uint32_t last_groups = 0;
+    RouteHint hint;                    // the routed calls' estimate of each unit's share (fcx_route_plan.h)
+    uint32_t last_grid[kRoutes] = {};  // the last call's unit grids
     bool last_routed = false, last_cold = false;
     int last_kernel = kMatchGeneral;   // the last call's match kernel (routed: the unit with the largest grid)
-    // pipelined launch: the shard's blocks in groups, consecutive groups on two streams so
-    // one group's serial / latency-bound kernels (stitch, tree, scan, emit, encode) overlap
-    // the next group's match kernel; the record-offset scans stay in group order
-    uint32_t groups = 0;       // 0 = automatic (fcx_ctx_set_groups)
-    hipStream_t gst[2] = {nullptr, nullptr};
-    hipEvent_t gsync[kMaxGroups + 3] = {};   // [0] start, [1..2] stream ends, [3 + g] scan of group g
     // profiling
     bool profiling = false;
     uint32_t match_mode = 0;   // k_match tile-mode bits (fcx_ctx_set_match_mode)
     int kernel = kMatchAuto;   // match kernel (MatchKernel): auto = chosen per call from the block kinds
     uint32_t emit_dbg = 0;     // k_emit development exits (fcx_debug_emit_bits; output invalid)
-    StageTimes times{kMaxGroups, kNumStages};   // a lane per block group, read on the first fcx_ctx_stage query
+    StageTimes times{kNumStages};   // read on the first fcx_ctx_stage query
     Layout last{};
-
-    fcx_ctx() {
-        for (auto &e : gsync) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        for (auto &s2 : gst) (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-    }
-    ~fcx_ctx() {
-        for (auto e : gsync)
-            if (e) (void)hipEventDestroy(e);
-        for (auto s2 : gst)
-            if (s2) (void)hipStreamDestroy(s2);
-    }
 };
-static_assert(kMaxGroups <= StageTimes::kLanes && kNumStages <= StageTimes::kStages, "StageTimes");
+static_assert(kNumStages <= StageTimes::kStages, "StageTimes");
 
 namespace {
 int ensure_scratch(fcx_ctx *c, uint64_t n) {
@@ -188,6 +165,63 @@ int ensure_scratch(fcx_ctx *c, uint64_t n) {
     c->cap_tiles = nt;
     c->cap_n = (uint64_t)L.nblocks * c->B;
     c->cap_blocks = L.nblocks;
+    return FCX_OK;
+}
+
+// The routed match stage of a compress call: classify the shard's tiles into the unit lists, then each
+// unit over its list with a grid from the estimate (the first call waits for its own counts),
+// k_match_rest for the rest.  ev: the stage events of a profiled call, or null (the route stage ends
+// at ev[1])
+int match_routed(fcx_ctx *c, const MatchArgs &ma, hipStream_t st, hipEvent_t *ev) {
+    uint32_t *rc = (uint32_t *)((uint8_t *)c->dev_words.p + kCwRouteBytes);   // the route counters
+    const uint32_t stride = (uint32_t)c->cap_tiles, ntg = ma.L.nblocks * ma.L.tpb;
+    auto list_of = [&](uint32_t u) { return c->rlist + (uint64_t)u * stride; };
+    launch_classify(ma.in, ma.L, c->rlist, stride, rc, c->tkind, st);
+    if (ev) FCX_HIP(hipEventRecord(ev[1], st));
+    uint64_t est[kRoutes];
+    if (!c->hint.have) {
+        uint32_t *cold = (uint32_t *)((uint8_t *)c->host_words.p + kHwColdBytes);
+        FCX_HIP(hipMemcpyAsync(cold, rc, 4 * kRouteWords, hipMemcpyDeviceToHost, st));
+        FCX_HIP(hipStreamSynchronize(st));
+        for (uint32_t u = 0; u < kRoutes; u++) est[u] = cold[u];
+        c->hint.adopt(cold, 0);   // (no hand-ons yet, no lazy tiles: fix stays 0)
+    } else {
+        route_estimate(c->hint.cnt, c->hint.valid, ntg, est);
+    }
+    const RoutePlan plan = plan_route(est, ntg, c->hint.fix != 0);
+    // the uniform unit first: the tiles it hands on join the runs list before any runs launch reads it
+    launch_match_uniform(ma, list_of(kRouteUniform), rc + kRouteUniform, list_of(kRouteRuns), rc + kRouteRuns,
+                         c->tkind, plan.ugrid, st);
+    MatchRoute rts[kSearchUnits];   // per unit: its routed form (its remainder's; its launch's unless direct)
+    for (uint32_t u : plan.order) {
+        const bool direct = plan.grid[u] == kRestDirect;
+        MatchRoute &rt = rts[u];
+        rt.kind = c->tkind;
+        rt.mine = u;
+        rt.cnt = rc + u;
+        if (!direct) rt.list = list_of(u);
+        if (u == kRouteSparse || u == kRouteRuns) {
+            rt.defer_list = list_of(kRouteNoFilter);
+            rt.defer_cnt = rc + kRouteNoFilter;
+        }
+        // the no-filter list's length now, before its listed launch (rest_start)
+        if (rest_start(plan.grid[u], u).word == (int)kRcCover) launch_route_mark(rc + kRcCover, rc + kRouteNoFilter, st);
+        // (direct over every tile: the unrouted code, no kind check and no hand-on)
+        const MatchRoute launch = direct && plan.every ? MatchRoute{} : rt;
+        kUnits[u].launch(ma, st, 0u, &launch, direct ? 0u : plan.grid[u]);
+        c->last_grid[u] = plan.grid[u];
+    }
+    c->last_kernel = est[kRouteUniform] > est[plan.best] ? kMatchUniform
+                     : est[plan.best]                    ? kUnits[plan.best].kernel
+                                                         : kMatchGeneral;
+    // each unit's remainder (the no-filter one last: it takes the others' hand-ons); a direct
+    // sparse / runs / 4-byte launch leaves none
+    for (uint32_t u = 0; u < kSearchUnits; u++) {
+        const RestStart rs = rest_start(plan.grid[u], u);
+        if (rs.none()) continue;
+        const RouteRest rest{list_of(u), rc + u, rs.start, rs.word >= 0 ? rc + rs.word : nullptr};
+        kUnits[u].rest(ma, rest, rts[u], kRestGrid, st);
+    }
     return FCX_OK;
 }
 }  // namespace
@@ -236,7 +270,6 @@ int fcx_ctx_create(fcx_ctx **out, int device, uint32_t block_bytes, uint64_t max
     std::unique_ptr<fcx_ctx, Calls<fcx_ctx_destroy>> c(new fcx_ctx());
     c->device = device;
     c->B = block_bytes;
-    static_assert(kMaxGroups == 8, "kRouteBytes");
     if ((e = c->host_words.alloc(kHwColdBytes + kRouteBytes)) != hipSuccess)
         return fail(FCX_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
     memset(c->host_words, 0, kHwColdBytes + kRouteBytes);
@@ -303,8 +336,6 @@ int fcx_ctx_set_match_mode(fcx_ctx *c, int mode) {
 
 int fcx_ctx_stage_count(fcx_ctx *c) { return c ? c->times.n : 0; }
 
-// per stage: the sum over the call's block groups of that stage's span on the group's stream (with
-// groups > 1 the spans include what the other stream ran meanwhile)
 int fcx_ctx_stage(fcx_ctx *c, int i, const char **name, float *ms) {
     if (!c || i < 0 || i >= kNumStages) return fail(FCX_ERR_ARG, "bad stage");
     if (!c->times.n) return fail(FCX_ERR_ARG, "last call was not profiled");
@@ -328,152 +359,52 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     c->last = L;
     uint64_t *total = c->dev_words + kCwTotal;
     uint32_t *err = (uint32_t *)(c->dev_words + kCwErr);
-    uint32_t *route_cnt = (uint32_t *)((uint8_t *)c->dev_words.p + kCwRouteBytes);   // kRouteWords per group
-    // block groups: automatic = one.  Measured on 128 MiB - 1 GiB rand / text / runs shards, 2-8
-    // groups were 0-7 % slower than one: every kernel of the sequence already fills the chip,
-    // so overlapping them only interleaves the same work
-    uint32_t G = c->groups;
-    if (G == 0) G = 1;
-    G = std::min(std::max(G, 1u), std::min(kMaxGroups, std::max(1u, L.nblocks / 64)));
-    const uint32_t per = (L.nblocks + G - 1) / G;
-    G = (L.nblocks + per - 1) / per;
     c->times.reset();
-    if (c->profiling) c->times.publish(kStageNames, kNumStages, (int)G);
+    hipEvent_t *ev = nullptr;   // the stage events of a profiled call
+    if (c->profiling) {
+        c->times.publish(kStageNames, kNumStages, true);
+        ev = c->times.events();
+    }
 
     // match search: unrouted when a unit is forced (fcx_ctx_set_match_mode), else routed per tile
     // (fcx_route.hip): the estimates of each unit's share come from the route counters of a recent
     // call (landing asynchronously: any values are a valid estimate, they only size the grids)
     const bool routed = c->kernel == kMatchAuto;
-    if (routed && c->have_hint) {
+    if (routed && c->hint.have) {
         const uint32_t *hr = (const uint32_t *)((const uint8_t *)c->host_words.p + kCwRouteBytes);
-        uint64_t cnt[kRoutes] = {}, valid = 0, fix = 0;
-        for (uint32_t g = 0; g < kMaxGroups; g++) {
-            for (uint32_t u = 0; u < kRoutes; u++) cnt[u] += __atomic_load_n(&hr[kRouteWords * g + u], __ATOMIC_RELAXED);
-            valid += __atomic_load_n(&hr[kRouteWords * g + kRcValid], __ATOMIC_RELAXED);
-            fix += __atomic_load_n(&hr[kRouteWords * g + kRouteNoFilter], __ATOMIC_RELAXED) -
-                   __atomic_load_n(&hr[kRouteWords * g + kRcNfFiled], __ATOMIC_RELAXED);
-        }
-        fix += (uint32_t)__atomic_load_n(&c->host_words[kCwLazy], __ATOMIC_RELAXED);   // lazy tiles (k_tree)
-        if (valid) {
-            for (uint32_t u = 0; u < kRoutes; u++) c->hint_cnt[u] = cnt[u];
-            c->hint_valid = valid;
-            c->hint_fix = fix;
-        }
+        uint32_t counters[kRouteWords];
+        for (uint32_t w = 0; w < kRouteWords; w++) counters[w] = __atomic_load_n(&hr[w], __ATOMIC_RELAXED);
+        const uint32_t lazy = (uint32_t)__atomic_load_n(&c->host_words[kCwLazy], __ATOMIC_RELAXED);   // (k_tree)
+        c->hint.adopt(counters, lazy);
     }
     c->last_routed = routed;
-    c->last_cold = routed && !c->have_hint;
-    c->last_groups = G;
+    c->last_cold = routed && !c->hint.have;
     c->last_kernel = routed ? kMatchGeneral : c->kernel;
-    uint64_t cold_cnt[kRoutes] = {}, cold_valid = 0;
     FCX_HIP(hipMemsetAsync(c->dev_words, 0, kWordBytes, st));
-    if (G > 1) {
-        FCX_HIP(hipEventRecord(c->gsync[0], st));
-        for (auto s2 : c->gst) FCX_HIP(hipStreamWaitEvent(s2, c->gsync[0], 0));
+    if (ev) FCX_HIP(hipEventRecord(ev[0], st));   // (the memset above is not timed)
+    const MatchArgs ma{d_in, L, c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok};
+    if (!routed) {
+        if (ev) FCX_HIP(hipEventRecord(ev[1], st));
+        match_unit(c->kernel).launch(ma, st, c->match_mode, nullptr, 0);
+    } else {
+        FCX_TRY(match_routed(c, ma, st, ev));
     }
-    for (uint32_t g = 0; g < G; g++) {
-        hipStream_t sg = G > 1 ? c->gst[g & 1] : st;
-        hipEvent_t *ev = c->profiling ? c->times.lane(g) : nullptr;
-        const uint64_t b0 = (uint64_t)g * per;
-        const uint32_t gb = (uint32_t)std::min<uint64_t>(per, L.nblocks - b0);
-        const Layout Lg = G > 1 ? make_layout(std::min<uint64_t>((uint64_t)gb * c->B, n - b0 * c->B), c->B) : L;
-        const uint64_t t0 = b0 * L.tpb;   // first tile of the group
-        uint8_t *sg_s[kStreams];
-        for (uint32_t q = 0; q < kStreams; q++) sg_s[q] = c->s[q] + b0 * L.sstride[q];
-        if (ev) FCX_HIP(hipEventRecord(ev[0], sg));   // (the memset above is not timed per group)
-        const uint8_t *gin = d_in + b0 * c->B;
-        const MatchArgs ma{gin, Lg, c->m + b0 * c->B, c->mbits + b0 * L.wpb, c->chain + b0 * L.wpb,
-                           c->chain_pfx + t0 * (kTile / 64), c->tinfo + 8 * t0, c->mtok + t0 * kTileMatches};
-        if (!routed) {
-            if (ev) FCX_HIP(hipEventRecord(ev[1], sg));
-            match_unit(c->kernel).launch(ma, sg, c->match_mode, nullptr, 0);
-        } else {
-            // classify the group's tiles into the unit lists, then each unit over its list with a grid
-            // from the estimate (the first call waits for its own counts), k_match_rest for the rest
-            uint32_t *rc = route_cnt + kRouteWords * g;
-            uint32_t *lists = c->rlist + t0;
-            const uint32_t stride = (uint32_t)c->cap_tiles, ntg = Lg.nblocks * Lg.tpb;
-            auto list_of = [&](uint32_t u) { return lists + (uint64_t)u * stride; };
-            launch_classify(gin, Lg, lists, stride, rc, c->tkind + t0, sg);
-            if (ev) FCX_HIP(hipEventRecord(ev[1], sg));
-            uint64_t est[kRoutes];
-            if (!c->have_hint) {
-                uint32_t *cold = (uint32_t *)((uint8_t *)c->host_words.p + kHwColdBytes);
-                FCX_HIP(hipMemcpyAsync(cold, rc, 4 * kRouteWords, hipMemcpyDeviceToHost, sg));
-                FCX_HIP(hipStreamSynchronize(sg));
-                for (uint32_t u = 0; u < kRoutes; u++) { est[u] = cold[u]; cold_cnt[u] += cold[u]; }
-                cold_valid += cold[kRcValid];
-            } else {
-                route_estimate(c->hint_cnt, c->hint_valid, ntg, est);
-            }
-            const RoutePlan plan = plan_route(est, ntg, c->hint_fix != 0);
-            // the uniform unit first: the tiles it hands on join the runs list before any runs launch reads it
-            launch_match_uniform(ma, list_of(kRouteUniform), rc + kRouteUniform, list_of(kRouteRuns), rc + kRouteRuns,
-                                 c->tkind + t0, plan.ugrid, sg);
-            MatchRoute rts[kSearchUnits];   // per unit: its routed form (its remainder's; its launch's unless direct)
-            for (uint32_t u : plan.order) {
-                const bool direct = plan.grid[u] == kRestDirect;
-                MatchRoute &rt = rts[u];
-                rt.kind = c->tkind + t0;
-                rt.mine = u;
-                rt.cnt = rc + u;
-                if (!direct) rt.list = list_of(u);
-                if (u == kRouteSparse || u == kRouteRuns) {
-                    rt.defer_list = list_of(kRouteNoFilter);
-                    rt.defer_cnt = rc + kRouteNoFilter;
-                }
-                // the no-filter list's length now, before its listed launch (rest_start)
-                if (rest_start(plan.grid[u], u).word == (int)kRcCover)
-                    launch_route_mark(rc + kRcCover, rc + kRouteNoFilter, sg);
-                // (direct over every tile: the unrouted code, no kind check and no hand-on)
-                const MatchRoute launch = direct && plan.every ? MatchRoute{} : rt;
-                kUnits[u].launch(ma, sg, 0u, &launch, direct ? 0u : plan.grid[u]);
-                c->last_grid[g][u] = plan.grid[u];
-            }
-            if (g == 0)
-                c->last_kernel = est[kRouteUniform] > est[plan.best] ? kMatchUniform
-                                 : est[plan.best]                    ? kUnits[plan.best].kernel
-                                                                     : kMatchGeneral;
-            // each unit's remainder (the no-filter one last: it takes the others' hand-ons); a direct
-            // sparse / runs / 4-byte launch leaves none
-            for (uint32_t u = 0; u < kSearchUnits; u++) {
-                const RestStart rs = rest_start(plan.grid[u], u);
-                if (rs.none()) continue;
-                const RouteRest rest{list_of(u), rc + u, rs.start, rs.word >= 0 ? rc + rs.word : nullptr};
-                kUnits[u].rest(ma, rest, rts[u], kRestGrid, sg);
-            }
-        }
-        if (ev) FCX_HIP(hipEventRecord(ev[2], sg));
-        launch_parse(gin, Lg, ma.m, ma.mbits, ma.chain, ma.chain_pfx, ma.tinfo, ma.mtok, c->fp + 12 * t0,
-                     c->tile_off + 3 * t0, c->tconv + t0, c->binfo + b0, sg_s[0], sg_s[1], sg_s[2], sg_s[3],
-                     c->thist + t0 * 256, c->sdesc + b0 * ((c->B + kCharSeg - 1) / kCharSeg), err, sg, ev ? ev + 3 : nullptr,
-                     c->emit_dbg);
-        if (c->emit_dbg & 0xFFFFu) {   // (development: k_emit's timing exits leave invalid streams; stop here)
-            if (ev)
-                for (int q = 5; q <= kNumStages; q++) FCX_HIP(hipEventRecord(ev[q], sg));
-            continue;
-        }
-        launch_entropy(Lg, c->binfo + b0, sg_s[0], sg_s[1], sg_s[2], sg_s[3], c->thist + t0 * 256,
-                       c->ctab + b0 * kStreams * 256,
-                       c->ltab + b0 * kStreams * 256, c->hhdr + b0 * kStreams * kHuffHdrStride,
-                       c->cstat + 2 * b0 * L.cpb_total, c->blk_off + b0, total, d_out, cap, err, gin, c->sdesc + b0 * ((c->B + kCharSeg - 1) / kCharSeg), sg,
-                       ev ? ev + 5 : nullptr,
-                       G > 1 && g > 0 ? c->gsync[3 + g - 1] : nullptr, G > 1 ? c->gsync[3 + g] : nullptr, c->emit_dbg >> 16);
-    }
-    if (G > 1) {
-        for (uint32_t q = 0; q < 2; q++) {
-            FCX_HIP(hipEventRecord(c->gsync[1 + q], c->gst[q]));
-            FCX_HIP(hipStreamWaitEvent(st, c->gsync[1 + q], 0));
-        }
+    if (ev) FCX_HIP(hipEventRecord(ev[2], st));
+    launch_parse(d_in, L, ma.m, ma.mbits, ma.chain, ma.chain_pfx, ma.tinfo, ma.mtok, c->fp, c->tile_off, c->tconv,
+                 c->binfo, c->s[0], c->s[1], c->s[2], c->s[3], c->thist, c->sdesc, err, st, ev ? ev + 3 : nullptr,
+                 c->emit_dbg);
+    if (c->emit_dbg & 0xFFFFu) {   // (development: k_emit's timing exits leave invalid streams; stop here)
+        if (ev)
+            for (int q = 5; q <= kNumStages; q++) FCX_HIP(hipEventRecord(ev[q], st));
+    } else {
+        launch_entropy(L, c->binfo, c->s[0], c->s[1], c->s[2], c->s[3], c->thist, c->ctab, c->ltab, c->hhdr, c->cstat,
+                       c->blk_off, total, d_out, cap, err, d_in, c->sdesc, st, ev ? ev + 5 : nullptr, c->emit_dbg >> 16);
     }
     FCX_HIP(hipGetLastError());
-    if (routed && !c->have_hint && cold_valid) {
-        for (uint32_t u = 0; u < kRoutes; u++) c->hint_cnt[u] = cold_cnt[u];
-        c->hint_valid = cold_valid;
-    }
     if (routed) {   // the lazy tiles and route counters back for the next calls' estimates (asynchronous)
         FCX_HIP(hipMemcpyAsync(c->host_words + kCwLazy, c->dev_words + kCwLazy, kWordBytes - 8 * kCwLazy,
                                hipMemcpyDeviceToHost, st));
-        c->have_hint = true;
+        c->hint.have = true;
     }
     if (out_len) {
         FCX_HIP(hipMemcpyAsync(c->host_words, c->dev_words, kCwHeadBytes, hipMemcpyDeviceToHost, st));
@@ -481,13 +412,6 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
         FCX_TRY(check_err_bits(c));
         *out_len = c->host_words[kCwTotal];
     }
-    return FCX_OK;
-}
-
-int fcx_ctx_set_groups(fcx_ctx *c, int groups) {
-    if (!c) return fail(FCX_ERR_ARG, "NULL ctx");
-    if (groups < 0 || groups > (int)kMaxGroups) return fail(FCX_ERR_ARG, "groups must be in [0, 8] (0 = automatic)");
-    c->groups = (uint32_t)groups;
     return FCX_OK;
 }
 
@@ -529,20 +453,17 @@ int fcx_ctx_route_stats(fcx_ctx *c, uint64_t *out, int n) {
     if (c->last_routed) {
         FCX_HIP(hipSetDevice(c->device));
         FCX_HIP(hipDeviceSynchronize());
-        uint32_t rc[kRouteWords * kMaxGroups];
-        FCX_HIP(hipMemcpy(rc, (uint8_t *)c->dev_words.p + kCwRouteBytes, sizeof(rc), hipMemcpyDeviceToHost));
-        for (uint32_t g = 0; g < c->last_groups; g++) {
-            const uint32_t *r = rc + kRouteWords * g;
-            for (uint32_t u = 0; u < kSearchUnits; u++) {
-                v[u] += r[u];
-                const uint32_t s0 = rest_start(c->last_grid[g][u], u, r);
-                v[6] += r[u] > s0 ? r[u] - s0 : 0u;
-            }
-            v[4] += r[kRouteNoFilter] - r[kRcNfFiled] + r[kRouteRuns] - r[kRcRunsFiled];
-            v[5] += r[kRcValid];
-            v[8] += r[kRouteUniform];
+        uint32_t r[kRouteWords];
+        FCX_HIP(hipMemcpy(r, (uint8_t *)c->dev_words.p + kCwRouteBytes, sizeof(r), hipMemcpyDeviceToHost));
+        for (uint32_t u = 0; u < kSearchUnits; u++) {
+            v[u] = r[u];
+            const uint32_t s0 = rest_start(c->last_grid[u], u, r);
+            v[6] += r[u] > s0 ? r[u] - s0 : 0u;
         }
+        v[4] = r[kRouteNoFilter] - r[kRcNfFiled] + r[kRouteRuns] - r[kRcRunsFiled];
+        v[5] = r[kRcValid];
         v[7] = c->last_cold;
+        v[8] = r[kRouteUniform];
     }
     for (int i = 0; i < n && i < FCX_ROUTE_STATS; i++) out[i] = v[i];
     return c->last_routed ? FCX_OK : fail(FCX_ERR_ARG, "the last call was not routed (a match unit is forced)");
@@ -578,6 +499,20 @@ int fcx_debug_route_estimate(const uint64_t cnt[5], uint64_t valid, uint32_t ntg
 // ... and where a unit's remainder starts, given its grid in the plan and the call's 16 route counters
 uint32_t fcx_debug_rest_start(uint32_t grid, uint32_t unit, const uint32_t counters[16]) {
     return unit < kSearchUnits && counters ? rest_start(grid, unit, counters) : ~0u;
+}
+// ... and the estimate a context keeps (RouteHint) after it adopts a call's 16 route counters and lazy
+// tiles.  hint: cnt[5], valid, fix, in and out
+int fcx_debug_route_hint(uint64_t hint[7], const uint32_t counters[16], uint32_t lazy) {
+    if (!hint || !counters) return fail(FCX_ERR_ARG, "fcx_debug_route_hint: NULL");
+    RouteHint h;
+    for (uint32_t u = 0; u < kRoutes; u++) h.cnt[u] = hint[u];
+    h.valid = hint[5];
+    h.fix = hint[6];
+    h.adopt(counters, lazy);
+    for (uint32_t u = 0; u < kRoutes; u++) hint[u] = h.cnt[u];
+    hint[5] = h.valid;
+    hint[6] = h.fix;
+    return FCX_OK;
 }
 
 // development only (not in fcx.h): the sparse unit's repeat filter on the host (fcx_sparse_filter.h), for

@@ -812,9 +812,9 @@ int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint
     if ((uint32_t)hw[kDwErr] & (kDErrRecord | kDErrHeader)) return fail(FCX_ERR_FORMAT, "malformed block records / headers");
     FCX_TRY(D.sym.reserve(hw[kDwSymBytes] + 64, "symbols"));
     FCX_TRY(D.glen.reserve(4 * hw[kDwGolombVals] + 64, "golomb values"));
-    if (c->profiling) c->times.publish(kDStageNames, kDStages, 1);
+    if (c->profiling) c->times.publish(kDStageNames, kDStages, true);
     dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.symb, D.tbl, D.child, D.sym, D.glen, D.words, err, 1, st,
-               c->profiling ? c->times.lane() : nullptr);
+               c->profiling ? c->times.events() : nullptr);
     FCX_HIP(hipGetLastError());
     FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * kDwWords, hipMemcpyDeviceToHost, st));
     FCX_HIP(hipStreamSynchronize(st));

@@ -383,7 +383,7 @@ struct fcx_dctx {
     fcx::Dec7 d7;
     std::unique_ptr<fcx::Scratch78, fcx::Calls<fcx::free_scratch78>> d78;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
-    fcx::StageTimes times{1, fcx::kD78Stages};
+    fcx::StageTimes times{fcx::kD78Stages};
 };
 
 #endif  // FCX_DEC_SHARED_H

@@ -68,7 +68,7 @@ constexpr uint32_t kCwErr = 1;       // error bits, a u32 (the kernels' err)
 constexpr uint32_t kCwLazy = 2;      // lazy tiles, a u32: k_tree adds them at err + kErrToLazy
 constexpr uint32_t kErrToLazy = 2 * (kCwLazy - kCwErr);   // (in u32 steps)
 constexpr uint32_t kCwHeadBytes = 16;    // [kCwTotal, kCwErr]: what a length read copies back
-constexpr uint32_t kCwRouteBytes = 64;   // byte offset of the route counters: kRouteWords u32 per block group
+constexpr uint32_t kCwRouteBytes = 64;   // byte offset of the route counters: kRouteWords u32
 
 // per-block results of the parse/emit stage
 struct BlockInfo {
@@ -150,8 +150,7 @@ void launch_parse(const uint8_t *in, const Layout &L, uint32_t *m, const uint64_
 void launch_entropy(const Layout &L, BlockInfo *binfo, uint8_t *s0, uint8_t *s1, uint8_t *s2, uint8_t *s3,
                     const uint16_t *thist, uint32_t *ctab, uint8_t *ltab, uint8_t *hhdr, uint64_t *cstat,
                     uint64_t *blk_off, uint64_t *total, uint8_t *out, uint64_t cap, uint32_t *err, const uint8_t *in,
-                    const uint32_t *sdesc, hipStream_t st, hipEvent_t *ev, hipEvent_t wait_scan, hipEvent_t rec_scan,
-                    uint32_t tree_dbg = 0);
+                    const uint32_t *sdesc, hipStream_t st, hipEvent_t *ev, uint32_t tree_dbg = 0);
 
 // ---- wave64 helpers --------------------------------------------------------
 __device__ inline uint32_t lane_id() { return __lane_id(); }

@@ -447,8 +447,7 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(uint32_t nblocks, const Bl
                                                       uint64_t cap, uint32_t *__restrict__ err) {
     __shared__ uint64_t wsum[16];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // offsets continue after the records of the shard's earlier block groups (fcx_compress_shard's
-    // pipelined launch: their scans ran before this one); 0 for the first group
+    // the offsets start at *total, which the call's memset of the status words cleared: 0
     uint64_t carry = *total;
     for (uint32_t b0 = 0; b0 < nblocks; b0 += 1024) {
         const uint32_t b = b0 + tid;
@@ -743,7 +742,7 @@ void launch_entropy(const Layout &L, BlockInfo *binfo, uint8_t *s0, uint8_t *s1,
                     const uint16_t *thist, uint32_t *ctab,
                     uint8_t *ltab, uint8_t *hhdr, uint64_t *cstat, uint64_t *blk_off, uint64_t *total, uint8_t *out,
                     uint64_t cap, uint32_t *err, const uint8_t *in, const uint32_t *sdesc, hipStream_t st, hipEvent_t *ev,
-                    hipEvent_t wait_scan, hipEvent_t rec_scan, uint32_t tree_dbg) {
+                    uint32_t tree_dbg) {
     const uint32_t nchunks = L.nblocks * L.cpb_total;
     if (ev) (void)hipEventRecord(ev[0], st);   // (the histograms are k_emit's: no stage of their own)
     if (tree_dbg) {   // (development: k_tree's timing exits; nothing after it runs)
@@ -758,9 +757,7 @@ void launch_entropy(const Layout &L, BlockInfo *binfo, uint8_t *s0, uint8_t *s1,
     if (ev) (void)hipEventRecord(ev[1], st);
     hipLaunchKernelGGL(k_block_layout, dim3((L.nblocks + 63) / 64), dim3(64), 0, st, L.nblocks, binfo);
     if (ev) (void)hipEventRecord(ev[2], st);
-    if (wait_scan) (void)hipStreamWaitEvent(st, wait_scan, 0);   // the previous group's record offsets
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, L.nblocks, binfo, blk_off, total, cap, err);
-    if (rec_scan) (void)hipEventRecord(rec_scan, st);
     if (ev) (void)hipEventRecord(ev[3], st);
     if (ev) (void)hipEventRecord(ev[4], st);   // (no edge zeroing: k_encode stores every word whole)
     hipLaunchKernelGGL(k_encode, dim3(nchunks), dim3(kEncT), 0, st, L, binfo, s0, s1, s2, s3, ctab, ltab, cstat,

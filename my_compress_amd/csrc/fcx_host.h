@@ -85,57 +85,55 @@ struct Calls {
 };
 
 // ---- stage times of a profiled call ------------------------------------------------------------
-// Stage k runs between events k and k + 1 of a lane (compress: one lane per block group; the
-// launchers record into lane(g) themselves).  A call starts with reset() and makes its table
-// visible to the *_stage queries with publish(): at once with the lanes still to read (lazy: the
-// first query waits for them and sums stage k over the lanes), or at its end after add() has
-// summed the spans itself (eager: FCX8 reuses one lane's events per batch).
+// Stage k runs between events k and k + 1 (the launchers record into events() themselves).  A
+// call starts with reset() and makes its table visible to the *_stage queries with publish(): at
+// once with the events still to read (lazy: the first query waits for them), or at its end after
+// add() has summed the spans itself (eager: FCX8 reuses the events per batch).
 struct StageTimes {
-    static constexpr int kLanes = 8, kStages = 11;
-    hipEvent_t ev[kLanes][kStages + 1] = {};
+    static constexpr int kStages = 11;
+    hipEvent_t ev[kStages + 1] = {};
     const char *const *names = nullptr;
-    int n = 0;         // stages of the published table; 0: the last call was not profiled
-    int pending = 0;   // lanes not read yet
+    int n = 0;           // stages of the published table; 0: the last call was not profiled
+    bool lazy = false;   // the events are not read yet
     float ms[kStages] = {};
 
-    StageTimes(int lanes, int stages) {
-        for (int g = 0; g < lanes; g++)
-            for (int i = 0; i <= stages; i++) (void)hipEventCreate(&ev[g][i]);
+    explicit StageTimes(int stages) {
+        for (int i = 0; i <= stages; i++) (void)hipEventCreate(&ev[i]);
     }
     StageTimes(const StageTimes &) = delete;
     StageTimes &operator=(const StageTimes &) = delete;
     ~StageTimes() {
-        for (auto &lane : ev)
-            for (hipEvent_t e : lane)
-                if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
     }
     void reset() {
-        n = pending = 0;
+        n = 0;
+        lazy = false;
         for (float &v : ms) v = 0;
     }
-    void publish(const char *const *table, int stages, int lanes = 0) {
+    void publish(const char *const *table, int stages, bool lazy_read = false) {
         names = table;
         n = stages;
-        pending = lanes;
+        lazy = lazy_read;
     }
-    hipEvent_t *lane(int g = 0) { return ev[g]; }
-    void mark(int i, hipStream_t st) { (void)hipEventRecord(ev[0][i], st); }
-    // ms[k] += the span of stage k on lane g, first <= k < last, once event `last` has passed
-    int add(int first, int last, int g = 0) {
-        FCX_HIP(hipEventSynchronize(ev[g][last]));
+    hipEvent_t *events() { return ev; }
+    void mark(int i, hipStream_t st) { (void)hipEventRecord(ev[i], st); }
+    // ms[k] += the span of stage k, first <= k < last, once event `last` has passed
+    int add(int first, int last) {
+        FCX_HIP(hipEventSynchronize(ev[last]));
         for (int k = first; k < last; k++) {
             float v = 0;
-            FCX_HIP(hipEventElapsedTime(&v, ev[g][k], ev[g][k + 1]));
+            FCX_HIP(hipEventElapsedTime(&v, ev[k], ev[k + 1]));
             ms[k] += v;
         }
         return FCX_OK;
     }
     // stage i of the published table (0 <= i < n)
     int stage(int i, const char **name, float *out) {
-        if (pending) {
+        if (lazy) {
             for (float &v : ms) v = 0;
-            for (int g = 0; g < pending; g++) FCX_TRY(add(0, n, g));
-            pending = 0;
+            FCX_TRY(add(0, n));
+            lazy = false;
         }
         if (name) *name = names[i];
         if (out) *out = ms[i];

@@ -16,7 +16,7 @@ enum : uint32_t {
     kRouteSparse = 0, kRouteRuns = 1, kRouteKey4 = 2, kRouteNoFilter = 3, kSearchUnits = 4,
     kRouteUniform = 4, kRoutes = 5
 };
-// route counters per block group (k_classify, the units' hand-ons, the host's cover mark): [0, kRoutes)
+// route counters of a call (k_classify, the units' hand-ons, the host's cover mark): [0, kRoutes)
 // list lengths, then these
 constexpr uint32_t kRcNfFiled = 5;    // tiles the classifier filed as no-filter (its list grows by hand-ons)
 constexpr uint32_t kRcValid = 6;      // tiles with bytes
@@ -25,25 +25,41 @@ constexpr uint32_t kRcRunsFiled = 8;  // tiles the classifier filed as runs (its
 constexpr uint32_t kRouteWords = 16;
 
 constexpr uint32_t kRouteMinTiles = 8;      // a unit expected to get fewer tiles is not launched (k_match_rest)
-constexpr uint32_t kRestDirect = ~0u;       // RoutePlan::grid: a direct launch (over every tile of the group)
+constexpr uint32_t kRestDirect = ~0u;       // RoutePlan::grid: a direct launch (over every tile of the shard)
 
-// each unit's expected tiles among the ntg of a group, from a recent call's list lengths cnt out of its
+// each unit's expected tiles among the ntg of a shard, from a recent call's list lengths cnt out of its
 // valid tiles with bytes (rounded up; any values are a valid estimate, they only size the grids)
 inline void route_estimate(const uint64_t cnt[kRoutes], uint64_t valid, uint32_t ntg, uint64_t est[kRoutes]) {
     const uint64_t v = std::max<uint64_t>(valid, 1);
     for (uint32_t u = 0; u < kRoutes; u++) est[u] = (cnt[u] * ntg + v - 1) / v;
 }
 
+// What a context keeps of a recent routed call for the next calls' estimates.
+struct RouteHint {
+    bool have = false;            // a routed call has run: the estimates below are set
+    uint64_t cnt[kRoutes] = {};   // tiles per list (after the hand-ons) of a recent call ...
+    uint64_t valid = 0;           // ... out of its tiles with bytes
+    uint64_t fix = 0;             // its hand-ons plus its lazy tiles (k_tree): > 0 keeps every unit listed
+    // takes over a call's route counters and lazy tiles; counters without a tile with bytes (nothing has
+    // landed in them yet) leave the estimate as it was
+    void adopt(const uint32_t counters[kRouteWords], uint32_t lazy) {
+        if (!counters[kRcValid]) return;
+        for (uint32_t u = 0; u < kRoutes; u++) cnt[u] = counters[u];
+        valid = counters[kRcValid];
+        fix = (uint64_t)(uint32_t)(counters[kRouteNoFilter] - counters[kRcNfFiled]) + lazy;
+    }
+};
+
 struct RoutePlan {
     uint32_t ugrid;                 // the uniform unit's grid (launched first)
     uint32_t best;                  // the search unit with the largest estimate (ties: the lowest index)
-    bool direct;                    // best runs direct, over every tile of the group ...
+    bool direct;                    // best runs direct, over every tile of the shard ...
     bool every;                     // ... with the unrouted kernel's exact code
     uint32_t order[kSearchUnits];   // the search units in launch order
     uint32_t grid[kSearchUnits];    // per unit: its listed grid (0: not launched), kRestDirect for the direct unit
 };
 
-// est: the group's expected tiles per list; ntg: its tiles; fix: a recent call had hand-ons or lazy
+// est: the shard's expected tiles per list; ntg: its tiles; fix: a recent call had hand-ons or lazy
 // tiles (k_tree) -- tiles its units' samples misfiled
 inline RoutePlan plan_route(const uint64_t est[kRoutes], uint32_t ntg, bool fix) {
     RoutePlan p{};
@@ -52,7 +68,7 @@ inline RoutePlan plan_route(const uint64_t est[kRoutes], uint32_t ntg, bool fix)
     // taken by 8 waves per CU
     p.ugrid = (uint32_t)std::min<uint64_t>(8192, std::max<uint64_t>(2048, (est[kRouteUniform] + 7) / 8 * 8));
     // the unit expected to take most of the tiles (at least half) runs first, direct over every
-    // tile of the group: it drops the others by their kind byte -- or, when the estimate gives
+    // tile of the shard: it drops the others by their kind byte -- or, when the estimate gives
     // it (nearly) all tiles, it searches every tile with the unrouted kernel's exact code, and
     // the few tiles of other kinds are searched again by their own units afterwards (the last
     // writer's outputs are complete).  The others run over their lists.

@@ -1,7 +1,7 @@
 """The routed call's launch plan (my_compress_amd/csrc/fcx_route_plan.h) through libfcx.so's development
 exports: pure host arithmetic, no GPU.  The expected values are worked out by hand from the rules the
-compress call has always applied per block group: a unit's grid is est + est/16 + 32 capped at the
-group's tiles (0 below 8 expected tiles), the unit with the largest estimate (ties: the lowest list)
+compress call has always applied: a unit's grid is est + est/16 + 32 capped at the
+shard's tiles (0 below 8 expected tiles), the unit with the largest estimate (ties: the lowest list)
 goes direct when 2 est >= tiles and no recent call misfiled tiles, with the unrouted code when
 64 est >= 63 tiles, and it is launched first."""
 import ctypes
@@ -25,6 +25,8 @@ def L():
                                              ctypes.POINTER(ctypes.c_uint64)]
     lib.fcx_debug_rest_start.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.fcx_debug_rest_start.restype = ctypes.c_uint32
+    lib.fcx_debug_route_hint.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.c_uint32]
     return lib
 
 
@@ -151,3 +153,48 @@ def test_rest_starts(L):
     # mark; hand-ons that arrive later sit past that length, also where it is below the grid
     assert rest_start(L, 395, NF, lists, nf_filed=290, cover=300) == 300
     assert rest_start(L, 395, NF, lists, nf_filed=290, cover=398) == 395
+
+
+def adopt(L, hint, lists, valid, nf_filed, lazy):
+    """the estimate (cnt[5], valid, fix) after RouteHint::adopt of a call's counters and lazy tiles"""
+    c = (ctypes.c_uint32 * 16)(*lists)
+    c[NF_FILED], c[VALID], c[COVER] = nf_filed, valid, 12345   # (the cover mark plays no part)
+    h = (ctypes.c_uint64 * 7)(*hint)
+    assert L.fcx_debug_route_hint(h, c, lazy) == 0
+    return list(h)
+
+
+def test_hint_ignores_counters_without_valid_tiles(L):
+    prev = [10, 20, 30, 40, 50, 150, 3]
+    assert adopt(L, prev, [1, 2, 3, 9, 5], valid=0, nf_filed=4, lazy=7) == prev
+    assert adopt(L, [0] * 7, [1, 2, 3, 9, 5], valid=0, nf_filed=4, lazy=7) == [0] * 7
+
+
+def test_hint_fix_is_hand_ons_plus_lazy_tiles(L):
+    prev = [10, 20, 30, 40, 50, 150, 3]
+    lists = [100, 200, 300, 400, 24]
+    # the no-filter list holds 400 tiles, 390 of them filed by the classifier: 10 hand-ons, + 2 lazy tiles
+    assert adopt(L, prev, lists, valid=1024, nf_filed=390, lazy=2) == lists + [1024, 12]
+    assert adopt(L, prev, lists, valid=1024, nf_filed=400, lazy=2) == lists + [1024, 2]
+    assert adopt(L, prev, lists, valid=1024, nf_filed=399, lazy=0) == lists + [1024, 1]
+    clean = adopt(L, prev, lists, valid=1024, nf_filed=400, lazy=0)   # (a clean call clears an earlier fix)
+    assert clean == lists + [1024, 0]
+    # a nonzero fix keeps every unit listed, where the same estimates would send no-filter direct
+    nf_most = [0, 0, 0, 1024, 0]
+    for nf_filed, lazy in ((1023, 0), (1024, 1)):
+        h = adopt(L, [0] * 7, nf_most, valid=1024, nf_filed=nf_filed, lazy=lazy)
+        assert h[6] == 1
+        p = plan(L, estimate(L, h[:5], h[5], 1024), 1024, fix=int(h[6] != 0))
+        assert not p["direct"] and p["order"] == [0, 1, 2, 3] and p["grid"] == [0, 0, 0, 1024]
+    h = adopt(L, [0] * 7, nf_most, valid=1024, nf_filed=1024, lazy=0)
+    assert plan(L, estimate(L, h[:5], h[5], 1024), 1024, fix=int(h[6] != 0))["grid"] == [0, 0, 0, DIRECT]
+
+
+def test_cold_adoption_is_adopt_of_the_calls_own_counts(L):
+    """a context's first routed call takes its own counts right after the classifier: every no-filter
+    tile is a filed one and no tile is lazy yet, so the estimate is those counts with fix 0 -- what
+    adopt makes of the same counters, whatever it held before"""
+    lists = [7, 100, 0, 893, 24]
+    want = lists + [1000, 0]
+    assert adopt(L, [0] * 7, lists, valid=1000, nf_filed=893, lazy=0) == want
+    assert adopt(L, [9, 9, 9, 9, 9, 45, 5], lists, valid=1000, nf_filed=893, lazy=0) == want

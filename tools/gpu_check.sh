@@ -1,5 +1,5 @@
 # parity (golden cases, mosaics, forced tile modes) + every full-size digest leg with its stage times
-# (tools/devbench.py); summary: bash tools/gpu_check_summary.sh
+# (tools/devbench.py); summary: bash tools/gpu_check_summary.sh <log directory>
 set -u
 timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_parity.py -m "gpu and not slow" > gpurun_out/gs_parity.log 2>&1 || exit 1
 timeout -k 10 200 python tools/devbench.py --kind rand --seed 4 --mib 1024 --check hl_rand_1GiB > gpurun_out/gs_rand.log 2>&1 || exit 1
