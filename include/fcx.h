@@ -260,6 +260,72 @@ int fcx_lz78_decompress_shard(fcx_dctx *ctx, const uint8_t *d_in, uint64_t in_le
 /* records per internal batch of fcx_lz78_decompress_shard */
 uint32_t fcx_lz78_decode_batch_records(void);
 
+/* ---- random access: decoded-size index and range decode (FCX7 and FCX8) -------------------
+ * A record stores neither its decoded size nor its block size, and the decoded size is not the
+ * encoder's block size: an incompressible FCX7 block may decode to 0 bytes (the early stop,
+ * :2331-2335), an FCX8 block whose bytes end in 0x00 loses that byte (:3701-3703).  So byte x of
+ * the decoded run is not in record x / block; the index below says where it is.
+ *
+ * The decoded bytes are the full decoders' bytes (fcx_decompress_shard, fcx_lz78_decompress_shard),
+ * quirks and all: one-symbol sub-streams decode as zeros, the early stop, the tail-zero rule.  The
+ * streams rejected are the full decoders' too, as far as a pass reads them:
+ * the FCX7 size pass decodes the flags and the Golomb bytes only, so a bad chars or distance
+ * *tree*, or a distance before the block start, is seen by the expansion of that record and not by
+ * the index.  (The FCX8 size pass decodes every stream of a record: it sees all the expansion sees.)
+ *
+ * Error codes: FCX_ERR_ARG for a NULL ctx, d_in (with in_len > 0 or nblocks > 0) or out_len, a
+ * kind other than '7' or '8', exactly one of the two index pointers NULL; FCX_ERR_CAPACITY when
+ * cap < *out_len (*out_len is set); FCX_ERR_FORMAT for a malformed stream. */
+
+/* Index of a device-resident run of nblocks records (kind '7' or '8'): two device arrays of
+ * nblocks + 1 u64 each.  rec_off[k] = byte offset in d_in of record k's u32 length prefix,
+ * rec_off[nblocks] = bytes the nblocks records span; dec_off[k] = decoded bytes of records
+ * 0..k-1 (the bytes fcx_decompress_shard / fcx_lz78_decompress_shard would write before record k),
+ * dec_off[nblocks] = the decoded total, also stored in *total when non-NULL.  Checks the framing,
+ * the headers and the size-bearing streams of every record.  Synchronises `stream`. */
+int fcx_index_shard(fcx_dctx *ctx, char kind, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks,
+                    uint64_t *d_rec_off, uint64_t *d_dec_off, uint64_t *total, void *stream);
+
+/* pread on the decoded run: bytes [off, off + len) of what the full decode would produce, written
+ * to d_out[0 ..).  *out_len = min(len, total - off), 0 when off >= total (not an error).  Nothing
+ * past d_out[*out_len) is written.  Only the records the range touches are expanded (records of
+ * decoded size 0 are skipped), and only the bytes inside the range are stored: there is no staging
+ * copy of whole records.
+ * d_rec_off / d_dec_off: an index from fcx_index_shard over the same run, or both NULL.
+ *  - Both NULL: the call builds an index in the context's scratch first, which checks the framing,
+ *    headers and size-bearing streams of *every* record of the run: a malformed record anywhere in
+ *    the run fails the call.
+ *  - An index given: only the records the call expands are read and checked.  A record outside
+ *    the range may be arbitrarily damaged and the call still succeeds.
+ * A given index is trusted for where things are, not for safety.  A touched record's rec_off must
+ * point at a length prefix that fits in_len, the touched records must chain (each length prefix
+ * leads to the next inside in_len), and each one's decoded size must equal dec_off[k + 1] -
+ * dec_off[k]: otherwise FCX_ERR_FORMAT.  An index that disagrees with the run in a way these
+ * checks do not see gives wrong bytes or FCX_ERR_FORMAT, never an access outside d_in[0, in_len),
+ * the two index arrays or d_out[0, *out_len).  Synchronises `stream`. */
+int fcx_decompress_range_shard(fcx_dctx *ctx, char kind, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks,
+                               const uint64_t *d_rec_off, const uint64_t *d_dec_off, uint64_t off, uint64_t len,
+                               uint8_t *d_out, uint64_t cap, uint64_t *out_len, void *stream);
+
+/* whole file (header + records) in host memory -> the range in host memory, through
+ * fcx_decompress_range_stream */
+int fcx_decompress_range_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t off, uint64_t len,
+                              uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* fcx_decompress_stream's twin: reads record groups as it does, indexes each group, decodes only the
+ * part of the range that falls in the group and writes it, and stops reading once the range is
+ * served (a range past the end reads the whole file and writes nothing).  Every record of the
+ * groups read is checked as by fcx_index_shard.  *total_out = bytes written. */
+int fcx_decompress_range_stream(fcx_dctx *ctx, fcx_read_fn read, fcx_write_fn write, void *user, uint64_t max_in,
+                                uint64_t off, uint64_t len, uint64_t *total_out);
+
+/* Counters of the last fcx_index_shard / fcx_decompress_range_shard call on the context (the host
+ * and stream forms: of their last group), read-only, min(n, FCX_RANGE_STATS) values: records whose
+ * sizes the size pass computed (0 when an index was given), records expanded, bytes stored to
+ * d_out (counted by the kernels that store them), 1 if the call built its own index. */
+#define FCX_RANGE_STATS 4
+int fcx_dctx_range_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

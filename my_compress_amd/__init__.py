@@ -113,6 +113,17 @@ def lib():
         L.fcx_lz78_decode_batch_records.argtypes = []
         L.fcx_lz78_decode_batch_records.restype = ctypes.c_uint32
     P64 = ctypes.POINTER(ctypes.c_uint64)
+    if hasattr(L, "fcx_index_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        L.fcx_index_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p, P64, ctypes.c_void_p]
+        L.fcx_decompress_range_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, P64, ctypes.c_void_p]
+        L.fcx_decompress_range_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                c_u8p, ctypes.c_uint64, P64]
+        L.fcx_decompress_range_stream.argtypes = [ctypes.c_void_p, READ_FN, WRITE_FN, ctypes.c_void_p, ctypes.c_uint64,
+                                                  ctypes.c_uint64, ctypes.c_uint64, P64]
+        L.fcx_dctx_range_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -331,6 +342,56 @@ class DContext:
                "fcx_decompress_stream")
         return t.value, o.value, n.value
 
+    # ---- random access (fcx_index_shard / fcx_decompress_range_*): kind is "7" (FCX7) or "8" (FCX8) ----
+    def index_shard(self, d_in: int, in_len: int, nblocks: int, kind: str, d_rec_off: int, d_dec_off: int,
+                    stream: int = 0) -> int:
+        """index of a device-resident run into two device arrays of nblocks + 1 u64 (record offsets,
+        decoded offsets); returns the decoded total"""
+        total = ctypes.c_uint64(0)
+        _check(lib().fcx_index_shard(self._h, kind.encode(), ctypes.c_void_p(d_in), in_len, nblocks,
+                                     ctypes.c_void_p(d_rec_off), ctypes.c_void_p(d_dec_off), ctypes.byref(total),
+                                     ctypes.c_void_p(stream)), "fcx_index_shard")
+        return total.value
+
+    def decompress_range_shard(self, d_in: int, in_len: int, nblocks: int, kind: str, off: int, n: int, d_out: int,
+                               cap: int, d_rec_off: int = 0, d_dec_off: int = 0, stream: int = 0) -> int:
+        """decoded bytes [off, off + n) of a device-resident run to d_out[0 ..); returns their count
+        (less than n at the end of the run).  d_rec_off / d_dec_off: an index_shard index, or both 0
+        (the call builds its own)."""
+        got = ctypes.c_uint64(0)
+        _check(lib().fcx_decompress_range_shard(self._h, kind.encode(), ctypes.c_void_p(d_in), in_len, nblocks,
+                                                ctypes.c_void_p(d_rec_off or None), ctypes.c_void_p(d_dec_off or None),
+                                                off, n, ctypes.c_void_p(d_out), cap, ctypes.byref(got),
+                                                ctypes.c_void_p(stream)), "fcx_decompress_range_shard")
+        return got.value
+
+    def decompress_range_host(self, blob: bytes, off: int, n: int) -> bytes:
+        """decoded bytes [off, off + n) of a whole FCX7 or FCX8 file, on the GPU"""
+        out = ctypes.create_string_buffer(max(n, 1))
+        got = ctypes.c_uint64(0)
+        _check(lib().fcx_decompress_range_host(self._h, blob, len(blob), off, n, out, n, ctypes.byref(got)),
+               "fcx_decompress_range_host")
+        return out.raw[:got.value]
+
+    def decompress_range_stream(self, src, sink, off: int, n: int) -> int:
+        """decoded bytes [off, off + n) of an FCX7 or FCX8 file from src (binary reader) to sink;
+        reads no further than the range needs; returns the bytes written"""
+        rd, wr = _stream_fns(src, sink)
+        o = ctypes.c_uint64()
+        _check(lib().fcx_decompress_range_stream(self._h, rd, wr, None, 0, off, n, ctypes.byref(o)),
+               "fcx_decompress_range_stream")
+        return o.value
+
+    RANGE_STATS = ("sized", "expanded", "stored", "built_index")
+
+    def range_stats(self) -> dict:
+        """counters of the last index / range call (fcx_dctx_range_stats): records the size pass
+        sized, records expanded, bytes stored to d_out, 1 if the call built its own index"""
+        n = len(self.RANGE_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_range_stats(self._h, vals, n), "fcx_dctx_range_stats")
+        return dict(zip(self.RANGE_STATS, [int(v) for v in vals]))
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -367,6 +428,16 @@ def decompress_gpu(blob: bytes, cap: int = None, device: int = 0, ctx: "DContext
     finally:
         if own:
             ctx.close()
+
+
+def decompress_range(blob: bytes, off: int, n: int, device: int = 0) -> bytes:
+    """decoded bytes [off, off + n) of a whole FCX7 or FCX8 file with the GPU decoder: only the
+    records the range touches are expanded"""
+    ctx = DContext(device)
+    try:
+        return ctx.decompress_range_host(blob, off, n)
+    finally:
+        ctx.close()
 
 
 def my_compress_file_lz77(block: bytes) -> bytes:

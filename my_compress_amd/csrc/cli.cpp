@@ -14,6 +14,11 @@
 // output).  `-c lz78` runs the LZ78 codec (FCX8) on the GPU: 256 MiB shards
 // through fcx_lz78_compress_host; an FCX8 file decompresses through
 // fcx_decompress_stream like an FCX7 one (GPU-only: no host decoder for FCX8).
+// Random access, decompress mode only (a usage error with -c, or both together):
+//   --range OFF:LEN   writes only the decoded bytes [OFF, OFF + LEN) to -o (fcx_decompress_range_stream:
+//                     only the records the range touches are expanded, nothing behind it is read)
+//   --list            one line per record (numbered from 0): compressed, decoded bytes, decoded offset
+// Without a HIP device both run on the host decoder for FCX7 and fail for FCX8, as decompress does.
 #include <getopt.h>
 
 #include <chrono>
@@ -26,12 +31,13 @@
 #include <hip/hip_runtime.h>
 
 #include "fcx.h"
+#include "fcx_cli_host.h"
 
 static int usage() {
     fprintf(stderr,
             "usage: ./my_compress -i[or --file_in] <input file name> [-o[or --file_out] <output file name>] "
             "[-c (or --compress) <lz77/lz78>] [-b (or --block) <bytes>] [-d (or --device) <hip device>] "
-            "[-g (or --gpus) <count>]\n");
+            "[-g (or --gpus) <count>] [--range <offset>:<length> | --list (decompress only)]\n");
     return -1;
 }
 
@@ -142,36 +148,13 @@ static int report(uint64_t got_total, uint32_t total) {
 
 // host decoder, used when no HIP device is present
 static int decompress_host(FILE *fin, FILE *fout, uint32_t total, uint16_t nblocks) {
-    std::vector<uint8_t> payload, plain(FCX_MAX_BLOCK_BYTES + 8);
     uint64_t got_total = 0;
-    // bytes left in the file bound every record length before anything is sized from it
-    const long here = ftell(fin);
-    uint64_t left = UINT64_MAX;
-    if (here >= 0 && fseek(fin, 0, SEEK_END) == 0) {
-        const long end = ftell(fin);
-        if (end >= here) left = (uint64_t)(end - here);
-        if (fseek(fin, here, SEEK_SET) != 0) return -1;
-    }
-    for (uint32_t b = 0; b < nblocks; b++) {
-        uint32_t sz = 0;
-        if (left < 4 || fread(&sz, 4, 1, fin) != 1) return -1;
-        if (left != UINT64_MAX) left -= 4;
-        if (sz > left) {
-            fprintf(stderr, "block %u: record of %u bytes runs past the end of the file\n", b + 1, sz);
-            return -1;
-        }
-        if (left != UINT64_MAX) left -= sz;
-        payload.resize(sz);
-        if (fread(payload.data(), 1, sz, fin) != sz) return -1;
-        int64_t n = fcx_decompress_block(payload.data(), sz, plain.data(), plain.size());
-        if (n < 0) {
-            fprintf(stderr, "block %u: %s\n", b + 1, n == FCX_ERR_FORMAT ? "malformed" : "decode error");
-            return -1;
-        }
-        fwrite(plain.data(), 1, (size_t)n, fout);
-        got_total += (uint64_t)n;
-    }
-    return report(got_total, total);
+    const int r = fcx_cli::host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        fwrite(plain, 1, (size_t)n, fout);
+        got_total += n;
+        return true;
+    });
+    return r ? r : report(got_total, total);
 }
 
 // FCX8 (-c lz78): 256 MiB shards of whole blocks, each through the GPU codec
@@ -215,7 +198,76 @@ static int compress_lz78(FILE *fin, FILE *fout, uint32_t block) {
     return 0;
 }
 
-static int do_decompress(FILE *fin, FILE *fout, int device) {
+// what the decompress mode does: everything, a byte range of the decoded file, or the record list
+struct Want {
+    bool range = false, list = false;
+    uint64_t off = 0, len = 0;
+};
+
+static int range_done(uint64_t n, uint64_t off) {
+    printf("range decompress bytes = %llu (offset %llu)\n", (unsigned long long)n, (unsigned long long)off);
+    return 0;
+}
+
+// --list on the GPU: the records in groups (as fcx_decompress_stream forms them: <= 256 records and
+// <= 128 MiB), each indexed on the device by fcx_index_shard.  An FCX7 file is read to its end, of
+// an FCX8 file the header's counted records.
+static int list_gpu(FILE *fin, fcx_dctx *d, char kind, uint16_t counted) {
+    constexpr uint32_t kGroup = 256;
+    constexpr uint64_t kBytes = 128ull << 20;
+    std::vector<uint8_t> buf;
+    std::vector<uint64_t> rec(kGroup + 1), dec(kGroup + 1);
+    uint8_t *d_in = nullptr;
+    uint64_t *d_idx = nullptr, d_cap = 0;
+    uint64_t left = kind == '7' ? UINT64_MAX : counted, k0 = 0, pos = 0, comp = 0;
+    int rc = 0;
+    if (hipMalloc((void **)&d_idx, 16 * (kGroup + 1)) != hipSuccess) return -1;
+    bool eof = false;
+    while (!eof && left && rc == 0) {
+        buf.clear();
+        uint32_t nb = 0;
+        while (nb < kGroup && left && buf.size() < kBytes) {
+            uint32_t sz = 0;
+            const size_t g = fread(&sz, 1, 4, fin);
+            if (g == 0 && kind == '7') { eof = true; break; }
+            if (g != 4 || sz > 10ull * FCX_MAX_BLOCK_BYTES + 4096) { fprintf(stderr, "truncated block record\n"); rc = -1; break; }
+            const size_t at = buf.size();
+            buf.resize(at + 4 + sz);
+            memcpy(buf.data() + at, &sz, 4);
+            if (fread(buf.data() + at + 4, 1, sz, fin) != sz) { fprintf(stderr, "truncated block record\n"); rc = -1; break; }
+            nb++;
+            left--;
+        }
+        if (rc || nb == 0) break;
+        if (buf.size() > d_cap) {
+            (void)hipFree(d_in);
+            d_in = nullptr;
+            d_cap = buf.size();
+            if (hipMalloc((void **)&d_in, d_cap) != hipSuccess) { fprintf(stderr, "fcx: hipMalloc failed\n"); rc = -1; break; }
+        }
+        uint64_t total = 0;
+        if (hipMemcpy(d_in, buf.data(), buf.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            fcx_index_shard(d, kind, d_in, buf.size(), nb, d_idx, d_idx + kGroup + 1, &total, nullptr) != FCX_OK ||
+            hipMemcpy(rec.data(), d_idx, 8 * (nb + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(dec.data(), d_idx + kGroup + 1, 8 * (nb + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            rc = -1;
+            break;
+        }
+        for (uint32_t k = 0; k < nb; k++) {
+            fcx_cli::list_line(k0 + k, rec[k + 1] - rec[k] - 4, dec[k + 1] - dec[k], pos + dec[k]);
+            comp += rec[k + 1] - rec[k] - 4;
+        }
+        k0 += nb;
+        pos += total;
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_idx);
+    if (rc == 0) fcx_cli::list_totals(k0, comp, pos);
+    return rc;
+}
+
+static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
         fprintf(stderr, "Read file head infomation error!!!\n");
@@ -235,13 +287,37 @@ static int do_decompress(FILE *fin, FILE *fout, int device) {
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        if (want.list) return fcx_cli::host_list(fin, nblocks);
+        if (want.range) {
+            uint64_t n = 0;
+            const int r = fcx_cli::host_range(fin, fout, nblocks, want.off, want.len, &n);
+            return r ? r : range_done(n, want.off);
+        }
         return decompress_host(fin, fout, total, nblocks);
+    }
+    if (want.list) {
+        const int r = list_gpu(fin, d, kind == '7' ? '7' : '8', nblocks);
+        fcx_dctx_destroy(d);
+        return r;
     }
     // GPU decoder over whole records, FCX7 and FCX8 alike (the stream path re-reads the header)
     rewind(fin);
     Files io{fin, fout};
     uint64_t got_total = 0, nrec = 0;
     uint32_t htotal = 0;
+    if (want.range) {
+        // the file's size bounds the staging: a small file does not pin a whole group's buffers
+        uint64_t max_in = 0;
+        if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+        rewind(fin);
+        const int r = fcx_decompress_range_stream(d, files_read, files_write, &io, max_in, want.off, want.len, &got_total);
+        fcx_dctx_destroy(d);
+        if (r) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        return range_done(got_total, want.off);
+    }
     const int r = fcx_decompress_stream(d, files_read, files_write, &io, 0, &htotal, &got_total, &nrec);
     fcx_dctx_destroy(d);
     if (r) {
@@ -258,12 +334,15 @@ int main(int argc, char **argv) {
                                            {"block", required_argument, nullptr, 'b'},
                                            {"device", required_argument, nullptr, 'd'},
                                            {"gpus", required_argument, nullptr, 'g'},
+                                           {"range", required_argument, nullptr, 'R'},
+                                           {"list", no_argument, nullptr, 'L'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
     uint32_t block = FCX_DEFAULT_BLOCK_BYTES;
     int device = 0, ngpus = 1, opt;
     bool dist = false;   // -g given: the RCCL multi-GPU path (also at -g 1)
+    Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
         switch (opt) {
@@ -276,18 +355,24 @@ int main(int argc, char **argv) {
         case 'b': block = (uint32_t)strtoul(optarg, nullptr, 0); break;
         case 'd': device = atoi(optarg); break;
         case 'g': ngpus = atoi(optarg); dist = true; break;
+        case 'R':
+            if (!fcx_cli::parse_range(optarg, &want.off, &want.len)) return usage();
+            want.range = true;
+            break;
+        case 'L': want.list = true; break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
+    if ((want.range || want.list) && (compress || (want.range && want.list))) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    FILE *fout = fopen(file_out.c_str(), "wb");
-    if (!fout) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
+    FILE *fout = want.list ? nullptr : fopen(file_out.c_str(), "wb");   // (--list writes no file)
+    if (!fout && !want.list) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
     if (compress && !lz77 && hipSetDevice(device) != hipSuccess) {
         fprintf(stderr, "fcx: no HIP device %d\n", device);
@@ -296,8 +381,8 @@ int main(int argc, char **argv) {
     const int r = compress ? (lz77 ? (dist ? do_compress_dist(fin, fout, block, device, ngpus)
                                                                   : do_compress(fin, fout, block, device))
                                    : compress_lz78(fin, fout, block))
-                           : do_decompress(fin, fout, device);
+                           : do_decompress(fin, fout, device, want);
     fclose(fin);
-    fclose(fout);
+    if (fout) fclose(fout);
     return r;
 }

@@ -1,0 +1,121 @@
+// fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
+// (fcx_decode.cpp) record by record, for the whole decompress, --list and --range.  Host code only
+// (stdio and fcx_decompress_block), so it also builds into a stand-alone program (tools/range_host_check.cpp).
+#ifndef FCX_CLI_HOST_H
+#define FCX_CLI_HOST_H
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "fcx.h"
+
+namespace fcx_cli {
+
+// "OFF:LEN", two unsigned decimal numbers; false for anything else
+inline bool parse_range(const char *s, uint64_t *off, uint64_t *len) {
+    uint64_t v[2];
+    for (int i = 0; i < 2; i++) {
+        if (*s < '0' || *s > '9') return false;
+        uint64_t x = 0;
+        for (; *s >= '0' && *s <= '9'; s++) {
+            if (x > (UINT64_MAX - (uint64_t)(*s - '0')) / 10) return false;
+            x = 10 * x + (uint64_t)(*s - '0');
+        }
+        v[i] = x;
+        if (*s != (i == 0 ? ':' : '\0')) return false;
+        s++;
+    }
+    *off = v[0];
+    *len = v[1];
+    return true;
+}
+
+// The nblocks records behind the header of an FCX7 file, each through the host decoder:
+// fn(k, payload bytes, decoded bytes, their count) -> false ends the walk early.  0, or -1 after a
+// message on stderr (a record past the end of the file, a malformed block).
+template <typename Fn>
+int host_each_record(FILE *fin, uint16_t nblocks, Fn fn) {
+    std::vector<uint8_t> payload, plain(FCX_MAX_BLOCK_BYTES + 8);
+    // bytes left in the file bound every record length before anything is sized from it
+    const long here = ftell(fin);
+    uint64_t left = UINT64_MAX;
+    if (here >= 0 && fseek(fin, 0, SEEK_END) == 0) {
+        const long end = ftell(fin);
+        if (end >= here) left = (uint64_t)(end - here);
+        if (fseek(fin, here, SEEK_SET) != 0) return -1;
+    }
+    for (uint32_t b = 0; b < nblocks; b++) {
+        uint32_t sz = 0;
+        if (left < 4 || fread(&sz, 4, 1, fin) != 1) return -1;
+        if (left != UINT64_MAX) left -= 4;
+        if (sz > left) {
+            fprintf(stderr, "block %u: record of %u bytes runs past the end of the file\n", b + 1, sz);
+            return -1;
+        }
+        if (left != UINT64_MAX) left -= sz;
+        payload.resize(sz);
+        if (fread(payload.data(), 1, sz, fin) != sz) return -1;
+        const int64_t n = fcx_decompress_block(payload.data(), sz, plain.data(), plain.size());
+        if (n < 0) {
+            fprintf(stderr, "block %u: %s\n", b + 1, n == FCX_ERR_FORMAT ? "malformed" : "decode error");
+            return -1;
+        }
+        if (!fn(b, sz, (const uint8_t *)plain.data(), (uint64_t)n)) break;
+    }
+    return 0;
+}
+
+inline void list_line(uint64_t k, uint64_t comp, uint64_t dec, uint64_t dec_off) {
+    printf("record %llu: compressed %llu bytes, decoded %llu bytes, decoded offset %llu\n", (unsigned long long)k,
+           (unsigned long long)comp, (unsigned long long)dec, (unsigned long long)dec_off);
+}
+inline void list_totals(uint64_t records, uint64_t comp, uint64_t dec) {
+    printf("records = %llu, compressed bytes = %llu, decoded bytes = %llu\n", (unsigned long long)records,
+           (unsigned long long)comp, (unsigned long long)dec);
+}
+
+// --list without a device
+inline int host_list(FILE *fin, uint16_t nblocks) {
+    uint64_t pos = 0, comp = 0, nrec = 0;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t k, uint32_t sz, const uint8_t *, uint64_t n) {
+        list_line(k, sz, n, pos);
+        pos += n;
+        comp += sz;
+        nrec++;
+        return true;
+    });
+    if (r) return r;
+    list_totals(nrec, comp, pos);
+    return 0;
+}
+
+// --range without a device: the decoded bytes [off, off + len) to fout; records behind the range
+// are not read
+inline int host_range(FILE *fin, FILE *fout, uint16_t nblocks, uint64_t off, uint64_t len, uint64_t *written) {
+    const uint64_t end = len < UINT64_MAX - off ? off + len : UINT64_MAX;
+    uint64_t pos = 0, out = 0;
+    bool io_ok = true;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        const uint64_t a = off > pos ? off - pos : 0, b = end - pos < n ? end - pos : n;   // this record's part
+        if (a < b) {
+            io_ok = fwrite(plain + a, 1, (size_t)(b - a), fout) == b - a;
+            out += b - a;
+        }
+        pos += n;
+        return io_ok && pos < end;
+    });
+    if (r) return r;
+    if (!io_ok) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    *written = out;
+    return 0;
+}
+
+}  // namespace fcx_cli
+
+#endif  // FCX_CLI_HOST_H

@@ -29,6 +29,13 @@
 //             and copy links (x -> x - p), and resolves the links by pointer
 //             jumping against the tile and the 2 KiB history before it.
 //
+// The range API (fcx_range.hip) runs two more passes over the same kernels: the size
+// pass (dec7_sizes) decodes only the flags and the Golomb bytes (k_dhead and k_dscan give only those
+// room in the symbol scratch, k_dsel lists their descriptors for k_dtable and k_dsyms), stops behind
+// k_dlen and hands the sizes out (k_dsizes_out); the range decode (dec7_range) runs every stage on a
+// sub-run, checks the sizes against the index (k_dcheck_sizes) and expands with k_dlz_clip, k_dlz's
+// body with a clip window.
+//
 // The bit reader, the table probes, the segment decoder and the block scan are in
 // fcx_dec_shared.h, which the FCX8 decoder (fcx_lz78_dec.hip) includes as well; it also
 // runs k_dtable and k_dsyms on its char streams (dec_launch_tables8 / dec_launch_syms8).
@@ -115,8 +122,9 @@ __device__ bool parse_sub(HCursor &c, DStream &s, uint32_t count) {
 }
 
 // one thread per block: payload header (my_decompress_file_lz77 2255-2330)
+// smask (kAllStreams, kSizeStreams): the sub-streams that get room in the symbol scratch
 __global__ void k_dhead(const uint8_t *in, uint32_t nblocks, DBlock *blk, DStream *ds, uint64_t *symb,
-                        uint32_t *err) {
+                        uint32_t smask, uint32_t *err) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nblocks) return;
     if (*err & kDErrRecord) return;
@@ -165,12 +173,14 @@ __global__ void k_dhead(const uint8_t *in, uint32_t nblocks, DBlock *blk, DStrea
     }
     B.N = N; B.nb = nb; B.pcnt = pcnt; B.G = G; B.pbytes = pbytes;
     auto a4 = [](uint64_t x) { return (x + 3) & ~3ull; };
-    symb[b] = a4(nb) + a4(N) + a4(pbytes) + 4ull * G;
+    symb[b] = (smask & 1u ? a4(nb) : 0) + (smask & 2u ? a4(N) : 0) + (smask & 4u ? a4(pbytes) : 0) +
+              (smask & 8u ? 4ull * G : 0);
 }
 
 // exclusive scans over blocks (one workgroup, sequential chunks): symbol bytes,
 // golomb values; sets DStream.dst and DBlock.sym_off / glen_off; totals out
-__global__ void k_dscan(uint32_t nblocks, DBlock *blk, DStream *ds, const uint64_t *symb, uint64_t *totals) {
+__global__ void k_dscan(uint32_t nblocks, DBlock *blk, DStream *ds, const uint64_t *symb, uint32_t smask,
+                        uint64_t *totals) {
     __shared__ uint64_t sh[2][1024 / 64];
     __shared__ uint64_t carry[2];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -205,10 +215,10 @@ __global__ void k_dscan(uint32_t nblocks, DBlock *blk, DStream *ds, const uint64
             B.glen_off = pre[1];
             auto a4 = [](uint64_t x) { return (x + 3) & ~3ull; };
             DStream *s = ds + 4ull * b;
-            s[0].dst = pre[0];
-            s[1].dst = pre[0] + a4(B.nb);
-            s[2].dst = s[1].dst + a4(B.N);
-            s[3].dst = s[2].dst + a4(B.pbytes);
+            s[0].dst = pre[0];   // (a sub-stream outside smask has no room: it is not decoded)
+            s[1].dst = s[0].dst + (smask & 1u ? a4(B.nb) : 0);
+            s[2].dst = s[1].dst + (smask & 2u ? a4(B.N) : 0);
+            s[3].dst = s[2].dst + (smask & 4u ? a4(B.pbytes) : 0);
         }
         __syncthreads();
         if (tid == 0) { carry[0] += tot[0]; carry[1] += tot[1]; }
@@ -523,9 +533,14 @@ __device__ inline uint32_t block_xmax(uint32_t v, uint32_t *sh) {   // exclusive
     return ex;
 }
 
-__global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_dlz(uint32_t nblocks, const DBlock *blk, const DStream *ds,
-                                                     const uint8_t *sym, const uint32_t *glen, uint8_t *out,
-                                                     uint32_t *err) {
+// kClip (a range decode, k_dlz_clip): only the decoded bytes [w.lo, w.hi) of the run are stored, byte
+// w.lo at out[0]; a block is still expanded from its first token (a link reaches back 2047 bytes),
+// but its step loop ends at the first step boundary at or past w.hi, and a block outside the window
+// is not expanded.  *stored counts the bytes stored.
+template <bool kClip>
+__device__ __forceinline__ void dlz_body(uint32_t nblocks, const DBlock *blk, const DStream *ds, const uint8_t *sym,
+                                         const uint32_t *glen, uint8_t *out, uint32_t *err, DClip w,
+                                         unsigned long long *stored) {
     __shared__ uint8_t ob[kHist + kDLzTile];              // [history | this step's bytes]
     __shared__ __attribute__((aligned(16))) uint32_t lk[kDLzTile];   // token marks, then links / bytes
     __shared__ uint2 tr[kDLzTPT * kDLzThreads];                 // this step's tokens: off | L << 13 | ism << 22 | ok << 23, P | c << 16
@@ -540,11 +555,31 @@ __global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))
     const uint8_t *pb = sym + ds[4ull * b + 2].dst;
     const uint32_t *gl = glen + B.glen_off;
     uint8_t *o = out + B.out_off;
+    // kClip: block bytes [clo, chi) are in the window; byte x of them goes to out[ob0 + x]
+    uint32_t clo = 0, chi = 0;
+    int64_t ob0 = 0;
+    if (kClip) {
+        if (B.out_off >= w.hi || B.out_off + B.out_len <= w.lo) return;   // (the whole workgroup)
+        clo = w.lo > B.out_off ? (uint32_t)(w.lo - B.out_off) : 0u;
+        chi = (uint32_t)min((uint64_t)B.out_len, w.hi - B.out_off);
+        ob0 = (int64_t)B.out_off - (int64_t)w.lo;
+    }
+    auto put = [&](uint32_t x, uint8_t v) {   // decoded byte x of the block
+        if (!kClip) o[x] = v;
+        else if (x >= clo && x < chi) out[ob0 + x] = v;
+    };
+    auto count = [&](uint32_t x0, uint32_t n) {   // kClip: bytes [x0, x0 + n) are done
+        if (kClip && tid == 0) {
+            const uint32_t a = max(x0, clo), e = min(x0 + n, chi);
+            if (e > a) atomicAdd(stored, (unsigned long long)(e - a));
+        }
+    };
     const uint32_t n_eff = B.n_eff;
     uint32_t tc = 0, mc = 0, oc = 0;
     uint32_t window = kDLzTPT * kDLzThreads;   // tokens read per step, adapted to the token length seen
     bool bad = false;
     while (tc < n_eff) {
+        if (kClip && oc >= chi) break;   // the window ends before this step
         const uint32_t limit = min(n_eff, tc + window);
         uint32_t len[kDLzTPT], L[kDLzTPT], P[kDLzTPT], c[kDLzTPT];
         bool ism[kDLzTPT], valid[kDLzTPT];
@@ -564,7 +599,8 @@ __global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))
             const uint32_t cnt = limit - tc;
 #pragma unroll
             for (uint32_t u = 0; u < kDLzTPT; u++)
-                if (valid[u]) o[oc + kDLzTPT * tid + u] = (uint8_t)c[u];
+                if (valid[u]) put(oc + kDLzTPT * tid + u, (uint8_t)c[u]);
+            count(oc, cnt);
             // history = the last 2 KiB of [history | these bytes]
             uint8_t h[kHist / kDLzThreads];
 #pragma unroll
@@ -675,8 +711,9 @@ __global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))
         for (uint32_t x = tid; x < used; x += kDLzThreads) {
             const uint8_t v = (uint8_t)lk[x];
             ob[kHist + x] = v;
-            o[oc + x] = v;
+            put(oc + x, v);
         }
+        count(oc, used);
         __syncthreads();
         // history = the last 2 KiB of [history | step bytes]
         const uint8_t h0 = ob[used + tid], h1 = ob[used + tid + kDLzThreads];
@@ -694,15 +731,50 @@ __global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))
     if (bad) atomicOr(err, kDErrDist);
 }
 
+__global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_dlz(uint32_t nblocks, const DBlock *blk, const DStream *ds,
+                                                     const uint8_t *sym, const uint32_t *glen, uint8_t *out,
+                                                     uint32_t *err) {
+    dlz_body<false>(nblocks, blk, ds, sym, glen, out, err, DClip{}, nullptr);
+}
+
+__global__ __launch_bounds__(kDLzThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_dlz_clip(uint32_t nblocks, const DBlock *blk, const DStream *ds,
+                                                          const uint8_t *sym, const uint32_t *glen, uint8_t *out,
+                                                          uint32_t *err, DClip w, unsigned long long *stored) {
+    dlz_body<true>(nblocks, blk, ds, sym, glen, out, err, w, stored);
+}
+
+// ---- the size pass and the range decode (fcx_range.hip) ----
+// the size pass's list of sub-streams to decode: sel[2b] = block b's flags, sel[2b + 1] = its Golomb
+// bytes, the rest of the nsel entries (a multiple of 4, as k_dtable and k_dsyms count) empty
+__global__ void k_dsel(uint32_t nblocks, uint32_t nsel, const DStream *ds, DStream *sel) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= nsel) return;
+    DStream s{};
+    s.raw = 1;
+    if (x < 2 * nblocks) s = ds[4ull * (x >> 1) + 3 * (x & 1)];
+    sel[x] = s;
+}
+
+// thread per block: the size pass's results as plain arrays (payload offset and length, decoded size)
+__global__ void k_dsizes_out(uint32_t nblocks, const DBlock *blk, uint64_t *roff, uint32_t *rlen, uint32_t *dsize) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nblocks) return;
+    roff[b] = blk[b].payload_off;
+    rlen[b] = blk[b].payload_len;
+    dsize[b] = blk[b].out_len;
+}
+
+// thread per block of a sub-run: its decoded size against the index's (dec_off: the sub-run's first entry)
+__global__ void k_dcheck_sizes(uint32_t nblocks, const DBlock *blk, const uint64_t *dec_off, uint32_t *err) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nblocks || *err) return;
+    if (dec_off[b + 1] - dec_off[b] != (uint64_t)blk[b].out_len) atomicOr(err, kDErrIndex);
+}
+
+// the full decode's stages behind the header pass (dec7_heads)
 void dec_launch(const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out, uint64_t cap, DBlock *blk,
-                DStream *ds, uint64_t *symb, uint16_t *tbl, uint16_t *child, uint8_t *sym, uint32_t *glen,
-                uint64_t *words, uint32_t *err, int phase, hipStream_t st, hipEvent_t *ev) {
-    if (phase == 0) {
-        hipLaunchKernelGGL(k_dindex, dim3(1), dim3(1), 0, st, d_in, in_len, nblocks, blk, err);
-        hipLaunchKernelGGL(k_dhead, dim3((nblocks + 255) / 256), dim3(256), 0, st, d_in, nblocks, blk, ds, symb, err);
-        hipLaunchKernelGGL(k_dscan, dim3(1), dim3(1024), 0, st, nblocks, blk, ds, symb, words + kDwSymBytes);
-        return;
-    }
+                DStream *ds, uint16_t *tbl, uint16_t *child, uint8_t *sym, uint32_t *glen, uint64_t *words,
+                uint32_t *err, hipStream_t st, hipEvent_t *ev) {
     auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], st); };
     mark(0);
     hipLaunchKernelGGL(k_dtable, dim3(4 * nblocks), dim3(64), 0, st, d_in, nblocks, ds, tbl, child, err, (uint32_t *)nullptr);
@@ -729,6 +801,93 @@ void dec_launch_syms8(const uint8_t *d_in, uint64_t in_len, uint32_t nstreams, c
                       uint64_t *stats, hipStream_t st) {
     hipLaunchKernelGGL(k_dsyms, dim3(nstreams), dim3(kDSymThreads), 0, st, d_in, in_len, nstreams / 4, ds, tbl, child, sym,
                        err, stats);
+}
+
+// The scratch per block of a call, the record walk, the header pass and the scratch offsets of the
+// sub-streams of smask; waits for the stream to size the symbol scratch from the totals.
+static int dec7_heads(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint32_t smask, hipStream_t st) {
+    Dec7 &D = c->d7;
+    if (nblocks > D.cap_blocks) {
+        static_cast<Dec7Blocks &>(D) = Dec7Blocks{};   // (the old scratch goes before the new is made)
+        FCX_TRY(D.blk.reserve(sizeof(DBlock) * (uint64_t)nblocks, "blocks"));
+        FCX_TRY(D.ds.reserve(sizeof(DStream) * 4ull * nblocks, "streams"));
+        FCX_TRY(D.ds_sel.reserve(sizeof(DStream) * (2ull * nblocks + 4), "size pass streams"));
+        FCX_TRY(D.symb.reserve(8ull * nblocks, "symb"));
+        FCX_TRY(D.tbl.reserve(2048ull * 4 * nblocks, "tables"));
+        FCX_TRY(D.child.reserve(1024ull * 4 * nblocks, "children"));
+        D.cap_blocks = nblocks;
+    }
+    uint64_t *hw = D.host_words;
+    uint32_t *err = (uint32_t *)(D.words + kDwErr);
+    memset(hw + kDwStats, 0, kSsWords * sizeof(uint64_t));
+    FCX_HIP(hipMemsetAsync(D.words, 0, 8 * kDwWords, st));
+    hipLaunchKernelGGL(k_dindex, dim3(1), dim3(1), 0, st, d_in, in_len, nblocks, D.blk, err);
+    hipLaunchKernelGGL(k_dhead, dim3((nblocks + 255) / 256), dim3(256), 0, st, d_in, nblocks, D.blk, D.ds, D.symb, smask, err);
+    hipLaunchKernelGGL(k_dscan, dim3(1), dim3(1024), 0, st, nblocks, D.blk, D.ds, D.symb, smask, D.words + kDwSymBytes);
+    FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * (kDwGolombVals + 1), hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    if ((uint32_t)hw[kDwErr] & (kDErrRecord | kDErrHeader)) return fail(FCX_ERR_FORMAT, "malformed block records / headers");
+    FCX_TRY(D.sym.reserve(hw[kDwSymBytes] + 64, "symbols"));
+    FCX_TRY(D.glen.reserve(4 * hw[kDwGolombVals] + 64, "golomb values"));
+    return FCX_OK;
+}
+
+// the stages every pass runs on the sub-streams of smask, up to the decoded sizes (k_dlen)
+static void dec7_launch_sizes(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint32_t smask,
+                              hipStream_t st) {
+    Dec7 &D = c->d7;
+    uint32_t *err = (uint32_t *)(D.words + kDwErr);
+    // tables and symbols of the sub-streams of smask: of all four in place, or of the flags and the
+    // Golomb bytes through a list of just those descriptors (k_dsel), the way the FCX8 decoder hands
+    // its char streams to the same two kernels
+    const DStream *ds = D.ds;
+    uint32_t nstreams = 4 * nblocks;
+    if (smask != kAllStreams) {
+        nstreams = (2 * nblocks + 3) & ~3u;
+        hipLaunchKernelGGL(k_dsel, dim3((nstreams + 255) / 256), dim3(256), 0, st, nblocks, nstreams, D.ds, D.ds_sel);
+        ds = D.ds_sel;
+    }
+    hipLaunchKernelGGL(k_dtable, dim3(nstreams), dim3(64), 0, st, d_in, nstreams / 4, ds, D.tbl, D.child, err,
+                       (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_dsyms, dim3(nstreams), dim3(kDSymThreads), 0, st, d_in, in_len, nstreams / 4, ds, D.tbl, D.child,
+                       D.sym, err, D.words + kDwStats);
+    hipLaunchKernelGGL(k_dgolomb, dim3(nblocks), dim3(kDSymThreads), 0, st, nblocks, D.blk, D.ds, D.sym, D.glen, err,
+                       D.words + kDwStats);
+    hipLaunchKernelGGL(k_dlen, dim3(nblocks), dim3(256), 0, st, nblocks, D.blk, D.sym, D.glen, err);
+}
+
+static int dec7_verdict(fcx_dctx *c, hipStream_t st) {
+    Dec7 &D = c->d7;
+    FCX_HIP(hipGetLastError());
+    FCX_HIP(hipMemcpyAsync(D.host_words, D.words, 8 * kDwWords, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    const uint32_t e = (uint32_t)D.host_words[kDwErr];
+    if (e & kDErrIndex) return fail(FCX_ERR_FORMAT, "the index disagrees with the run: a touched record's decoded size differs");
+    if (e) return fail(FCX_ERR_FORMAT, "malformed stream (decoder error bits " + std::to_string(e) + ")");
+    return FCX_OK;
+}
+
+int dec7_sizes(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint64_t *d_roff, uint32_t *d_rlen,
+               uint32_t *d_dsize, hipStream_t st) {
+    FCX_TRY(dec7_heads(c, d_in, in_len, nblocks, kSizeStreams, st));
+    dec7_launch_sizes(c, d_in, in_len, nblocks, kSizeStreams, st);
+    hipLaunchKernelGGL(k_dsizes_out, dim3((nblocks + 255) / 256), dim3(256), 0, st, nblocks, c->d7.blk, d_roff, d_rlen, d_dsize);
+    return dec7_verdict(c, st);
+}
+
+int dec7_range(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, const uint64_t *d_dec_off, DClip w,
+               uint8_t *d_out, hipStream_t st, uint64_t *stored) {
+    Dec7 &D = c->d7;
+    FCX_TRY(dec7_heads(c, d_in, in_len, nblocks, kAllStreams, st));
+    dec7_launch_sizes(c, d_in, in_len, nblocks, kAllStreams, st);
+    uint32_t *err = (uint32_t *)(D.words + kDwErr);
+    hipLaunchKernelGGL(k_dscan_out, dim3(1), dim3(1024), 0, st, nblocks, D.blk, ~0ull, D.words, err);
+    hipLaunchKernelGGL(k_dcheck_sizes, dim3((nblocks + 255) / 256), dim3(256), 0, st, nblocks, D.blk, d_dec_off, err);
+    hipLaunchKernelGGL(k_dlz_clip, dim3(nblocks), dim3(kDLzThreads), 0, st, nblocks, D.blk, D.ds, D.sym, D.glen, d_out, err, w,
+                       (unsigned long long *)(D.words + kDwStored));
+    FCX_TRY(dec7_verdict(c, st));
+    *stored = D.host_words[kDwStored];
+    return FCX_OK;
 }
 
 }  // namespace fcx
@@ -791,29 +950,11 @@ int fcx_decompress_shard(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint
         return FCX_OK;
     }
     Dec7 &D = c->d7;
-    if (nblocks > D.cap_blocks) {
-        static_cast<Dec7Blocks &>(D) = Dec7Blocks{};   // (the old scratch goes before the new is made)
-        FCX_TRY(D.blk.reserve(sizeof(DBlock) * (uint64_t)nblocks, "blocks"));
-        FCX_TRY(D.ds.reserve(sizeof(DStream) * 4ull * nblocks, "streams"));
-        FCX_TRY(D.symb.reserve(8ull * nblocks, "symb"));
-        FCX_TRY(D.tbl.reserve(2048ull * 4 * nblocks, "tables"));
-        FCX_TRY(D.child.reserve(1024ull * 4 * nblocks, "children"));
-        D.cap_blocks = nblocks;
-    }
+    FCX_TRY(dec7_heads(c, d_in, in_len, nblocks, kAllStreams, st));
     uint64_t *hw = D.host_words;
     uint32_t *err = (uint32_t *)(D.words + kDwErr);
-    memset(hw + kDwStats, 0, kSsWords * sizeof(uint64_t));   // fcx_dctx_symbol_stats: this call's counters only
-    FCX_HIP(hipMemsetAsync(D.words, 0, 8 * kDwWords, st));
-    dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.symb, D.tbl, D.child, D.sym, D.glen, D.words, err, 0, st,
-               nullptr);
-    // k_dscan left the scratch totals next to the error bits
-    FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * (kDwGolombVals + 1), hipMemcpyDeviceToHost, st));
-    FCX_HIP(hipStreamSynchronize(st));
-    if ((uint32_t)hw[kDwErr] & (kDErrRecord | kDErrHeader)) return fail(FCX_ERR_FORMAT, "malformed block records / headers");
-    FCX_TRY(D.sym.reserve(hw[kDwSymBytes] + 64, "symbols"));
-    FCX_TRY(D.glen.reserve(4 * hw[kDwGolombVals] + 64, "golomb values"));
     if (c->profiling) c->times.publish(kDStageNames, kDStages, true);
-    dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.symb, D.tbl, D.child, D.sym, D.glen, D.words, err, 1, st,
+    dec_launch(d_in, in_len, nblocks, d_out, cap, D.blk, D.ds, D.tbl, D.child, D.sym, D.glen, D.words, err, st,
                c->profiling ? c->times.events() : nullptr);
     FCX_HIP(hipGetLastError());
     FCX_HIP(hipMemcpyAsync(hw, D.words, 8 * kDwWords, hipMemcpyDeviceToHost, st));

@@ -14,7 +14,18 @@ namespace fcx {
 
 // device error bits of the decoders
 constexpr uint32_t kDErrRecord = 1, kDErrHeader = 2, kDErrTree = 4, kDErrGolomb = 8, kDErrDist = 16,
-                   kDErrOutCap = 32, kDErrScratch = 64;
+                   kDErrOutCap = 32, kDErrScratch = 64,
+                   kDErrIndex = 128;   // a range decode: a touched record's size is not the index's
+
+// the FCX7 sub-streams a pass gives room in the symbol scratch and decodes, bit q = sub-stream q (flags,
+// chars, distances, Golomb bytes): no decoded size depends on the chars or the distances, so the size
+// pass leaves them out
+constexpr uint32_t kAllStreams = 0xFu, kSizeStreams = 0x9u;
+
+// window of a range decode in the decoded bytes of the records being expanded: byte lo goes to d_out[0]
+struct DClip {
+    uint64_t lo = 0, hi = 0;
+};
 
 constexpr uint32_t kDSymThreads = 1024;
 constexpr uint32_t kDTblBits = 10;
@@ -334,8 +345,9 @@ constexpr uint32_t kDwErr = 1;         // error bits (kDErr*), a u32
 constexpr uint32_t kDwSymBytes = 2;    // symbol scratch bytes, and right behind them ...
 constexpr uint32_t kDwGolombVals = 3;  // ... the golomb values (k_dscan's totals[0..1]): they size the scratch
 constexpr uint32_t kDwStats = 4;       // the segment decoder's statistics block (kSs* above)
+constexpr uint32_t kDwStored = 12;     // bytes a range decode stored (k_dlz_clip)
 constexpr uint32_t kDwWords = 16;      // (128 bytes)
-static_assert(kDwStats + kSsWords <= kDwWords, "FCX7 status words");
+static_assert(kDwStats + kSsWords <= kDwStored && kDwStored < kDwWords, "FCX7 status words");
 
 // The 8-bit Huffman sub-streams of ds[0, nstreams) (nstreams a multiple of 4; unused entries raw with
 // count 0): decode tables (k_dtable) and symbols into sym + ds[q].dst (k_dsyms), zeros past a
@@ -355,11 +367,44 @@ constexpr int kD78Stages = 6;     // FCX8 stages (fcx_lz78_dec.hip)
 int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
                              uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
 
+// ---- the two passes of the range API (fcx_range.hip), per codec; DESIGN.md §9c ----
+// Size pass over a run of nblocks records: payload offset and length of every record (the record
+// walk) and its decoded size into three device arrays of nblocks entries.  FCX7 decodes the flags
+// and the Golomb bytes only; FCX8 runs its stages up to the links and skips the expansion.
+int dec7_sizes(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint64_t *d_roff, uint32_t *d_rlen,
+               uint32_t *d_dsize, hipStream_t st);
+int lz78_sizes(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint64_t *d_roff, uint32_t *d_rlen,
+               uint32_t *d_dsize, hipStream_t st);
+// Clipped expansion of the nblocks records at d_in (a sub-run: d_in points at its first length
+// prefix): the decoded bytes [w.lo, w.hi) of the sub-run go to d_out[0, w.hi - w.lo), nothing else
+// is stored.  d_dec_off: the index's nblocks + 1 entries for these records; a record whose decoded
+// size is not dec_off[k + 1] - dec_off[k] fails the call.  Messages number the records from rec_base
+// (FCX8).  *stored: bytes stored.
+int dec7_range(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, const uint64_t *d_dec_off, DClip w,
+               uint8_t *d_out, hipStream_t st, uint64_t *stored);
+int lz78_range(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, const uint64_t *d_dec_off, DClip w,
+               uint8_t *d_out, hipStream_t st, uint64_t rec_base, uint64_t *stored);
+
+// fcx_decompress_range_shard behind its argument checks, for the stream path's groups of a longer
+// run: messages number the records from rec_base, *total (when given) = the run's decoded bytes
+int range_shard(fcx_dctx *c, char kind, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, const uint64_t *d_rec_off,
+                const uint64_t *d_dec_off, uint64_t off, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len,
+                hipStream_t st, uint64_t rec_base, uint64_t *total);
+
+// scratch and counters of the range API (fcx_range.hip)
+struct RangeScratch {
+    DevBuf<uint64_t> roff, rec_off, dec_off;   // per record (+ 1): the size pass's offsets, the call's own index
+    DevBuf<uint32_t> rlen, dsize;
+    DevBuf<uint64_t> words;                    // what k_rlocate found
+    PinnedBuf<uint64_t> host_words;
+    uint64_t stats[FCX_RANGE_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
     DevBuf<DBlock> blk;
-    DevBuf<DStream> ds;
+    DevBuf<DStream> ds, ds_sel;   // (ds_sel: the size pass's list of the flags and Golomb-byte streams)
     DevBuf<uint64_t> symb;
     DevBuf<uint16_t> tbl, child;
 };
@@ -382,6 +427,7 @@ struct fcx_dctx {
     bool profiling = false;
     fcx::Dec7 d7;
     std::unique_ptr<fcx::Scratch78, fcx::Calls<fcx::free_scratch78>> d78;
+    fcx::RangeScratch rg;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

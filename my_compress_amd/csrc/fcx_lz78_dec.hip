@@ -29,6 +29,11 @@
 //                 kLong-th, 2 kLong-th, ... ancestors, copied 64 bytes at a time.
 //
 // Everything is written straight to its final place in the caller's buffer.
+//
+// The range API (fcx_range.hip) runs the same batches with another last step
+// (Pass78): the size pass hands the sizes out behind k78d_scan_out and expands nothing; the range
+// decode checks the sizes against the index and expands with k78d_expand_clip /
+// k78d_expand_long_clip, which store only the bytes of the window.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,8 +75,10 @@ constexpr uint32_t kW8Pindex = 3;      // ... its pindex entries
 constexpr uint32_t kW8BadRec = 4;      // first bad record (1-based, u32; kNone: none)
 constexpr uint32_t kW8BadStream = 5;   // first bad char stream of the batch (u32; kNone: none)
 constexpr uint32_t kW8Stats = 8;       // the segment decoder's statistics block (kSs*, fcx_dec_shared.h)
+constexpr uint32_t kW8Stored = 16;     // bytes a range decode stored (the clipped expansion)
 constexpr uint32_t kWords = 32;
-static_assert(kW8BadStream == kW8BadRec + 1 && kW8Stats + kSsWords <= kWords, "FCX8 status words");
+static_assert(kW8BadStream == kW8BadRec + 1 && kW8Stats + kSsWords <= kW8Stored && kW8Stored < kWords,
+              "FCX8 status words");
 
 // the error word as one value for the whole workgroup (lanes that read it apart could part at a barrier)
 __device__ inline bool wg_err(const uint32_t *err) { return __syncthreads_or(threadIdx.x == 0 && *err != 0); }
@@ -521,6 +528,121 @@ __global__ __launch_bounds__(256) void k78d_expand_long(const DRec *rec, const u
     }
 }
 
+// ---- the range API's passes (fcx_range.hip) ----
+// the size pass: the batch's decoded sizes as a plain array
+__global__ __launch_bounds__(kBatch) void k78d_sizes_out(uint32_t nb, const DRec *rec, uint32_t *dsize) {
+    const uint32_t b = threadIdx.x;
+    if (b < nb) dsize[b] = rec[b].out_len;
+}
+
+// the batch's decoded sizes against the index's (dec_off: the batch's first entry)
+__global__ __launch_bounds__(kBatch) void k78d_check_sizes(uint32_t nb, const DRec *rec, uint32_t r0,
+                                                           const uint64_t *dec_off, uint32_t *err, uint32_t *badrec) {
+    const uint32_t b = threadIdx.x;
+    if (b >= nb || *err) return;
+    if (dec_off[b + 1] - dec_off[b] != (uint64_t)rec[b].out_len) {
+        atomicOr(err, kDErrIndex);
+        atomicMin(badrec, r0 + b + 1);
+    }
+}
+
+// A record's part of the window: its bytes [clo, chi) are stored, byte x at out[ob0 + x].
+struct Clip78 {
+    uint32_t clo, chi;
+    int64_t ob0;
+    __device__ bool set(const DRec &R, const DClip &w) {   // false: the record is outside the window
+        if (R.out >= w.hi || R.out + R.out_len <= w.lo) return false;
+        clo = w.lo > R.out ? (uint32_t)(w.lo - R.out) : 0u;
+        chi = (uint32_t)min((uint64_t)R.out_len, w.hi - R.out);   // (<= out_len: the dropped tail zero stays out)
+        ob0 = (int64_t)R.out - (int64_t)w.lo;
+        return true;
+    }
+};
+
+__device__ inline void wave_count(uint32_t n, unsigned long long *stored) {   // every lane of the wave calls
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(stored, (unsigned long long)n);
+}
+
+// k78d_expand clipped: a token whose phrase misses the window stores nothing and, when its phrase
+// is short, is not walked at all; a long phrase still leaves its kLong-th ancestor in skip[], which
+// the long phrases below it hop over.  The first and last phrase of the window are cut byte-wise.
+__global__ __launch_bounds__(256) void k78d_expand_clip(const DRec *rec, const uint8_t *chr, const uint32_t *par,
+                                                        const uint32_t *pstart, uint32_t *skip, uint8_t *out,
+                                                        const uint32_t *err, DClip w, unsigned long long *stored) {
+    const uint32_t b = blockIdx.y;
+    const DRec R = rec[b];
+    Clip78 cl;
+    if (*err || !R.ok || !cl.set(R, w)) return;
+    const uint8_t *c = chr + R.tok;
+    const uint32_t *pa = par + R.tok;
+    const uint32_t *ps = pstart + R.tok + b;
+    uint32_t n = 0;
+    for (uint32_t t = blockIdx.x * 256 + threadIdx.x; t < R.N; t += gridDim.x * 256) {
+        const uint32_t s = ps[t], e = ps[t + 1], L = e - s;
+        const bool hit = s < cl.chi && e > cl.clo;
+        if (!hit && L <= kLong) continue;
+        const uint32_t steps = min(L, kLong);
+        uint32_t a = t;
+        for (uint32_t k = 0; k < steps; k++) {
+            const uint32_t pos = e - 1 - k;
+            if (hit && pos >= cl.clo && pos < cl.chi) {
+                out[cl.ob0 + pos] = c[a];
+                n++;
+            }
+            if (k + 1 < L) a = pa[a] - 1;
+        }
+        if (L > kLong) skip[R.tok + t] = a;
+    }
+    wave_count(n, stored);
+}
+
+// k78d_expand_long clipped: the ancestors' bytes may lie outside the window, so a piece is not
+// copied from the output: lane i of a piece walks i links up from the piece's ancestor and stores
+// that token's char.  Pieces outside the window are hopped over.
+__global__ __launch_bounds__(256) void k78d_expand_long_clip(const DRec *rec, const uint8_t *chr, const uint32_t *par,
+                                                             const uint32_t *pstart, const uint32_t *skip, uint8_t *out,
+                                                             const uint32_t *err, DClip w, unsigned long long *stored) {
+    const uint32_t b = blockIdx.y;
+    const DRec R = rec[b];
+    Clip78 cl;
+    if (*err || !R.ok || !cl.set(R, w)) return;
+    const uint8_t *c = chr + R.tok;
+    const uint32_t *pa = par + R.tok;
+    const uint32_t *ps = pstart + R.tok + b;
+    const uint32_t *sk = skip + R.tok;
+    const uint32_t lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    uint32_t cnt = 0;
+    for (uint32_t base = wave * 64; base < R.N; base += nwaves * 64) {
+        const uint32_t t = base + lane;
+        const uint32_t s = t < R.N ? ps[t] : 0u, e = t < R.N ? ps[t + 1] : 0u, L = e - s;
+        // the bytes before the last kLong: [s, e - kLong)
+        uint64_t mask = __ballot(L > kLong && s < cl.chi && e - kLong > cl.clo);
+        while (mask) {
+            const int j = __ffsll((unsigned long long)mask) - 1;
+            mask &= mask - 1;
+            uint32_t rem = (uint32_t)__shfl((int)L, j, 64) - kLong;
+            uint32_t dend = (uint32_t)__shfl((int)e, j, 64) - 1 - kLong;   // last byte still to write
+            uint32_t a = sk[base + j];
+            while (rem > 0) {   // a: the ancestor of depth rem; this piece: bytes (dend - n, dend]
+                const uint32_t n = min(rem, kLong);
+                const uint32_t pos = dend - lane;
+                if (lane < n && pos >= cl.clo && pos < cl.chi) {
+                    uint32_t x = a;
+                    for (uint32_t i = 0; i < lane; i++) x = pa[x] - 1;   // (depth rem > lane: the chain holds)
+                    out[cl.ob0 + pos] = c[x];
+                    cnt++;
+                }
+                rem -= n;
+                if (rem == 0 || dend - n < cl.clo) break;   // the rest lies before the window
+                dend -= n;
+                a = sk[a];
+            }
+        }
+    }
+    wave_count(cnt, stored);
+}
+
 }  // namespace fcx78d
 
 // ---------------------------------------------------------------------------
@@ -556,6 +678,8 @@ static int verdict(const Scratch78 *S, uint64_t rec_base, uint32_t batch0) {
     if (!e) return FCX_OK;
     if (e & ~kDErrOutCap) {
         uint64_t k = (uint32_t)S->host_words[kW8BadRec];
+        if (e == kDErrIndex)
+            return fail(FCX_ERR_FORMAT, "fcx_lz78: the index disagrees with the run at record " + std::to_string(rec_base + k));
         const uint32_t q = (uint32_t)S->host_words[kW8BadStream];   // a char tree: its stream's place in the batch
         if (q != kNone) k = std::min<uint64_t>(k, (uint64_t)batch0 + q + 1);
         return fail(FCX_ERR_FORMAT, "fcx_lz78: malformed record " + std::to_string(rec_base + k));
@@ -563,8 +687,16 @@ static int verdict(const Scratch78 *S, uint64_t rec_base, uint32_t batch0) {
     return fail(FCX_ERR_CAPACITY, "fcx_lz78: decoded output exceeds capacity");
 }
 
-int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
-                             uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base) {
+// What a run does with a batch once its links and sizes are known: the expansion (pass == nullptr,
+// the full decode), or one of the range API's passes.
+struct Pass78 {
+    uint32_t *dsize = nullptr;           // size pass: the decoded sizes go here, nothing is expanded
+    const uint64_t *dec_off = nullptr;   // range decode: the index's entries for these records, and ...
+    DClip w;                             // ... the window the clipped expansion stores
+};
+
+static int lz78_run(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out, uint64_t cap,
+                    uint64_t *out_len, hipStream_t st, uint64_t rec_base, const Pass78 *pass) {
     FCX_HIP(hipSetDevice(c->device));
     StageTimes &T = c->times;
     T.reset();
@@ -627,9 +759,20 @@ int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, 
                            S->pstart, err, badrec);
         hipLaunchKernelGGL(k78d_scan_out, dim3(1), dim3(kBatch), 0, st, nb, S->rec, cap, S->words, err);
         mark(5);
-        hipLaunchKernelGGL(k78d_expand, dim3(32, nb), dim3(256), 0, st, S->rec, S->chr, S->par, S->pstart, S->skip, d_out,
-                           err);
-        hipLaunchKernelGGL(k78d_expand_long, dim3(8, nb), dim3(256), 0, st, S->rec, S->pstart, S->skip, d_out, err);
+        if (!pass) {
+            hipLaunchKernelGGL(k78d_expand, dim3(32, nb), dim3(256), 0, st, S->rec, S->chr, S->par, S->pstart, S->skip, d_out,
+                               err);
+            hipLaunchKernelGGL(k78d_expand_long, dim3(8, nb), dim3(256), 0, st, S->rec, S->pstart, S->skip, d_out, err);
+        } else if (pass->dsize) {
+            hipLaunchKernelGGL(k78d_sizes_out, dim3(1), dim3(kBatch), 0, st, nb, S->rec, pass->dsize + r0);
+        } else {
+            unsigned long long *stored = (unsigned long long *)(S->words + kW8Stored);
+            hipLaunchKernelGGL(k78d_check_sizes, dim3(1), dim3(kBatch), 0, st, nb, S->rec, r0, pass->dec_off + r0, err, badrec);
+            hipLaunchKernelGGL(k78d_expand_clip, dim3(32, nb), dim3(256), 0, st, S->rec, S->chr, S->par, S->pstart, S->skip,
+                               d_out, err, pass->w, stored);
+            hipLaunchKernelGGL(k78d_expand_long_clip, dim3(8, nb), dim3(256), 0, st, S->rec, S->chr, S->par, S->pstart,
+                               S->skip, d_out, err, pass->w, stored);
+        }
         mark(6);
         FCX_HIP(hipGetLastError());
         if (prof) FCX_TRY(T.add(1, kD78Stages));
@@ -639,6 +782,35 @@ int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, 
     FCX_TRY(verdict(S, rec_base, (nblocks - 1) / kBatch * kBatch));
     if (prof) T.publish(kD78StageNames, kD78Stages);
     *out_len = hw[kW8Total];
+    return FCX_OK;
+}
+
+int lz78_decompress_shard_at(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint8_t *d_out,
+                             uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base) {
+    return lz78_run(c, d_in, in_len, nblocks, d_out, cap, out_len, st, rec_base, nullptr);
+}
+
+int lz78_sizes(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, uint64_t *d_roff, uint32_t *d_rlen,
+               uint32_t *d_dsize, hipStream_t st) {
+    Pass78 pass;
+    pass.dsize = d_dsize;
+    uint64_t total = 0;
+    FCX_TRY(lz78_run(c, d_in, in_len, nblocks, nullptr, ~0ull, &total, st, 0, &pass));
+    if (nblocks) {   // the record walk's offsets and lengths (k78d_index)
+        FCX_HIP(hipMemcpyAsync(d_roff, c->d78->roff, 8ull * nblocks, hipMemcpyDeviceToDevice, st));
+        FCX_HIP(hipMemcpyAsync(d_rlen, c->d78->rlen, 4ull * nblocks, hipMemcpyDeviceToDevice, st));
+    }
+    return FCX_OK;
+}
+
+int lz78_range(fcx_dctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t nblocks, const uint64_t *d_dec_off, DClip w,
+               uint8_t *d_out, hipStream_t st, uint64_t rec_base, uint64_t *stored) {
+    Pass78 pass;
+    pass.dec_off = d_dec_off;
+    pass.w = w;
+    uint64_t total = 0;
+    FCX_TRY(lz78_run(c, d_in, in_len, nblocks, d_out, ~0ull, &total, st, rec_base, &pass));
+    *stored = nblocks ? c->d78->host_words[kW8Stored] : 0;
     return FCX_OK;
 }
 }  // namespace fcx

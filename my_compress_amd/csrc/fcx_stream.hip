@@ -231,9 +231,18 @@ int fcx_compress_host(fcx_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out,
     return FCX_OK;
 }
 
-int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
-                          uint32_t *hdr_total, uint64_t *total_out, uint64_t *nblocks) {
-    if (!dctx || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_decompress_stream: NULL argument");
+}  // extern "C"
+
+namespace {
+
+constexpr int kStopReading = 1;   // a group function's "the caller has what it wants"
+
+// The reading half of the decompress stream paths: the header, then groups of whole records staged
+// in slot 0 of the pipeline and copied to the device.  group(lz78, slot, bytes, records, out_cap,
+// records before, stream) decodes one; it returns FCX_OK, an error, or kStopReading.
+template <typename Group>
+int stream_groups(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint32_t *hdr_total, uint64_t *nblocks,
+                  Group group) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (read_full(rd, user, hdr, sizeof(hdr)) != (int64_t)sizeof(hdr)) return fail(FCX_ERR_FORMAT, "short header");
     uint32_t total = 0;
@@ -265,7 +274,7 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
     if ((r = get_pipe(1, dev, in_cap, out_cap, &PP))) return r;
     Pipeline &P = *PP;
     Slot &x = P.s[0];
-    uint64_t tout = 0, tblocks = 0;
+    uint64_t tblocks = 0;
     // FCX8: the header's counted records and no more (main() reads block_num records, 4162-4201)
     uint64_t left = lz78 ? counted : ~0ull;
     bool eof = false, have_len = false;
@@ -295,20 +304,78 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
         }
         if (nb == 0) break;
         FCX_HIP(hipMemcpyAsync(x.din, x.hin, used, hipMemcpyHostToDevice, P.scomp));
-        uint64_t got = 0;
-        if (lz78) r = fcx::lz78_decompress_shard_at(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp, tblocks);
-        else r = fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, P.scomp);
+        r = group(lz78, x, used, nb, out_cap, tblocks, P.scomp);
+        tblocks += nb;
+        if (r == kStopReading) break;
         if (r) return r;
-        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, P.scomp));
-        FCX_HIP(hipStreamSynchronize(P.scomp));
+    }
+    if (hdr_total) *hdr_total = total;
+    if (nblocks) *nblocks = tblocks;
+    return FCX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
+                          uint32_t *hdr_total, uint64_t *total_out, uint64_t *nblocks) {
+    if (!dctx || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_decompress_stream: NULL argument");
+    uint64_t tout = 0;
+    const int r = stream_groups(dctx, rd, user, max_in, hdr_total, nblocks,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
+                                    hipStream_t st) -> int {
+        uint64_t got = 0;
+        if (lz78) FCX_TRY(fcx::lz78_decompress_shard_at(dctx, x.din, used, nb, x.dout, out_cap, &got, st, before));
+        else FCX_TRY(fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, st));
+        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, st));
+        FCX_HIP(hipStreamSynchronize(st));
         const int w = wr(user, x.hout, got);
         if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
         tout += got;
-        tblocks += nb;
-    }
-    if (hdr_total) *hdr_total = total;
+        return FCX_OK;
+    });
+    if (r) return r;
     if (total_out) *total_out = tout;
-    if (nblocks) *nblocks = tblocks;
+    return FCX_OK;
+}
+
+int fcx_decompress_range_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in, uint64_t off,
+                                uint64_t len, uint64_t *total_out) {
+    if (!dctx || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_decompress_range_stream: NULL argument");
+    uint64_t pos = 0, tout = 0;   // decoded bytes before the group, bytes written
+    const uint64_t end = len < ~0ull - off ? off + len : ~0ull;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
+                                    hipStream_t st) -> int {
+        // the group's part of the range, in the group's decoded bytes (empty before the range starts:
+        // the call then only indexes the group, for its decoded size)
+        const uint64_t lo = off > pos ? off - pos : 0, n = end > pos + lo ? end - pos - lo : 0;
+        uint64_t got = 0, gtotal = 0;
+        FCX_TRY(fcx::range_shard(dctx, lz78 ? '8' : '7', x.din, used, nb, nullptr, nullptr, lo, n, x.dout, out_cap, &got, st,
+                                 before, &gtotal));
+        if (got) {
+            FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, st));
+            FCX_HIP(hipStreamSynchronize(st));
+            const int w = wr(user, x.hout, got);
+            if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
+            tout += got;
+        }
+        pos += gtotal;
+        return pos >= end ? kStopReading : FCX_OK;
+    });
+    if (r) return r;
+    if (total_out) *total_out = tout;
+    return FCX_OK;
+}
+
+int fcx_decompress_range_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint64_t off, uint64_t len, uint8_t *out,
+                              uint64_t cap, uint64_t *out_len) {
+    if (!dctx || !in || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_decompress_range_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO m{in, in_len, 0, out, cap, 0};
+    FCX_TRY(fcx_decompress_range_stream(dctx, mem_read, mem_write, &m, in_len - FCX_HEADER_BYTES, off, len, nullptr));
+    *out_len = m.out_pos;
     return FCX_OK;
 }
 
