@@ -326,6 +326,69 @@ int fcx_decompress_range_stream(fcx_dctx *ctx, fcx_read_fn read, fcx_write_fn wr
 #define FCX_RANGE_STATS 4
 int fcx_dctx_range_stats(fcx_dctx *ctx, uint64_t *out, int n);
 
+/* ---- round-trip verification: does each record decode back to its block? (FCX7 and FCX8) -----
+ * The byte stream is the reference's, and the reference's decoder does not return every input:
+ *  - a Huffman sub-stream with one distinct symbol stores no symbol identity and decodes as zeros
+ *    (:930-984), so a block of one repeated byte value decodes to the right length of zeros;
+ *  - an all-literal FCX7 block of 16 or more bytes has flag bytes that are all 0xFF, one distinct
+ *    symbol: its flags decode as "all matches", and with pCnt = 0 the block stops at once and decodes
+ *    to 0 bytes (the early stop, :2331-2335): an incompressible stretch of a file is lost;
+ *  - an FCX8 block whose bytes end in 0x00 loses that byte (:3701-3703).
+ * The decompress mode's own check compares total sizes only, modulo 2^32.  The calls below decode
+ * the records with the full decoders and compare them, block by block, with what was compressed.
+ *
+ * What is compared: record k with original block k, the bytes [k B, min(n, (k + 1) B)) of the
+ * original for the block size B the run was compressed with, wherever record k's bytes fall in the
+ * decoded run.  Per record a pair of u32: the decoded byte count, and the first difference: the
+ * smallest i < min(decoded, block length) at which the bytes differ; if there is none and the sizes
+ * differ, min(decoded, block length); otherwise FCX_VERIFY_SAME.
+ * stats[0 .. FCX_VERIFY_STATS): blocks, blocks that differ, the first differing block (UINT64_MAX if
+ * none), blocks whose decoded size is not the block's length, original bytes lying in differing
+ * blocks, decoded bytes in total.
+ *
+ * Return codes: FCX_OK whether or not blocks differ (the verdict is in the data); FCX_ERR_ARG for a
+ * NULL ctx or stats, a kind other than '7' or '8', block_bytes outside [1, FCX_MAX_BLOCK_BYTES],
+ * nblocks != ceil(n / block_bytes); FCX_ERR_FORMAT exactly where the full decoders give it. */
+#define FCX_VERIFY_SAME 0xFFFFFFFFu
+#define FCX_VERIFY_STATS 6
+
+/* Verifies the nblocks records (no file header) of rec_len device bytes at d_rec against the n
+ * device bytes at d_orig that were compressed in blocks of block_bytes.  d_blocks (device, 2 * nblocks
+ * u32, or NULL) receives the pairs, stats (host) the summary.  The run is indexed
+ * (fcx_index_shard), then decoded in groups of consecutive records whose decoded bytes fit a
+ * buffer the context keeps (256 MiB by default, grown on demand; a record of no bytes counts as one
+ * byte, a record larger than the bound is a group of its own), each group through fcx_decompress_shard / fcx_lz78_decompress_shard and then
+ * compared.  Only d_blocks is written.  nblocks == 0 with n == 0 gives zero stats (the first
+ * differing block UINT64_MAX) and touches no device memory.  Synchronises `stream`.  With
+ * fcx_dctx_set_profiling the stage table of the call is index, decode, compare, summary. */
+int fcx_verify_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                     const uint8_t *d_orig, uint64_t n, uint32_t block_bytes, uint32_t *d_blocks, uint64_t *stats,
+                     void *stream);
+/* Host buffers: `rec` the records without the file header, `orig` what was compressed; blocks_host
+ * (2 * nblocks u32) may be NULL.  Copies in and calls fcx_verify_shard. */
+int fcx_verify_host(fcx_dctx *ctx, char kind, const uint8_t *rec, uint64_t rec_len, uint32_t nblocks,
+                    const uint8_t *orig, uint64_t n, uint32_t block_bytes, uint32_t *blocks_host, uint64_t *stats);
+/* one differing block: its number in the file, its length in the original, its decoded bytes, the
+ * first difference */
+typedef void (*fcx_verify_fn)(void *user, uint64_t block, uint64_t block_len, uint64_t decoded, uint32_t first_diff);
+/* fcx_decompress_stream's twin: reads a whole FCX7 or FCX8 file (header first) from read_comp in the
+ * same record groups (<= 256 records, <= 128 MiB; an FCX7 file to its end, of an FCX8 file the
+ * counted records), for each group the matching records * block_bytes bytes of the original from
+ * read_orig, and verifies the group.  on_block (may be NULL) is called for every differing block, in
+ * order.  A record for which the original has no bytes left differs, with block length 0, whatever
+ * it decodes to.  Original bytes left after the last record are reported too: they are added to
+ * stats[4], and on_block is called once more, last, with block = stats[0] (the number of records),
+ * their count as block_len, decoded 0 and first_diff 0.  So the file round-trips exactly when
+ * stats[1] == 0 and stats[4] == 0.  Stats are summed over the groups; the first differing block is
+ * numbered over the whole file. */
+int fcx_verify_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, fcx_read_fn read_orig, void *user_orig,
+                      uint32_t block_bytes, uint64_t max_in, fcx_verify_fn on_block, void *user_cb, uint64_t *stats);
+/* Testing: bound of a group's decoded bytes in later fcx_verify_* calls (0 = the default, 256 MiB),
+ * so that small inputs cross group boundaries; and the groups the last fcx_verify_shard call made
+ * (-1 for a NULL ctx).  The results do not depend on the bound. */
+int fcx_dctx_set_verify_group(fcx_dctx *ctx, uint64_t bytes);
+int fcx_dctx_verify_groups(fcx_dctx *ctx);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -124,6 +124,16 @@ def lib():
         L.fcx_decompress_range_stream.argtypes = [ctypes.c_void_p, READ_FN, WRITE_FN, ctypes.c_void_p, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_uint64, P64]
         L.fcx_dctx_range_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+    if hasattr(L, "fcx_verify_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        L.fcx_verify_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, P64,
+                                       ctypes.c_void_p]
+        L.fcx_verify_host.argtypes = [ctypes.c_void_p, ctypes.c_char, c_u8p, ctypes.c_uint64, ctypes.c_uint32, c_u8p,
+                                      ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, P64]
+        L.fcx_verify_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, READ_FN, ctypes.c_void_p,
+                                        ctypes.c_uint32, ctypes.c_uint64, VERIFY_FN, ctypes.c_void_p, P64]
+        L.fcx_dctx_set_verify_group.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        L.fcx_dctx_verify_groups.argtypes = [ctypes.c_void_p]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -162,6 +172,9 @@ def lib():
 # fcx_read_fn / fcx_write_fn (include/fcx.h)
 READ_FN = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
+# fcx_verify_fn: block, its length in the original, its decoded bytes, the first difference
+VERIFY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32)
+VERIFY_SAME = 0xFFFFFFFF   # FCX_VERIFY_SAME
 
 
 def _stream_fns(src, sink):
@@ -392,6 +405,58 @@ class DContext:
         _check(lib().fcx_dctx_range_stats(self._h, vals, n), "fcx_dctx_range_stats")
         return dict(zip(self.RANGE_STATS, [int(v) for v in vals]))
 
+    # ---- round-trip verification (fcx_verify_*): does each record decode back to its block? ----
+    VERIFY_STATS = ("blocks", "differ", "first", "size_differs", "bytes", "decoded")
+
+    @classmethod
+    def _verify_stats(cls, vals) -> dict:
+        d = dict(zip(cls.VERIFY_STATS, [int(v) for v in vals]))
+        if d["first"] == 2 ** 64 - 1:
+            d["first"] = None
+        return d
+
+    def verify_shard(self, d_rec: int, rec_len: int, nblocks: int, kind: str, d_orig: int, n: int, block_bytes: int,
+                     d_blocks: int = 0, stream: int = 0) -> dict:
+        """device records (no header) against the n device bytes they were compressed from, in blocks
+        of block_bytes; d_blocks (2 * nblocks u32 on the device, or 0) receives per record the decoded
+        bytes and the first difference (VERIFY_SAME: none).  Returns the stats: blocks, differ, first
+        (None: no block differs), size_differs, bytes (of the original in differing blocks), decoded."""
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        _check(lib().fcx_verify_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                      ctypes.c_void_p(d_orig or None), n, block_bytes, ctypes.c_void_p(d_blocks or None),
+                                      vals, ctypes.c_void_p(stream)), "fcx_verify_shard")
+        return self._verify_stats(vals)
+
+    def verify_host(self, records: bytes, nblocks: int, kind: str, orig: bytes, block_bytes: int):
+        """the same on host bytes; returns (stats, [(decoded bytes, first difference)] per record)"""
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        pairs = (ctypes.c_uint32 * max(2 * nblocks, 1))()
+        _check(lib().fcx_verify_host(self._h, kind.encode(), records, len(records), nblocks, orig, len(orig), block_bytes,
+                                     pairs, vals), "fcx_verify_host")
+        return self._verify_stats(vals), [(int(pairs[2 * k]), int(pairs[2 * k + 1])) for k in range(nblocks)]
+
+    def verify_stream(self, src, orig, block_bytes: int = BLOCK_BYTES, max_in: int = 0):
+        """a whole FCX7 or FCX8 file from src against the original from orig (binary readers); returns
+        (stats, [(block, its length in the original, decoded bytes, first difference)] of the differing
+        blocks).  Original bytes behind the last record come last, as block number stats["blocks"].
+        The file round-trips when stats["differ"] == 0 and stats["bytes"] == 0.  max_in (0: unknown): the
+        bytes behind the header, which bound the staging buffers."""
+        rd, _ = _stream_fns(src, None)
+        ro, _ = _stream_fns(orig, None)
+        bad = []
+        cb = VERIFY_FN(lambda _u, k, blen, dec, fd: bad.append((int(k), int(blen), int(dec), int(fd))))
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        _check(lib().fcx_verify_stream(self._h, rd, None, ro, None, block_bytes, max_in, cb, None, vals), "fcx_verify_stream")
+        return self._verify_stats(vals), bad
+
+    def set_verify_group(self, nbytes: int):
+        """testing: bound of a group's decoded bytes in later verify calls (0: the default, 256 MiB)"""
+        _check(lib().fcx_dctx_set_verify_group(self._h, nbytes), "fcx_dctx_set_verify_group")
+
+    def verify_groups(self) -> int:
+        """groups the last verify_shard call decoded"""
+        return int(lib().fcx_dctx_verify_groups(self._h))
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -436,6 +501,18 @@ def decompress_range(blob: bytes, off: int, n: int, device: int = 0) -> bytes:
     ctx = DContext(device)
     try:
         return ctx.decompress_range_host(blob, off, n)
+    finally:
+        ctx.close()
+
+
+def verify(blob: bytes, data: bytes, block_bytes: int = BLOCK_BYTES, device: int = 0):
+    """does the FCX7 or FCX8 file `blob` decode back to `data`, block by block?  Returns (stats, differing
+    blocks) as DContext.verify_stream; it does when stats["differ"] == 0 and stats["bytes"] == 0"""
+    import io
+
+    ctx = DContext(device)
+    try:
+        return ctx.verify_stream(io.BytesIO(blob), io.BytesIO(data), block_bytes, max(0, len(blob) - HEADER_BYTES))
     finally:
         ctx.close()
 

@@ -19,6 +19,12 @@
 //                     only the records the range touches are expanded, nothing behind it is read)
 //   --list            one line per record (numbered from 0): compressed, decoded bytes, decoded offset
 // Without a HIP device both run on the host decoder for FCX7 and fail for FCX8, as decompress does.
+// Round-trip verification (fcx_verify_stream: every record decoded and compared with its block):
+//   --verify            with -c: compress as usual, close the output, then check it against the input
+//   --compare ORIGINAL  decompress mode: check the -i file against ORIGINAL (-b: the block size it was
+//                       made with, when not 1 MiB); writes no -o file.  Not with -c, --range, --list, --verify.
+// One line per differing block, then the verdict; exit status 0 for OK, 1 for FAIL.  Without a HIP
+// device --compare runs on the host decoder for FCX7 and fails for FCX8.
 #include <getopt.h>
 
 #include <chrono>
@@ -37,7 +43,8 @@ static int usage() {
     fprintf(stderr,
             "usage: ./my_compress -i[or --file_in] <input file name> [-o[or --file_out] <output file name>] "
             "[-c (or --compress) <lz77/lz78>] [-b (or --block) <bytes>] [-d (or --device) <hip device>] "
-            "[-g (or --gpus) <count>] [--range <offset>:<length> | --list (decompress only)]\n");
+            "[-g (or --gpus) <count>] [--verify (with -c)] [--range <offset>:<length> | --list | --compare <original> "
+            "(decompress only)]\n");
     return -1;
 }
 
@@ -267,6 +274,57 @@ static int list_gpu(FILE *fin, fcx_dctx *d, char kind, uint16_t counted) {
     return rc;
 }
 
+struct Differing {
+    uint64_t block, len, dec;
+    uint32_t first;
+};
+static void on_differing(void *u, uint64_t block, uint64_t len, uint64_t dec, uint32_t first) {
+    ((std::vector<Differing> *)u)->push_back({block, len, dec, first});
+}
+
+// --compare, and the second half of --verify: the compressed file fcomp against the original, by
+// fcx_verify_stream on the device, or for an FCX7 file without one by the host decoder
+static int do_compare(FILE *fcomp, const char *orig_path, int device, uint32_t block) {
+    FILE *forig = fopen(orig_path, "rb");
+    if (!forig) { printf("open: %s Fail!!\n", orig_path); return -1; }
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    int r = -1;
+    fcx_dctx *d = nullptr;
+    if (fread(hdr, 1, sizeof(hdr), fcomp) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+    } else if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+    } else if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        } else {
+            fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+            r = fcx_cli::host_compare(fcomp, forig, nblocks, block, nullptr);
+        }
+    } else {
+        uint64_t max_in = 0, stats[FCX_VERIFY_STATS];
+        if (fseek(fcomp, 0, SEEK_END) == 0 && ftell(fcomp) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fcomp) - FCX_HEADER_BYTES;
+        rewind(fcomp);
+        std::vector<Differing> bad;
+        const int v = fcx_verify_stream(d, file_read, fcomp, file_read, forig, block, max_in, on_differing, &bad, stats);
+        fcx_dctx_destroy(d);
+        if (v) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        } else {
+            for (const Differing &b : bad) {
+                if (b.block == stats[0]) fcx_cli::verify_extra(b.len);   // (bytes behind the last record)
+                else fcx_cli::verify_line(b.block, b.dec, b.len, b.first);
+            }
+            r = fcx_cli::verify_totals(stats[1], stats[0], stats[4]);
+        }
+    }
+    fclose(forig);
+    return r;
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -336,12 +394,16 @@ int main(int argc, char **argv) {
                                            {"gpus", required_argument, nullptr, 'g'},
                                            {"range", required_argument, nullptr, 'R'},
                                            {"list", no_argument, nullptr, 'L'},
+                                           {"verify", no_argument, nullptr, 'V'},
+                                           {"compare", required_argument, nullptr, 'C'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
     uint32_t block = FCX_DEFAULT_BLOCK_BYTES;
     int device = 0, ngpus = 1, opt;
     bool dist = false;   // -g given: the RCCL multi-GPU path (also at -g 1)
+    bool verify = false, compare = false;
+    std::string original;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -360,29 +422,45 @@ int main(int argc, char **argv) {
             want.range = true;
             break;
         case 'L': want.list = true; break;
+        case 'V': verify = true; break;
+        case 'C': compare = true; original = optarg; break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
     if ((want.range || want.list) && (compress || (want.range && want.list))) return usage();
+    if ((compare && (compress || want.range || want.list || verify)) || (verify && !compress)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    FILE *fout = want.list ? nullptr : fopen(file_out.c_str(), "wb");   // (--list writes no file)
-    if (!fout && !want.list) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
+    const bool no_out = want.list || compare;   // (--list and --compare write no file)
+    FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
+    if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
     if (compress && !lz77 && hipSetDevice(device) != hipSuccess) {
         fprintf(stderr, "fcx: no HIP device %d\n", device);
         return -1;
     }
-    const int r = compress ? (lz77 ? (dist ? do_compress_dist(fin, fout, block, device, ngpus)
-                                                                  : do_compress(fin, fout, block, device))
-                                   : compress_lz78(fin, fout, block))
-                           : do_decompress(fin, fout, device, want);
+    if (compare) {
+        const int r = do_compare(fin, original.c_str(), device, block);
+        fclose(fin);
+        return r;
+    }
+    int r = compress ? (lz77 ? (dist ? do_compress_dist(fin, fout, block, device, ngpus)
+                                     : do_compress(fin, fout, block, device))
+                             : compress_lz78(fin, fout, block))
+                     : do_decompress(fin, fout, device, want);
     fclose(fin);
     if (fout) fclose(fout);
+    if (verify && r == 0) {   // the finished output file against the input, whichever path wrote it
+        FILE *fcomp = fopen(file_out.c_str(), "rb");
+        if (!fcomp) { printf("open: %s Fail!!\n", file_out.c_str()); return -1; }
+        (void)hipSetDevice(device);
+        r = do_compare(fcomp, file_in.c_str(), device, block);
+        fclose(fcomp);
+    }
     return r;
 }

@@ -1,6 +1,7 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
-// (fcx_decode.cpp) record by record, for the whole decompress, --list and --range.  Host code only
-// (stdio and fcx_decompress_block), so it also builds into a stand-alone program (tools/range_host_check.cpp).
+// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range and --compare.  Host code
+// only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
+// (tools/range_host_check.cpp, tools/compare_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -114,6 +115,57 @@ inline int host_range(FILE *fin, FILE *fout, uint16_t nblocks, uint64_t off, uin
     }
     *written = out;
     return 0;
+}
+
+// ---- --compare / --verify: the printout, the same on the GPU and on the host ----
+inline void verify_line(uint64_t k, uint64_t dec, uint64_t blen, uint64_t first_diff) {
+    printf("block %llu: decoded %llu of %llu bytes, first difference at %llu\n", (unsigned long long)k,
+           (unsigned long long)dec, (unsigned long long)blen, (unsigned long long)first_diff);
+}
+inline void verify_extra(uint64_t extra) {
+    printf("original: %llu bytes after the last block\n", (unsigned long long)extra);
+}
+// the verdict: 0 (OK) when no block differs and the original has no bytes left, else 1 (FAIL)
+inline int verify_totals(uint64_t bad, uint64_t blocks, uint64_t bytes) {
+    const bool ok = bad == 0 && bytes == 0;
+    printf("verify: %llu of %llu blocks differ, %llu input bytes in them [%s]\n", (unsigned long long)bad,
+           (unsigned long long)blocks, (unsigned long long)bytes, ok ? "OK" : "FAIL");
+    return ok ? 0 : 1;
+}
+
+// --compare without a device: every record through the host decoder against its block of `block`
+// bytes of forig.  A record the original has no bytes for differs (block length 0); original bytes
+// behind the last record are reported and fail the verdict.  stats as fcx_verify_stream's.  Returns
+// the verdict (0 / 1), or -1 after a message (a damaged record).
+inline int host_compare(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t block, uint64_t *stats) {
+    std::vector<uint8_t> orig(block);
+    uint64_t s[6] = {0, 0, UINT64_MAX, 0, 0, 0};
+    const int r = host_each_record(fin, nblocks, [&](uint32_t k, uint32_t, const uint8_t *plain, uint64_t n) {
+        const size_t blen = fread(orig.data(), 1, block, forig);
+        const uint64_t m = n < blen ? n : blen;
+        uint64_t fd = 0;
+        while (fd < m && plain[fd] == orig[fd]) fd++;
+        const bool differs = fd < m || n != blen || blen == 0;
+        s[0]++;
+        s[3] += n != blen;
+        s[5] += n;
+        if (differs) {
+            if (blen == 0) fd = 0;
+            verify_line(k, n, blen, fd);
+            if (s[1]++ == 0) s[2] = k;
+            s[4] += blen;
+        }
+        return true;
+    });
+    if (r) return r;
+    uint64_t extra = 0;
+    for (size_t g; (g = fread(orig.data(), 1, block, forig)) > 0;) extra += g;
+    if (extra) {
+        verify_extra(extra);
+        s[4] += extra;
+    }
+    if (stats) memcpy(stats, s, sizeof(s));
+    return verify_totals(s[1], s[0], s[4]);
 }
 
 }  // namespace fcx_cli

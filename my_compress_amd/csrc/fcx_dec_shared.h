@@ -400,6 +400,34 @@ struct RangeScratch {
     uint64_t stats[FCX_RANGE_STATS] = {};
 };
 
+// ---- status words of a verification (fcx_dctx's vf.words, u64 each; host_words mirrors them): the
+// first FCX_VERIFY_STATS are the call's stats in the order of fcx.h, written by k_vsummary ----
+constexpr uint32_t kVwBlocks = 0;    // records of the run
+constexpr uint32_t kVwDiffer = 1;    // blocks that differ
+constexpr uint32_t kVwFirst = 2;     // the first of them (preset to ~0: none)
+constexpr uint32_t kVwSized = 3;     // blocks whose decoded size is not the block's length
+constexpr uint32_t kVwBytes = 4;     // original bytes in differing blocks
+constexpr uint32_t kVwDecoded = 5;   // decoded bytes of the run
+constexpr uint32_t kVwWords = 8;
+static_assert(FCX_VERIFY_STATS <= kVwWords, "verify status words");
+
+// fcx_verify_shard behind its argument checks (fcx_verify.hip), for the stream path's groups of a
+// longer file: nblocks may exceed ceil(n / block_bytes) (records the original has no bytes for: they
+// differ, with block length 0); messages number the records from rec_base
+int verify_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *d_orig,
+               uint64_t n, uint32_t block_bytes, uint32_t *d_blocks, uint64_t *stats, hipStream_t st, uint64_t rec_base);
+
+// scratch of the verification (fcx_verify.hip)
+struct VerifyScratch {
+    DevBuf<uint8_t> buf;             // a group's decoded bytes, grown on demand up to the group bound
+    DevBuf<uint32_t> first_diff;     // per record: the first differing byte k_vcompare found
+    DevBuf<uint32_t> blocks;         // the stream form's (decoded, first difference) pairs of a group
+    DevBuf<uint64_t> words;          // kVw*
+    PinnedBuf<uint64_t> host_words;
+    uint64_t group_bytes = 0;        // fcx_dctx_set_verify_group (0: 256 MiB)
+    uint32_t groups = 0;             // groups of the last call
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -428,6 +456,7 @@ struct fcx_dctx {
     fcx::Dec7 d7;
     std::unique_ptr<fcx::Scratch78, fcx::Calls<fcx::free_scratch78>> d78;
     fcx::RangeScratch rg;
+    fcx::VerifyScratch vf;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

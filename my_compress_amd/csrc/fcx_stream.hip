@@ -379,6 +379,87 @@ int fcx_decompress_range_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len
     return FCX_OK;
 }
 
+// Original bytes left after the last record are counted (read and dropped through the staging of
+// slot 0), added to stats[4] and reported by a last on_block call with block = the number of records.
+int fcx_verify_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_orig, void *user_orig,
+                      uint32_t block_bytes, uint64_t max_in, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
+    if (!dctx || !rd || !rd_orig || !stats) return fail(FCX_ERR_ARG, "fcx_verify_stream: NULL argument");
+    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
+        return fail(FCX_ERR_ARG, "fcx_verify_stream: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
+    const uint64_t B = block_bytes;
+    uint64_t sum[FCX_VERIFY_STATS] = {0, 0, ~0ull, 0, 0, 0};
+    std::vector<uint32_t> pairs;
+    bool orig_end = false;
+    uint8_t *spare = nullptr;   // (pinned staging of slot 0, for the bytes after the last record)
+    uint64_t spare_cap = 0;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
+                                    hipStream_t st) -> int {
+        spare = x.hout;
+        spare_cap = out_cap;
+        // the group's blocks of the original, staged where a decompress stages the decoded bytes
+        // (every record is >= 7 bytes of a staging that holds 1 MiB of output per 7 bytes of input)
+        const uint64_t want = (uint64_t)nb * B;
+        if (want > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_verify_stream: staging too small");
+        int64_t got = orig_end ? 0 : read_full(rd_orig, user_orig, x.hout, want);
+        if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
+        if ((uint64_t)got < want) orig_end = true;
+        if (got) FCX_HIP(hipMemcpyAsync(x.dout, x.hout, (uint64_t)got, hipMemcpyHostToDevice, st));
+        FCX_TRY(dctx->vf.blocks.reserve(8ull * nb, "verify pairs"));
+        uint64_t gs[FCX_VERIFY_STATS];
+        FCX_TRY(fcx::verify_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, (uint64_t)got, block_bytes, dctx->vf.blocks,
+                                gs, st, before));
+        pairs.resize(2ull * nb);
+        FCX_HIP(hipMemcpy(pairs.data(), dctx->vf.blocks, 8ull * nb, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < nb && on_block; k++) {
+            if (pairs[2 * k + 1] == FCX_VERIFY_SAME) continue;
+            const uint64_t o0 = (uint64_t)k * B, blen = o0 < (uint64_t)got ? ((uint64_t)got - o0 < B ? (uint64_t)got - o0 : B) : 0;
+            on_block(user_cb, before + k, blen, pairs[2 * k], pairs[2 * k + 1]);
+        }
+        if (gs[2] != ~0ull && sum[2] == ~0ull) sum[2] = before + gs[2];
+        for (int i : {0, 1, 3, 4, 5}) sum[i] += gs[i];
+        return FCX_OK;
+    });
+    if (r) return r;
+    uint64_t extra = 0;
+    if (!orig_end) {
+        uint8_t small[4096];
+        uint8_t *buf = spare ? spare : small;
+        const uint64_t cap = spare ? spare_cap : sizeof(small);
+        for (;;) {
+            const int64_t got = rd_orig(user_orig, buf, cap);
+            if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
+            if (got == 0) break;
+            extra += (uint64_t)got;
+        }
+    }
+    if (extra) {
+        sum[4] += extra;
+        if (on_block) on_block(user_cb, sum[0], extra, 0, 0);
+    }
+    for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = sum[i];
+    return FCX_OK;
+}
+
+int fcx_verify_host(fcx_dctx *dctx, char kind, const uint8_t *rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *orig,
+                    uint64_t n, uint32_t block_bytes, uint32_t *blocks_host, uint64_t *stats) {
+    if (!dctx || !stats || (rec_len && !rec) || (n && !orig)) return fail(FCX_ERR_ARG, "fcx_verify_host: NULL argument");
+    int dev = 0;
+    if (fcx_dctx_device(dctx, &dev)) return FCX_ERR_ARG;
+    FCX_HIP(hipSetDevice(dev));
+    DevBuf<uint8_t> d_rec, d_orig;
+    DevBuf<uint32_t> d_blocks;
+    FCX_TRY(d_rec.reserve(rec_len, "records"));
+    FCX_TRY(d_orig.reserve(n, "original"));
+    if (blocks_host) FCX_TRY(d_blocks.reserve(8ull * nblocks, "verify pairs"));
+    if (rec_len) FCX_HIP(hipMemcpy(d_rec, rec, rec_len, hipMemcpyHostToDevice));
+    if (n) FCX_HIP(hipMemcpy(d_orig, orig, n, hipMemcpyHostToDevice));
+    FCX_TRY(fcx_verify_shard(dctx, kind, d_rec, rec_len, nblocks, d_orig, n, block_bytes, blocks_host ? d_blocks.p : nullptr,
+                             stats, nullptr));
+    if (blocks_host && nblocks) FCX_HIP(hipMemcpy(blocks_host, d_blocks, 8ull * nblocks, hipMemcpyDeviceToHost));
+    return FCX_OK;
+}
+
 int fcx_decompress_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap,
                         uint64_t *out_len) {
     if (!dctx || !in || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_decompress_host: NULL argument");
