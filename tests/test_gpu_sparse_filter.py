@@ -13,6 +13,7 @@ import pytest
 import inputs
 import my_compress_amd as mc
 import oracle
+from match_craft import geometry, plant, planted_input
 
 pytestmark = pytest.mark.gpu
 
@@ -20,39 +21,6 @@ TILE, HALO = 4096, 2048
 LENGTHS = (3, 4, 11, 12, 13, 257, 258, 259, 300)
 DISTANCES = (1, 2, 3, 2046, 2047, 2048, 2049)
 BLOCKS = (65536, 12293, 5000)
-
-
-def plant(buf: bytearray, p: int, d: int, length: int) -> bool:
-    """copy `length` bytes from p - d to p, byte by byte (d < length gives a period-d run)"""
-    if p - d < 0 or p < 0 or p + length > len(buf):
-        return False
-    for i in range(length):
-        buf[p + i] = buf[p - d + i]
-    return True
-
-
-def geometry(n: int, block: int):
-    """block ranges and the tile starts inside blocks (not the block starts themselves)"""
-    blocks = [(bs, min(bs + block, n)) for bs in range(0, n, block)]
-    tiles = [bs + t for bs, be in blocks for t in range(TILE, be - bs, TILE)]
-    return blocks, tiles
-
-
-def planted_input(seed: int, ntiles: int, block: int, length: int, d: int) -> bytes:
-    n = ntiles * TILE
-    buf = bytearray(inputs.generate("rand", seed, n))
-    blocks, tiles = geometry(n, block)
-    pick = lambda lst, i: lst[i % len(lst)]
-    b_last, b_mid = blocks[-1], blocks[len(blocks) // 2]
-    plant(buf, pick(tiles, 0), d, length)                    # on a tile start: the candidate in the halo
-    plant(buf, pick(tiles, 1) - 1, d, length)                # one position before a tile start
-    plant(buf, pick(tiles, 2) - 1 + d, d, length)            # the source straddles a tile boundary
-    plant(buf, b_mid[0], d, length)                          # block position 0 (nothing may cross blocks)
-    plant(buf, b_last[0] + 1, d, length)                     # block position 1
-    plant(buf, 1, d, length)                                 # ... of the first block (d = 1 only)
-    plant(buf, b_last[1] - length, d, length)                # ending at the block's end
-    plant(buf, b_mid[1] - 3, d, 3)                           # fewer than 4 bytes left in the block
-    return bytes(buf)
 
 
 def model_max_flagged(L, data: bytes, block: int):
@@ -173,8 +141,12 @@ def test_routed_rand_and_text_blocks(cuda, L):
     classifier files the rand tiles for the sparse unit; those whose flagged keys exceed the cap
     are not sparse and go on to the no-filter list once the units run listed.  (No lazy-tile bar
     here: in some calls one tile of this input is left to the stitch, with the 17-bit filter as
-    well and more often -- presumably a long planted run exhausting a query's extension budget,
-    whose use depends on the order the candidates come in; the bytes are the oracle's either way.)"""
+    well and more often.  The cause is the extension budget of the bucket search: a query inside a
+    planted run of period 1-3 and 257-300 bytes has hundreds of candidates of 12 bytes or more;
+    oldest first one extension serves, in pass B as many extend as arrive before the oldest has
+    written the best -- more than 24 in some calls.  Without those plants the input never showed
+    a lazy tile, with them alone it did: DESIGN.md §3, test_gpu_match_edges.py.  The bytes are the
+    oracle's either way.)"""
     block, nblocks = 65536, 32
     rng = random.Random(7)
     parts = []
