@@ -597,6 +597,15 @@ def compress_lz78(data: bytes, block_bytes: int = BLOCK_BYTES) -> bytes:
     return out.raw[:n.value]
 
 
+def lz78_compress_shard(d_in: int, n: int, block_bytes: int, d_out: int, cap: int, stream: int = 0) -> int:
+    """n device bytes at d_in -> FCX8 records (no header) at d_out; returns their byte count.  The
+    scratch stays cached on the current device for the next call (lz78_release frees it)."""
+    out = ctypes.c_uint64(0)
+    _check(lib().fcx_lz78_compress_shard(ctypes.c_void_p(d_in), n, block_bytes, ctypes.c_void_p(d_out), cap,
+                                         ctypes.byref(out), ctypes.c_void_p(stream)), "fcx_lz78_compress_shard")
+    return out.value
+
+
 def my_decompress_file_lz78(payload: bytes, cap: int = BLOCK_BYTES + 8) -> bytes:
     """one payload -> block bytes on the GPU (reference decoder semantics, :3478)"""
     out = ctypes.create_string_buffer(max(cap, 1))

@@ -630,86 +630,73 @@ using namespace fcx78;
 using namespace fcx;
 
 namespace {
-struct Alloc78 {
+// what the block size alone fixes of a call's scratch; the rest of S is bind()'s
+Scratch geometry(uint32_t B) {
     Scratch S{};
-    void *mem = nullptr;
-};
-
-// Compress scratch is kept per device between calls (grow-only; ~40 GB for a 1 GiB
-// batch), so repeated shards do not pay hipMalloc/hipFree; fcx_lz78_release frees it.
-// Calls on one device are serialised on its slot.
-struct Cache78 {
-    std::mutex mu;
-    void *mem = nullptr;
-    uint64_t bytes = 0;
-};
-Cache78 g_cache[64];
-
-Cache78 *cache_for_current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    return &g_cache[dev];
-}
-
-int setup(Alloc78 &A, Cache78 &C, uint32_t B, uint32_t nb) {
-    Scratch &S = A.S;
     S.B = B;
-    S.nb = nb;
     S.cap_log2 = 10;
     // only phrases of >= 3 bytes reach the hash table, so it holds <= B/3 entries:
     // B + 2 slots keep the load <= 1/3 and always leave an empty slot
     while ((1ull << S.cap_log2) < (uint64_t)B + 2) S.cap_log2++;
-    S.Gmax = B / 256 + 2;
-    if (S.Gmax < 1024) S.Gmax = 1024;   // the char tree borrows iw[0..511]; parents need 2*256
+    S.Gmax = std::max<uint32_t>(1024, B / 256 + 2);   // the char tree borrows iw[0..511]; parents need 2*256
     S.tiles = (B + 1 + kTileTok - 1) / kTileTok;
     S.bmw = B / 32 + 2;
     S.dense1 = B >= kDense1Min ? 1u : 0u;
-    const uint64_t nbl = nb;
-    uint64_t sz[] = {
-        (nbl << S.cap_log2) * 8, nbl * B * 4, nbl * B, nbl * S.bmw * 4, nbl * S.bmw * 4, nbl * B * 2, nbl * B,
-        nbl * S.Gmax * 4, nbl * 256 * 4, nbl * S.Gmax * 4, nbl * S.Gmax, nbl * 256 * 4, nbl * 256,
-        nbl * 2 * S.Gmax * 4, nbl * 2 * S.Gmax * 4, nbl * S.Gmax * 4, nbl * 576, nbl * S.tiles * 8,
-        nbl * (B + 2) * 4, nbl * (B + 2) * 4, nbl * sizeof(Rec78), nbl * 8, 8, S.dense1 ? (nbl << 16) * 4 : 0};
-    constexpr int K = sizeof(sz) / sizeof(sz[0]);
-    uint64_t offs[K], tot = 0;
-    for (int i = 0; i < K; i++) {
-        offs[i] = tot;
-        tot += (sz[i] + 255) & ~255ull;
-    }
-    if (C.bytes < tot) {
-        if (C.mem) (void)hipFree(C.mem);
-        C.mem = nullptr;
-        C.bytes = 0;
-        FCX_HIP(hipMalloc(&C.mem, tot));
-        C.bytes = tot;
-    }
-    A.mem = C.mem;
-    char *m = (char *)A.mem;
-    S.slot = (uint64_t *)(m + offs[0]);
-    S.idx = (uint32_t *)(m + offs[1]);
-    S.c = (uint8_t *)(m + offs[2]);
-    S.bm = (uint32_t *)(m + offs[3]);
-    S.rbase = (uint32_t *)(m + offs[4]);
-    S.grp = (uint16_t *)(m + offs[5]);
-    S.gpos = (uint8_t *)(m + offs[6]);
-    S.gcnt = (uint32_t *)(m + offs[7]);
-    S.chist = (uint32_t *)(m + offs[8]);
-    S.gcode = (uint32_t *)(m + offs[9]);
-    S.glen = (uint8_t *)(m + offs[10]);
-    S.ccode = (uint32_t *)(m + offs[11]);
-    S.clen = (uint8_t *)(m + offs[12]);
-    S.tree = (uint32_t *)(m + offs[13]);
-    S.par = (uint32_t *)(m + offs[14]);
-    S.iw = (uint32_t *)(m + offs[15]);
-    S.chdr = (uint8_t *)(m + offs[16]);
-    S.tbits = (uint32_t *)(m + offs[17]);
-    S.gstage = (uint32_t *)(m + offs[18]);
-    S.cstage = (uint32_t *)(m + offs[19]);
-    S.rec = (Rec78 *)(m + offs[20]);
-    S.off = (uint64_t *)(m + offs[21]);
-    S.total = (uint64_t *)(m + offs[22]);
-    S.d1 = S.dense1 ? (uint32_t *)(m + offs[23]) : nullptr;
+    return S;
+}
+
+// ---- status words of a compress call (Cache78::words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kEwTotal = 0;   // running output bytes across batches (k78_scan, as S.total)
+constexpr uint32_t kEwErr = 1;     // error bits (kErr78*), a u32
+constexpr uint32_t kEwWords = 2;
+
+// The compress scratch of one device, kept between calls (grow-only; ~40 GB for a 1 GiB batch) so
+// that repeated shards do not pay hipMalloc/hipFree; fcx_lz78_release drops it as a whole.
+struct Cache78 {
+    DevBuf<uint64_t> slot, off;
+    DevBuf<uint32_t> d1, idx, bm, rbase, gcnt, chist, gcode, ccode, tree, par, iw, tbits, gstage, cstage;
+    DevBuf<uint16_t> grp;
+    DevBuf<uint8_t> c, gpos, glen, clen, chdr;
+    DevBuf<Rec78> rec;
+    DevBuf<uint64_t> words;           // the status words (kEw*)
+    PinnedBuf<uint64_t> host_words;   // (made last: set = words is)
+};
+
+// Every per-block scratch field, once: its buffer, its Scratch pointer, its bytes for nb blocks (the
+// sizes of struct Scratch's comments), its name in an error message, whether a batch starts from zeros.
+template <typename F>
+int each_field(const Scratch &g, uint64_t nb, F f) {
+    const uint64_t B = g.B, G = g.Gmax;
+    FCX_TRY(f(&Cache78::slot, &Scratch::slot, (nb << g.cap_log2) * 8, "trie", true));
+    FCX_TRY(f(&Cache78::d1, &Scratch::d1, g.dense1 ? (nb << 16) * 4 : 0, "depth-1 table", true));
+    FCX_TRY(f(&Cache78::idx, &Scratch::idx, nb * B * 4, "token indices", false));
+    FCX_TRY(f(&Cache78::c, &Scratch::c, nb * B, "token chars", false));
+    FCX_TRY(f(&Cache78::bm, &Scratch::bm, nb * g.bmw * 4, "index bitmap", true));
+    FCX_TRY(f(&Cache78::rbase, &Scratch::rbase, nb * g.bmw * 4, "rank bases", false));
+    FCX_TRY(f(&Cache78::grp, &Scratch::grp, nb * B * 2, "groups", false));
+    FCX_TRY(f(&Cache78::gpos, &Scratch::gpos, nb * B, "group positions", false));
+    FCX_TRY(f(&Cache78::gcnt, &Scratch::gcnt, nb * G * 4, "group counts", true));
+    FCX_TRY(f(&Cache78::chist, &Scratch::chist, nb * 256 * 4, "char counts", true));
+    FCX_TRY(f(&Cache78::gcode, &Scratch::gcode, nb * G * 4, "group codes", false));
+    FCX_TRY(f(&Cache78::glen, &Scratch::glen, nb * G, "group code lengths", false));
+    FCX_TRY(f(&Cache78::ccode, &Scratch::ccode, nb * 256 * 4, "char codes", false));
+    FCX_TRY(f(&Cache78::clen, &Scratch::clen, nb * 256, "char code lengths", false));
+    FCX_TRY(f(&Cache78::tree, &Scratch::tree, nb * 2 * G * 4, "group tree", false));
+    FCX_TRY(f(&Cache78::par, &Scratch::par, nb * 2 * G * 4, "tree parents", false));
+    FCX_TRY(f(&Cache78::iw, &Scratch::iw, nb * G * 4, "tree weights", false));
+    FCX_TRY(f(&Cache78::chdr, &Scratch::chdr, nb * 576, "char headers", false));
+    FCX_TRY(f(&Cache78::tbits, &Scratch::tbits, nb * g.tiles * 2 * 4, "tile bits", false));
+    FCX_TRY(f(&Cache78::gstage, &Scratch::gstage, nb * (B + 2) * 4, "group words", true));
+    FCX_TRY(f(&Cache78::cstage, &Scratch::cstage, nb * (B + 2) * 4, "char words", true));
+    FCX_TRY(f(&Cache78::rec, &Scratch::rec, nb * sizeof(Rec78), "records", false));
+    FCX_TRY(f(&Cache78::off, &Scratch::off, nb * 8, "record offsets", false));
     return FCX_OK;
+}
+
+uint64_t bytes_per_block(const Scratch &g) {
+    uint64_t sum = 0;
+    (void)each_field(g, 1, [&](auto, auto, uint64_t bytes, const char *, bool) { return sum += bytes, FCX_OK; });
+    return sum;
 }
 
 // scratch is ~40 B per input byte of a batch (the trie 16 B): 1 GiB batches (~40 GB of
@@ -717,6 +704,39 @@ int setup(Alloc78 &A, Cache78 &C, uint32_t B, uint32_t nb) {
 // (256 MiB: 539 MB/s, 1 GiB: 1386 MB/s on rand)
 constexpr uint64_t kBatchBytes = 1024ull << 20;
 constexpr uint64_t kScratchBudget = 64ull << 30;
+
+// blocks per batch: <= 1 GiB of input, and per-block scratch (trie, dense depth-1
+// table, group tables: large for tiny blocks) within a 64 GiB budget
+uint32_t batch_blocks(const Scratch &g, uint64_t n) {
+    const uint64_t nblk = (n + g.B - 1) / g.B, by_budget = std::max<uint64_t>(1, kScratchBudget / bytes_per_block(g));
+    return (uint32_t)std::max<uint64_t>(1, std::min({nblk, kBatchBytes / g.B, by_budget}));
+}
+
+// S for batches of nb blocks: every field holds its bytes (grown when it held fewer) and is bound
+int bind(Cache78 &C, Scratch &S, uint32_t nb) {
+    S.nb = nb;
+    return each_field(S, nb, [&](auto buf, auto ptr, uint64_t bytes, const char *what, bool) -> int {
+        auto &b = C.*buf;
+        const hipError_t e = bytes && (!b.p || b.bytes < bytes) ? b.alloc(bytes) : hipSuccess;
+        if (e != hipSuccess)
+            return fail(FCX_ERR_HIP, std::string("fcx_lz78_compress_shard: hipMalloc ") + what + ": " + hipGetErrorString(e));
+        S.*ptr = bytes ? b.p : nullptr;   // (null: d1 below kDense1Min)
+        return FCX_OK;
+    });
+}
+
+// Calls on one device are serialised on its slot.  The table is made by the first call and never
+// destroyed: its buffers must not call the runtime at process exit.
+struct Device78 {
+    std::mutex mu;
+    Cache78 cache;
+};
+Device78 *current_device78() {
+    static Device78 *const table = new Device78[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    return &table[dev];
+}
 }  // namespace
 
 extern "C" {
@@ -729,37 +749,28 @@ int fcx_lz78_compress_shard(const uint8_t *d_in, uint64_t n, uint32_t block_byte
     *out_len = 0;
     if (n == 0) return FCX_OK;
     hipStream_t st = (hipStream_t)stream;
+    Scratch S = geometry(block_bytes);
     const uint64_t nblk = (n + block_bytes - 1) / block_bytes;
-    // blocks per batch: <= 1 GiB of input, and per-block scratch (trie, dense depth-1
-    // table, group tables: large for tiny blocks) within a 64 GiB budget
-    uint32_t cl2 = 10;
-    while ((1ull << cl2) < (uint64_t)block_bytes + 2) cl2++;
-    const uint64_t per_block = (8ull << cl2) + (block_bytes >= kDense1Min ? 1ull << 18 : 0) +
-                               64ull * std::max<uint32_t>(1024, block_bytes / 256 + 2) +
-                               24ull * block_bytes + 4096;
-    const uint64_t by_budget = std::max<uint64_t>(1, kScratchBudget / per_block);
-    const uint32_t batch = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>(std::min<uint64_t>(nblk, kBatchBytes / block_bytes), by_budget));
-    Cache78 *C = cache_for_current_device();
-    if (!C) return fail(FCX_ERR_HIP, "fcx_lz78_compress_shard: no current HIP device");
-    std::lock_guard<std::mutex> lock(C->mu);
-    Alloc78 A;
-    if (int rc = setup(A, *C, block_bytes, batch)) return rc;
-    Scratch S = A.S;
-    DevBuf<uint32_t> d_err;
-    FCX_HIP(d_err.alloc(4));
-    FCX_HIP(hipMemsetAsync(d_err, 0, 4, st));
-    FCX_HIP(hipMemsetAsync(S.total, 0, 8, st));
+    const uint32_t batch = batch_blocks(S, n);
+    Device78 *D = current_device78();
+    if (!D) return fail(FCX_ERR_HIP, "fcx_lz78_compress_shard: no current HIP device");
+    std::lock_guard<std::mutex> lock(D->mu);
+    Cache78 &C = D->cache;
+    if (!C.host_words) {
+        FCX_HIP(C.words.alloc(8 * kEwWords));
+        FCX_HIP(C.host_words.alloc(8 * kEwWords));
+    }
+    FCX_TRY(bind(C, S, batch));
+    S.total = C.words + kEwTotal;
+    uint32_t *err = (uint32_t *)(C.words + kEwErr);
+    FCX_HIP(hipMemsetAsync(C.words, 0, 8 * kEwWords, st));   // (every call: a failed one leaves its bits)
     for (uint64_t b0 = 0; b0 < nblk; b0 += batch) {
         S.nb = (uint32_t)std::min<uint64_t>(batch, nblk - b0);
         const uint32_t nb = S.nb;
-        FCX_HIP(hipMemsetAsync(S.slot, 0, ((uint64_t)nb << S.cap_log2) * 8, st));
-        if (S.dense1) FCX_HIP(hipMemsetAsync(S.d1, 0, ((uint64_t)nb << 16) * 4, st));
-        FCX_HIP(hipMemsetAsync(S.bm, 0, (uint64_t)nb * S.bmw * 4, st));
-        FCX_HIP(hipMemsetAsync(S.gcnt, 0, (uint64_t)nb * S.Gmax * 4, st));
-        FCX_HIP(hipMemsetAsync(S.chist, 0, (uint64_t)nb * 256 * 4, st));
-        FCX_HIP(hipMemsetAsync(S.gstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
-        FCX_HIP(hipMemsetAsync(S.cstage, 0, (uint64_t)nb * (S.B + 2) * 4, st));
+        FCX_TRY(each_field(S, nb, [&](auto, auto ptr, uint64_t bytes, const char *, bool zero) -> int {
+            if (zero && bytes) FCX_HIP(hipMemsetAsync(S.*ptr, 0, bytes, st));
+            return FCX_OK;
+        }));
         const dim3 tok_grid(S.tiles, nb);
         if (S.dense1) k78_parse<true><<<nb, 64, 0, st>>>(d_in, n, S, b0);
         else k78_parse<false><<<nb, 64, 0, st>>>(d_in, n, S, b0);
@@ -767,31 +778,38 @@ int fcx_lz78_compress_shard(const uint8_t *d_in, uint64_t n, uint32_t block_byte
         k78_rank<<<nb, 1024, 0, st>>>(S);
         k78_group<<<tok_grid, 256, 0, st>>>(S);
         k78_tree<<<nb, 256, 0, st>>>(S);
-        k78_scan<<<1, 1024, 0, st>>>(S, cap, d_err);
+        k78_scan<<<1, 1024, 0, st>>>(S, cap, err);
         k78_tilesum<<<tok_grid, 256, 0, st>>>(S);
         k78_tilescan<<<(nb + 63) / 64, 64, 0, st>>>(S);
         k78_pack<<<tok_grid, 256, 0, st>>>(S);
-        k78_write<<<dim3(64, nb), 256, 0, st>>>(S, d_out, d_err);
+        k78_write<<<dim3(64, nb), 256, 0, st>>>(S, d_out, err);
         FCX_HIP(hipGetLastError());
     }
-    uint32_t herr = 0;
-    uint64_t total = 0;
-    FCX_HIP(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, st));
-    FCX_HIP(hipMemcpyAsync(&total, S.total, 8, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipMemcpyAsync(C.host_words, C.words, 8 * kEwWords, hipMemcpyDeviceToHost, st));
     FCX_HIP(hipStreamSynchronize(st));
+    const uint32_t herr = (uint32_t)C.host_words[kEwErr];
     if (herr & kErr78Capacity) return fail(FCX_ERR_CAPACITY, "fcx_lz78_compress_shard: output capacity exceeded");
     if (herr & kErr78CodeLen) return fail(FCX_ERR_INTERNAL, "fcx_lz78_compress_shard: Huffman code longer than 32 bits");
-    *out_len = total;
+    *out_len = C.host_words[kEwTotal];
     return FCX_OK;
 }
 
 int fcx_lz78_release(void) {
-    Cache78 *C = cache_for_current_device();
-    if (!C) return fail(FCX_ERR_HIP, "fcx_lz78_release: no current HIP device");
-    std::lock_guard<std::mutex> lock(C->mu);
-    if (C->mem) FCX_HIP(hipFree(C->mem));
-    C->mem = nullptr;
-    C->bytes = 0;
+    Device78 *D = current_device78();
+    if (!D) return fail(FCX_ERR_HIP, "fcx_lz78_release: no current HIP device");
+    std::lock_guard<std::mutex> lock(D->mu);
+    D->cache = Cache78{};
+    return FCX_OK;
+}
+
+// development only (not in fcx.h): the scratch plan of a compress call for the tests; no GPU.
+// out: cap_log2, Gmax, tiles, bmw, dense1, scratch bytes per block, blocks per batch
+int fcx_debug_lz78_plan(uint32_t block_bytes, uint64_t n, uint64_t out[7]) {
+    if (!out || block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
+        return fail(FCX_ERR_ARG, "fcx_debug_lz78_plan: bad argument");
+    const Scratch g = geometry(block_bytes);
+    const uint64_t v[7] = {g.cap_log2, g.Gmax, g.tiles, g.bmw, g.dense1, bytes_per_block(g), batch_blocks(g, n)};
+    std::copy(v, v + 7, out);
     return FCX_OK;
 }
 

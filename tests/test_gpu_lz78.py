@@ -117,3 +117,74 @@ def test_tiny_blocks_vs_oracle(block):
     assert blob == oracle.lz78_compress_file(data, block)
     assert mc.decompress_lz78(blob, len(data) + 64 * ((len(data) + block - 1) // block)) == \
         oracle.lz78_decompress_file(blob, len(data) + 64 * ((len(data) + block - 1) // block))
+
+
+# ---- the scratch cached per device across calls (what bench.py's lz78 leg and the tools do) ----
+import torch  # noqa: E402  (here, not in the tests: torch finds no GPU once libfcx.so has run without it loaded)
+
+
+def shard_records(cuda, data: bytes, block: int, cap: int = None, stream: int = None) -> bytes:
+    """mc.lz78_compress_shard on device tensors: the records, without the file header; no release"""
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(cuda)
+    bound = mc.lz78_bound(len(data), block)
+    d_out = torch.zeros(bound, dtype=torch.uint8, device=cuda)
+    torch.cuda.synchronize()
+    sid = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    m = mc.lz78_compress_shard(d_in.data_ptr(), len(data), block, d_out.data_ptr(), bound if cap is None else cap, sid)
+    return d_out[:m].cpu().numpy().tobytes()
+
+
+def oracle_records(data: bytes, block: int) -> bytes:
+    return oracle.lz78_compress_file(data, block)[mc.HEADER_BYTES:]
+
+
+def test_one_cache_across_geometries(cuda):
+    # 65535 / 65536 straddle the dense depth-1 table (d1 null against bound), 4096 after 65536 is a
+    # smaller call on a larger cache, 1-byte blocks have the largest table per input byte, the calls
+    # after the release rebuild everything
+    mc.lz78_release()
+    try:
+        for k, (n, block) in enumerate([(3 * 65536 + 5, 65536), (40000, 4096), (300, 1), (5 * 65536, 65536),
+                                        (70000, 65535), (0, 0), (70000, 65536), (1 << 20, 1 << 20)]):
+            if n == 0:
+                mc.lz78_release()
+                continue
+            data = inputs.mosaic(400 + k, n)
+            assert shard_records(cuda, data, block) == oracle_records(data, block), (n, block)
+    finally:
+        mc.lz78_release()
+
+
+def test_failed_call_leaves_the_cache_usable(cuda):
+    data = inputs.generate("rand", 1, 100000)
+    try:
+        with pytest.raises(mc.FcxError, match=r"\(-2\)"):   # FCX_ERR_CAPACITY
+            shard_records(cuda, data, 1 << 20, cap=1000)
+        assert shard_records(cuda, data, 1 << 20) == oracle_records(data, 1 << 20)
+    finally:
+        mc.lz78_release()
+
+
+def test_two_threads_one_device(cuda):
+    import threading
+
+    n, block = 200003, 65536
+    datas = [inputs.mosaic(500 + t, n) for t in range(2)]
+    streams = [torch.cuda.Stream(device=cuda) for _ in datas]
+    got = [[] for _ in datas]
+
+    def work(t):
+        for _ in range(3):
+            got[t].append(shard_records(cuda, datas[t], block, stream=streams[t].cuda_stream))
+
+    try:
+        threads = [threading.Thread(target=work, args=(t,)) for t in range(2)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+        for t, data in enumerate(datas):
+            want = oracle_records(data, block)
+            assert len(got[t]) == 3 and all(g == want for g in got[t]), t
+    finally:
+        mc.lz78_release()

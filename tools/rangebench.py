@@ -86,12 +86,7 @@ def main():
             else:
                 cap = mc.lz78_bound(n, block)
                 d_rec = torch.empty(cap, dtype=torch.uint8, device=dev)
-                got = mc.ctypes.c_uint64()
-                mc._check(mc.lib().fcx_lz78_compress_shard(mc.ctypes.c_void_p(d_plain.data_ptr()), n, block,
-                                                           mc.ctypes.c_void_p(d_rec.data_ptr()), cap,
-                                                           mc.ctypes.byref(got), mc.ctypes.c_void_p(sid)),
-                          "fcx_lz78_compress_shard")
-                m = got.value
+                m = mc.lz78_compress_shard(d_plain.data_ptr(), n, block, d_rec.data_ptr(), cap, sid)
                 mc.lz78_release()
                 full = lambda: dc.decompress_lz78_shard(d_rec.data_ptr(), m, nb, d_back.data_ptr(), n + 64, sid)
             d_back = torch.zeros(n + 64, dtype=torch.uint8, device=dev)
