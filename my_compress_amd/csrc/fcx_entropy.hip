@@ -280,8 +280,12 @@ __global__ __launch_bounds__(kTreeT) void k_tree(Layout L, const uint16_t *__res
     // first on a tie) and I[k] = P[2k] + P[2k+1].  From I = infinity, each round ranks every leaf and
     // internal node into P by binary search and recomputes I; I only decreases towards the merge's
     // (I[0] is right after one round, and I[k] is right one round after every node P[0..2k+1] uses),
-    // and the measured histograms settle in 8-15 rounds.  Past kJacobiMax rounds, or for short
-    // merges, one thread runs the two-queue merge below.
+    // so the rounds follow the tree's height: 9-12 for the chars of random and mixed data, 24-28 for
+    // Fibonacci-like histograms.  Over histograms of <= 2^20 symbols and >= 65 leaves the worst found
+    // is 26 rounds, for codes of 25 bits (tests/test_entropy_craft.py's sweep; a code of d bits needs
+    // F(d + 2) symbols, so d <= 28 below FCX_MAX_BLOCK_BYTES and kErrCodeLen cannot be raised by a
+    // legal block).  The exit past kJacobiMax rounds was therefore never seen taken; it, and short
+    // merges, leave the merge to one thread's two-queue form below.
     bool merged = fifo;
     if (!fifo && nint >= kJacobiMin) {
         constexpr uint32_t kInf = 0xFFFFFFFFu;

@@ -44,12 +44,13 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def source_constants(fname: str, names) -> dict:
-    """`constexpr uint32_t NAME = VALUE;` of the decoder sources"""
+    """`constexpr uint32_t NAME = VALUE;` of the kernel sources, also where one declaration
+    holds several (`constexpr uint32_t A = 1, NAME = VALUE;`); None where VALUE is no literal"""
     with open(os.path.join(CSRC, fname)) as f:
         text = f.read()
     out = {}
     for n in names:
-        m = re.search(r"constexpr\s+uint32_t\s+" + n + r"\s*=\s*(\d+)\s*;", text)
+        m = re.search(r"constexpr\s+uint32_t\s+(?:\w+\s*=\s*[^,;]+,\s*)*" + n + r"\s*=\s*(\d+)\s*[,;]", text)
         out[n] = int(m.group(1)) if m else None
     return out
 

@@ -11,64 +11,13 @@ huffman_tree KATs in test_oracle.py):
               P[2k+1]; from I = infinity, rank everything into P and recompute I until it settles
 
 Each model returns the children (left, right) of every internal node as ("L", symbol) or
-("I", creation index); the oracle's node ids are mapped the same way."""
-import bisect
+("I", creation index); the oracle's node ids are mapped the same way.  The models live in
+tests/entropy_craft.py, which also uses them to say which form a crafted histogram takes."""
 import ctypes
 import random
 
 import oracle
-
-INF = 2**32 - 1
-
-
-def sorted_leaves(w):
-    """(weight, symbol) of the symbols with weight > 0, stably sorted by weight (458-498)"""
-    return sorted(((x, s) for s, x in enumerate(w) if x > 0), key=lambda t: (t[0], t[1]))
-
-
-def serial(leaves):
-    L = [x for x, _ in leaves]
-    n = len(L)
-    I, kids = [], []
-    lq = iq = 0
-    for k in range(n - 1):
-        pick = []
-        for _ in range(2):
-            if lq < n and (iq >= len(I) or L[lq] <= I[iq]):
-                pick.append((L[lq], ("L", leaves[lq][1])))
-                lq += 1
-            else:
-                pick.append((I[iq], ("I", iq)))
-                iq += 1
-        I.append(pick[0][0] + pick[1][0])
-        kids.append((pick[0][1], pick[1][1]))
-    return kids
-
-
-def closed(leaves):
-    n = len(leaves)
-    L = [x for x, _ in leaves]
-    if n < 2 or not L[0] + L[1] > L[-1]:
-        return None
-    ident = lambda i: ("L", leaves[i][1]) if i < n else ("I", i - n)
-    return [(ident(2 * k), ident(2 * k + 1)) for k in range(n - 1)]
-
-
-def fixed_point(leaves, max_rounds=400):
-    n = len(leaves)
-    L = [x for x, _ in leaves]
-    I = [INF] * (n - 1)
-    for rounds in range(1, max_rounds + 1):
-        P = [None] * (2 * n - 1)
-        for t, x in enumerate(L):   # a leaf after the internal nodes lighter than it
-            P[t + bisect.bisect_left(I, x)] = (x, ("L", leaves[t][1]))
-        for j, x in enumerate(I):   # an internal node after the leaves no heavier than it
-            P[j + bisect.bisect_right(L, x)] = (x, ("I", j))
-        nI = [INF if INF in (P[2 * k][0], P[2 * k + 1][0]) else P[2 * k][0] + P[2 * k + 1][0] for k in range(n - 1)]
-        if nI == I:
-            return [(P[2 * k][1], P[2 * k + 1][1]) for k in range(n - 1)], rounds
-        I = nI
-    return None, max_rounds
+from entropy_craft import closed, fixed_point, serial, sorted_leaves   # the models (moved there)
 
 
 def reference(w):
