@@ -389,6 +389,97 @@ int fcx_verify_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, fcx
 int fcx_dctx_set_verify_group(fcx_dctx *ctx, uint64_t bytes);
 int fcx_dctx_verify_groups(fcx_dctx *ctx);
 
+/* ---- repair sidecar: every FCX7 and FCX8 file decodes back to its input -----------------------
+ * The records stay the reference's bytes, so what its decoder does not return (above) cannot be
+ * mended inside them.  A repair is a second, small piece of data made from the records and the
+ * original while both are at hand: one entry per block that does not come back, which says what to
+ * keep of the decoded record and what to write behind it.  A decompress that is given the repair
+ * returns the original exactly; without it nothing changes.
+ *
+ * Record k with (decoded bytes dlen, first difference fd) as fcx_verify_shard computes them and its
+ * block of blen bytes: no entry when fd == FCX_VERIFY_SAME; otherwise one entry that keeps the decoded
+ * prefix [0, from) with from = fd and writes len = blen - from bytes: FCX_REPAIR_FILL when those bytes
+ * of the original are all one value (len <= 1 included; len == 0 only truncates), else FCX_REPAIR_RAW
+ * with the bytes appended to the repair's data.  Always from <= min(dlen, blen).
+ * The entry is the same 32 little-endian bytes on the device, in the FCXR file and in Python. */
+typedef struct fcx_repair_entry {
+    uint64_t block;     /* run-relative in the shard calls, file-wide in the file */
+    uint64_t data_off;  /* RAW: offset of its bytes in the data (of the call / of its section); FILL: 0 */
+    uint32_t from, len;
+    uint32_t kind;      /* FCX_REPAIR_RAW or FCX_REPAIR_FILL */
+    uint32_t fill;      /* low 8 bits; 0 for RAW */
+} fcx_repair_entry;
+#define FCX_REPAIR_RAW 0u
+#define FCX_REPAIR_FILL 1u
+
+/* Builds the repair of a device-resident run: fcx_verify_shard's index, decode and compare, then the
+ * entries of the differing blocks in block order at d_entries (nblocks slots, or NULL) and the RAW
+ * bytes back to back in entry order at d_data (capacity data_cap).  *nentries and *data_bytes are set
+ * whenever the call gets as far as the plan (every return but FCX_ERR_ARG / FCX_ERR_FORMAT / a
+ * HIP error).  data_cap < *data_bytes: FCX_ERR_CAPACITY, nothing is gathered, so d_data == NULL with
+ * data_cap == 0 is the size query.  d_entries == NULL only together with d_data == NULL: the counts
+ * alone.  stats (FCX_VERIFY_STATS values, may be NULL): fcx_verify_shard's.  Only d_entries[0,
+ * *nentries) and d_data[0, *data_bytes) are written, and of the original only [d_orig, d_orig + n) is
+ * read.  FCX_ERR_ARG as fcx_verify_shard.  The result does not depend on fcx_dctx_set_verify_group.
+ * Stage table with profiling: index, decode, compare, summary, plan, gather. */
+int fcx_repair_build_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                           const uint8_t *d_orig, uint64_t n, uint32_t block_bytes, fcx_repair_entry *d_entries,
+                           uint8_t *d_data, uint64_t data_cap, uint32_t *nentries, uint64_t *data_bytes, uint64_t *stats,
+                           void *stream);
+/* Decodes the run and applies the repair: the n original bytes, block k at d_out + k block_bytes.
+ * The run is indexed, the entries are validated against it and every record without an entry is
+ * checked, and only then is d_out written.  FCX_ERR_FORMAT, naming the first bad entry or else the first
+ * bad record (numbered from 0), when an entry's block is >= nblocks or not strictly ascending, kind > 1,
+ * from > the record's decoded bytes, from + len != the block's length, a RAW range lies outside
+ * [0, data_bytes), or a record without an entry does not decode to its block's length.  cap < n:
+ * FCX_ERR_CAPACITY with *out_len = n.  FCX_ERR_ARG as fcx_verify_shard (nblocks != ceil(n / block_bytes)
+ * included).  With nentries == 0 the call is the index plus one full decode straight into d_out;
+ * otherwise record groups are formed as fcx_verify_shard forms them: a group without entries decodes
+ * straight to its place in d_out, a group with entries into the context's bounded buffer, from where
+ * its blocks are assembled.  On an error d_out[0, n) is unspecified; d_out[n, cap) is never written.
+ * What these checks cannot see: a repair made for another file whose entries happen to fit gives wrong
+ * bytes.  The FCXR file's header and trailer (kind, block size, n, records) guard the file forms.
+ * Stage table with profiling: index, check, decode, assemble. */
+int fcx_repair_apply_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
+                           uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries,
+                           const uint8_t *d_data, uint64_t data_bytes, uint8_t *d_out, uint64_t cap, uint64_t *out_len,
+                           void *stream);
+/* Counters of the last fcx_repair_build_shard / fcx_repair_apply_shard call on the context (the host
+ * and stream forms: of their last group), min(n, FCX_REPAIR_STATS) values: entries, FILL entries, data
+ * bytes, groups decoded straight into d_out, groups staged and assembled (both 0 after a build). */
+#define FCX_REPAIR_STATS 5
+int fcx_dctx_repair_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
+/* The FCXR file.  Header, 16 bytes: "FCXR", u8 version 1, u8 kind '7' / '8', u16 0, u32 block_bytes,
+ * u32 0.  Sections: u32 nentries (1..256), u32 0, u64 data_bytes, the entries (block file-wide,
+ * data_off into the section's data), the data.  Trailer: u32 0xFFFFFFFF, u32 0, u64 n, u64 records,
+ * u64 entries, u64 data_bytes.  The writer is canonical: a section holds exactly the entries whose
+ * block >> 8 is equal, everything ascends, the RAW bytes lie back to back in entry order; so the bytes
+ * do not depend on how a path groups the records.  The reader takes any sectioning that ascends
+ * strictly with 1..256 entries per section, and reads sections as the record groups need them. */
+#define FCX_REPAIR_HEADER_BYTES 16u
+#define FCX_REPAIR_TRAILER_BYTES 40u
+#define FCX_REPAIR_FILE_STATS 4   /* the trailer: original bytes, records, entries, data bytes */
+/* fcx_verify_stream's twin: reads the FCX7 / FCX8 file and the original in the same record groups and
+ * writes the canonical FCXR file through write_repair.  Original bytes after the last record, or
+ * records the original has no bytes for, are FCX_ERR_ARG: a repair cannot express them.
+ * stats (FCX_REPAIR_FILE_STATS values, may be NULL): the trailer's. */
+int fcx_repair_build_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, fcx_read_fn read_orig, void *user_orig,
+                            uint32_t block_bytes, uint64_t max_in, fcx_write_fn write_repair, void *user_repair,
+                            uint64_t *stats);
+/* fcx_decompress_stream's twin: reads the file in its record groups, for each group the sections of
+ * the FCXR file that hold its entries, and writes the repaired bytes.  FCX_ERR_FORMAT for an FCXR file
+ * of another kind than the FCX file's, a malformed one, a trailer that disagrees with the records read
+ * or the bytes written, or a block shorter than the block size that is not the last record. */
+int fcx_repair_apply_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, fcx_read_fn read_repair,
+                            void *user_repair, fcx_write_fn write_out, void *user_out, uint64_t max_in,
+                            uint64_t *total_out);
+/* on memory, through the stream forms: `in` a whole FCX7 / FCX8 file, `repair` a whole FCXR file */
+int fcx_repair_build_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *orig, uint64_t n,
+                          uint32_t block_bytes, uint8_t *repair, uint64_t cap, uint64_t *repair_len);
+int fcx_repair_apply_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
+                          uint8_t *out, uint64_t cap, uint64_t *out_len);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -134,6 +134,24 @@ def lib():
                                         ctypes.c_uint32, ctypes.c_uint64, VERIFY_FN, ctypes.c_void_p, P64]
         L.fcx_dctx_set_verify_group.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         L.fcx_dctx_verify_groups.argtypes = [ctypes.c_void_p]
+    if hasattr(L, "fcx_repair_build_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        P32 = ctypes.POINTER(ctypes.c_uint32)
+        L.fcx_repair_build_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, P32, P64, P64, ctypes.c_void_p]
+        L.fcx_repair_apply_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, P64,
+                                             ctypes.c_void_p]
+        L.fcx_dctx_repair_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+        L.fcx_repair_build_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, READ_FN, ctypes.c_void_p,
+                                              ctypes.c_uint32, ctypes.c_uint64, WRITE_FN, ctypes.c_void_p, P64]
+        L.fcx_repair_apply_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, READ_FN, ctypes.c_void_p, WRITE_FN,
+                                              ctypes.c_void_p, ctypes.c_uint64, P64]
+        L.fcx_repair_build_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64, ctypes.c_uint32,
+                                            c_u8p, ctypes.c_uint64, P64]
+        L.fcx_repair_apply_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64, c_u8p,
+                                            ctypes.c_uint64, P64]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -175,6 +193,60 @@ WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes
 # fcx_verify_fn: block, its length in the original, its decoded bytes, the first difference
 VERIFY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32)
 VERIFY_SAME = 0xFFFFFFFF   # FCX_VERIFY_SAME
+
+
+# the repair sidecar (include/fcx.h): one 32-byte entry layout on the device, in the FCXR file and here
+REPAIR_RAW, REPAIR_FILL = 0, 1
+REPAIR_ENTRY_BYTES, REPAIR_HEADER_BYTES, REPAIR_TRAILER_BYTES = 32, 16, 40
+_REPAIR_ENTRY = struct.Struct("<QQIIII")
+
+
+class RepairEntry(tuple):
+    """(block, data_off, from, len, kind, fill) of an fcx_repair_entry"""
+    __slots__ = ()
+    block = property(lambda s: s[0])
+    data_off = property(lambda s: s[1])
+    start = property(lambda s: s[2])   # the entry's `from`
+    len = property(lambda s: s[3])
+    kind = property(lambda s: s[4])
+    fill = property(lambda s: s[5])
+
+    def pack(self) -> bytes:
+        return _REPAIR_ENTRY.pack(*self)
+
+
+def unpack_repair_entries(raw: bytes, count: int = None):
+    count = len(raw) // REPAIR_ENTRY_BYTES if count is None else count
+    return [RepairEntry(_REPAIR_ENTRY.unpack_from(raw, REPAIR_ENTRY_BYTES * i)) for i in range(count)]
+
+
+def parse_repair(blob: bytes) -> dict:
+    """an FCXR file taken apart, for tests: kind, block_bytes, the sections as ([RepairEntry], data) with the
+    entries' blocks file-wide and data_off into the section's data, and the trailer (n, records, entries,
+    data_bytes).  Checks the layout only (ValueError), not the rules of the reader."""
+    if len(blob) < REPAIR_HEADER_BYTES or blob[:4] != b"FCXR":
+        raise ValueError("not an FCXR file")
+    version, kind, zero, block_bytes, zero2 = struct.unpack_from("<BBHII", blob, 4)
+    if version != 1 or zero or zero2:
+        raise ValueError("bad FCXR header")
+    q, sections, trailer = REPAIR_HEADER_BYTES, [], None
+    while trailer is None:
+        ne, zero, nd = struct.unpack_from("<IIQ", blob, q)
+        if ne == 0xFFFFFFFF:
+            trailer = struct.unpack_from("<QQQQ", blob, q + 8)
+            q += REPAIR_TRAILER_BYTES
+            break
+        q += 16
+        if q + REPAIR_ENTRY_BYTES * ne + nd > len(blob):
+            raise ValueError("truncated FCXR section")
+        ents = unpack_repair_entries(blob[q:q + REPAIR_ENTRY_BYTES * ne], ne)
+        q += REPAIR_ENTRY_BYTES * ne
+        sections.append((ents, blob[q:q + nd]))
+        q += nd
+    if q != len(blob):
+        raise ValueError("bytes behind the FCXR trailer")
+    return {"kind": chr(kind), "block_bytes": block_bytes, "sections": sections,
+            "trailer": dict(zip(("n", "records", "entries", "data_bytes"), trailer))}
 
 
 def _stream_fns(src, sink):
@@ -457,6 +529,84 @@ class DContext:
         """groups the last verify_shard call decoded"""
         return int(lib().fcx_dctx_verify_groups(self._h))
 
+    # ---- the repair sidecar (fcx_repair_*): what restores the blocks that do not come back ----
+    REPAIR_STATS = ("entries", "fills", "data_bytes", "groups_direct", "groups_staged")
+
+    def repair_build_shard(self, d_rec: int, rec_len: int, nblocks: int, kind: str, d_orig: int, n: int, block_bytes: int,
+                           d_entries: int = 0, d_data: int = 0, data_cap: int = 0, stream: int = 0, check: bool = True):
+        """the repair of device records against the n device bytes they were compressed from: the entries
+        (32 bytes each, block order) to d_entries (nblocks slots, or 0), the RAW bytes to d_data.  Returns
+        (rc, entries, data bytes, verify stats); d_data == 0 is the size query (rc FCX_ERR_CAPACITY when there
+        are RAW bytes).  check: raise on any rc but 0 and FCX_ERR_CAPACITY."""
+        ne, nd = ctypes.c_uint32(), ctypes.c_uint64()
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        rc = lib().fcx_repair_build_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                          ctypes.c_void_p(d_orig or None), n, block_bytes, ctypes.c_void_p(d_entries or None),
+                                          ctypes.c_void_p(d_data or None), data_cap, ctypes.byref(ne), ctypes.byref(nd), vals,
+                                          ctypes.c_void_p(stream))
+        if check and rc not in (0, -2):
+            _check(rc, "fcx_repair_build_shard")
+        return rc, int(ne.value), int(nd.value), self._verify_stats(vals)
+
+    def repair_apply_shard(self, d_rec: int, rec_len: int, nblocks: int, kind: str, n: int, block_bytes: int, d_entries: int,
+                           nentries: int, d_data: int, data_bytes: int, d_out: int, cap: int, stream: int = 0) -> int:
+        """decodes the device records and applies the repair: the n original bytes to d_out; returns n"""
+        out_len = ctypes.c_uint64()
+        _check(lib().fcx_repair_apply_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, n,
+                                            block_bytes, ctypes.c_void_p(d_entries or None), nentries,
+                                            ctypes.c_void_p(d_data or None), data_bytes, ctypes.c_void_p(d_out or None), cap,
+                                            ctypes.byref(out_len), ctypes.c_void_p(stream)), "fcx_repair_apply_shard")
+        return int(out_len.value)
+
+    def repair_stats(self) -> dict:
+        """counters of the last repair call (fcx_dctx_repair_stats)"""
+        n = len(self.REPAIR_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_repair_stats(self._h, vals, n), "fcx_dctx_repair_stats")
+        return dict(zip(self.REPAIR_STATS, [int(v) for v in vals]))
+
+    def repair_build_stream(self, src, orig, sink, block_bytes: int = BLOCK_BYTES, max_in: int = 0) -> dict:
+        """a whole FCX7 or FCX8 file from src and the original from orig (binary readers) -> the canonical
+        FCXR file to sink (a binary writer); returns the trailer: n, records, entries, data_bytes"""
+        rd, _ = _stream_fns(src, None)
+        ro, _ = _stream_fns(orig, None)
+        _, wr = _stream_fns(None, sink)
+        vals = (ctypes.c_uint64 * 4)()
+        _check(lib().fcx_repair_build_stream(self._h, rd, None, ro, None, block_bytes, max_in, wr, None, vals),
+               "fcx_repair_build_stream")
+        return dict(zip(("n", "records", "entries", "data_bytes"), [int(v) for v in vals]))
+
+    def repair_apply_stream(self, src, repair, sink, max_in: int = 0) -> int:
+        """a whole FCX7 or FCX8 file from src and its FCXR file from repair -> the original bytes to sink"""
+        rd, _ = _stream_fns(src, None)
+        rr, _ = _stream_fns(repair, None)
+        _, wr = _stream_fns(None, sink)
+        total = ctypes.c_uint64()
+        _check(lib().fcx_repair_apply_stream(self._h, rd, None, rr, None, wr, None, max_in, ctypes.byref(total)),
+               "fcx_repair_apply_stream")
+        return int(total.value)
+
+    def repair_build_host(self, blob: bytes, data: bytes, block_bytes: int = BLOCK_BYTES) -> bytes:
+        """the FCXR file of the whole file `blob` against `data`"""
+        nrec = max(1, (len(data) + block_bytes - 1) // block_bytes)
+        cap = REPAIR_HEADER_BYTES + REPAIR_TRAILER_BYTES + len(data) + (REPAIR_ENTRY_BYTES + 16) * nrec
+        out = ctypes.create_string_buffer(cap)
+        got = ctypes.c_uint64()
+        _check(lib().fcx_repair_build_host(self._h, blob, len(blob), data, len(data), block_bytes, out, cap, ctypes.byref(got)),
+               "fcx_repair_build_host")
+        return out.raw[:got.value]
+
+    def repair_apply_host(self, blob: bytes, repair: bytes, cap: int = None) -> bytes:
+        """the whole file `blob` and its FCXR file -> the original bytes (cap defaults to the trailer's n)"""
+        if cap is None:
+            cap = struct.unpack_from("<Q", repair, len(repair) - REPAIR_TRAILER_BYTES + 8)[0] if len(repair) >= 56 else 0
+            cap = min(cap, len(blob) // 7 * (BLOCK_BYTES + 8) + 8)   # (what the records can decode to at most)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        got = ctypes.c_uint64()
+        _check(lib().fcx_repair_apply_host(self._h, blob, len(blob), repair, len(repair), out, cap, ctypes.byref(got)),
+               "fcx_repair_apply_host")
+        return out.raw[:got.value]
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -513,6 +663,25 @@ def verify(blob: bytes, data: bytes, block_bytes: int = BLOCK_BYTES, device: int
     ctx = DContext(device)
     try:
         return ctx.verify_stream(io.BytesIO(blob), io.BytesIO(data), block_bytes, max(0, len(blob) - HEADER_BYTES))
+    finally:
+        ctx.close()
+
+
+def repair(blob: bytes, data: bytes, block_bytes: int = BLOCK_BYTES, device: int = 0) -> bytes:
+    """the repair sidecar (an FCXR file) of the FCX7 or FCX8 file `blob`, made from `data` in blocks of
+    block_bytes: with it, decompress_repaired(blob, ...) returns `data` exactly"""
+    ctx = DContext(device)
+    try:
+        return ctx.repair_build_host(blob, data, block_bytes)
+    finally:
+        ctx.close()
+
+
+def decompress_repaired(blob: bytes, repair: bytes, device: int = 0) -> bytes:
+    """the FCX7 or FCX8 file `blob` decoded and mended by its FCXR file: the bytes that were compressed"""
+    ctx = DContext(device)
+    try:
+        return ctx.repair_apply_host(blob, repair)
     finally:
         ctx.close()
 

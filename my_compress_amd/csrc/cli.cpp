@@ -25,6 +25,13 @@
 //                       made with, when not 1 MiB); writes no -o file.  Not with -c, --range, --list, --verify.
 // One line per differing block, then the verdict; exit status 0 for OK, 1 for FAIL.  Without a HIP
 // device --compare runs on the host decoder for FCX7 and fails for FCX8.
+// Repair sidecar (an FCXR file: per block that does not decode back to its input, what restores it):
+//   --repair FILE   with -c: compress as usual, close the output, then write the sidecar in a pass over the
+//                   finished file and the input (after --verify's pass, when both are given);
+//                   with --compare ORIGINAL: also write the sidecar of the -i file against ORIGINAL;
+//                   otherwise (decompress): read the sidecar and write the repaired output, the original bytes.
+//                   Not with --range or --list.  Prints "repair: E entries, D data bytes for R blocks" when
+//                   it writes one.  Without a HIP device both run on the host decoder for FCX7 and fail for FCX8.
 #include <getopt.h>
 
 #include <chrono>
@@ -44,7 +51,7 @@ static int usage() {
             "usage: ./my_compress -i[or --file_in] <input file name> [-o[or --file_out] <output file name>] "
             "[-c (or --compress) <lz77/lz78>] [-b (or --block) <bytes>] [-d (or --device) <hip device>] "
             "[-g (or --gpus) <count>] [--verify (with -c)] [--range <offset>:<length> | --list | --compare <original> "
-            "(decompress only)]\n");
+            "(decompress only)] [--repair <sidecar file> (written with -c or --compare, read by a decompress)]\n");
     return -1;
 }
 
@@ -151,6 +158,14 @@ static int report(uint64_t got_total, uint32_t total) {
     printf("All block decompress total bytes = %llu, Compress Before bytes = %u [%s]\n",
            (unsigned long long)got_total, total, ok ? "SUCCESS" : "FAIL");
     return ok ? 0 : 1;
+}
+
+// with --repair the size that counts is the sidecar's (its trailer was checked against what was written):
+// the header's total is that of the bytes that were compressed, which an edited original need not match
+static int report_repaired(uint64_t got_total) {
+    printf("All block decompress total bytes = %llu, the repair sidecar's bytes = %llu [SUCCESS]\n",
+           (unsigned long long)got_total, (unsigned long long)got_total);
+    return 0;
 }
 
 // host decoder, used when no HIP device is present
@@ -325,7 +340,49 @@ static int do_compare(FILE *fcomp, const char *orig_path, int device, uint32_t b
     return r;
 }
 
-static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want) {
+// --repair with -c or --compare: the sidecar of the compressed file fcomp (at its start) against the
+// original, by fcx_repair_build_stream on the device, or for an FCX7 file without one by the host decoder
+static int do_repair_build(FILE *fcomp, const char *orig_path, int device, uint32_t block, const char *repair_path) {
+    FILE *forig = fopen(orig_path, "rb");
+    if (!forig) { printf("open: %s Fail!!\n", orig_path); return -1; }
+    FILE *frep = fopen(repair_path, "wb");
+    if (!frep) { printf("open: %s Fail!!\n", repair_path); fclose(forig); return -1; }
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    int r = -1;
+    uint64_t stats[FCX_REPAIR_FILE_STATS] = {};
+    fcx_dctx *d = nullptr;
+    if (fread(hdr, 1, sizeof(hdr), fcomp) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+    } else if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+    } else if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        } else {
+            fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+            r = fcx_cli::host_repair_build(fcomp, forig, nblocks, block, frep, stats);
+        }
+    } else {
+        uint64_t max_in = 0;
+        if (fseek(fcomp, 0, SEEK_END) == 0 && ftell(fcomp) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fcomp) - FCX_HEADER_BYTES;
+        rewind(fcomp);
+        r = fcx_repair_build_stream(d, file_read, fcomp, file_read, forig, block, max_in, fcx_cli::stdio_write, frep, stats);
+        fcx_dctx_destroy(d);
+        if (r) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            r = -1;
+        }
+    }
+    fclose(forig);
+    if (fclose(frep) != 0 && r == 0) { fprintf(stderr, "write error\n"); r = -1; }
+    if (r == 0) fcx_cli::repair_totals(stats[2], stats[3], stats[1]);
+    return r;
+}
+
+static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
         fprintf(stderr, "Read file head infomation error!!!\n");
@@ -350,6 +407,11 @@ static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want) {
             uint64_t n = 0;
             const int r = fcx_cli::host_range(fin, fout, nblocks, want.off, want.len, &n);
             return r ? r : range_done(n, want.off);
+        }
+        if (frep) {
+            uint64_t n = 0;
+            const int r = fcx_cli::host_repair_apply(fin, frep, fout, nblocks, &n);
+            return r ? r : report_repaired(n);
         }
         return decompress_host(fin, fout, total, nblocks);
     }
@@ -376,13 +438,14 @@ static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want) {
         }
         return range_done(got_total, want.off);
     }
-    const int r = fcx_decompress_stream(d, files_read, files_write, &io, 0, &htotal, &got_total, &nrec);
+    const int r = frep ? fcx_repair_apply_stream(d, file_read, fin, file_read, frep, fcx_cli::stdio_write, fout, 0, &got_total)
+                       : fcx_decompress_stream(d, files_read, files_write, &io, 0, &htotal, &got_total, &nrec);
     fcx_dctx_destroy(d);
     if (r) {
         fprintf(stderr, "fcx: %s\n", fcx_last_error());
         return -1;
     }
-    return report(got_total, total);
+    return frep ? report_repaired(got_total) : report(got_total, total);
 }
 
 int main(int argc, char **argv) {
@@ -396,6 +459,7 @@ int main(int argc, char **argv) {
                                            {"list", no_argument, nullptr, 'L'},
                                            {"verify", no_argument, nullptr, 'V'},
                                            {"compare", required_argument, nullptr, 'C'},
+                                           {"repair", required_argument, nullptr, 'P'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -403,7 +467,7 @@ int main(int argc, char **argv) {
     int device = 0, ngpus = 1, opt;
     bool dist = false;   // -g given: the RCCL multi-GPU path (also at -g 1)
     bool verify = false, compare = false;
-    std::string original;
+    std::string original, repair;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -424,12 +488,14 @@ int main(int argc, char **argv) {
         case 'L': want.list = true; break;
         case 'V': verify = true; break;
         case 'C': compare = true; original = optarg; break;
+        case 'P': repair = optarg; break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
     if ((want.range || want.list) && (compress || (want.range && want.list))) return usage();
     if ((compare && (compress || want.range || want.list || verify)) || (verify && !compress)) return usage();
+    if (!repair.empty() && (want.range || want.list)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
@@ -445,21 +511,38 @@ int main(int argc, char **argv) {
         return -1;
     }
     if (compare) {
-        const int r = do_compare(fin, original.c_str(), device, block);
+        int r = do_compare(fin, original.c_str(), device, block);
+        if (!repair.empty() && r >= 0) {   // the sidecar of the same pair, whatever the verdict
+            rewind(fin);
+            if (do_repair_build(fin, original.c_str(), device, block, repair.c_str())) r = -1;
+        }
         fclose(fin);
         return r;
+    }
+    FILE *frep = nullptr;   // a decompress reads the sidecar
+    if (!compress && !repair.empty() && !(frep = fopen(repair.c_str(), "rb"))) {
+        printf("open: %s Fail!!\n", repair.c_str());
+        return -1;
     }
     int r = compress ? (lz77 ? (dist ? do_compress_dist(fin, fout, block, device, ngpus)
                                      : do_compress(fin, fout, block, device))
                              : compress_lz78(fin, fout, block))
-                     : do_decompress(fin, fout, device, want);
+                     : do_decompress(fin, fout, device, want, frep);
     fclose(fin);
     if (fout) fclose(fout);
+    if (frep) fclose(frep);
     if (verify && r == 0) {   // the finished output file against the input, whichever path wrote it
         FILE *fcomp = fopen(file_out.c_str(), "rb");
         if (!fcomp) { printf("open: %s Fail!!\n", file_out.c_str()); return -1; }
         (void)hipSetDevice(device);
         r = do_compare(fcomp, file_in.c_str(), device, block);
+        fclose(fcomp);
+    }
+    if (compress && !repair.empty() && r >= 0) {   // the sidecar of the finished output file, whichever path wrote it
+        FILE *fcomp = fopen(file_out.c_str(), "rb");
+        if (!fcomp) { printf("open: %s Fail!!\n", file_out.c_str()); return -1; }
+        (void)hipSetDevice(device);
+        if (do_repair_build(fcomp, file_in.c_str(), device, block, repair.c_str())) r = -1;
         fclose(fcomp);
     }
     return r;

@@ -1,7 +1,7 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
-// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range and --compare.  Host code
+// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare and --repair.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
-// (tools/range_host_check.cpp, tools/compare_host_check.cpp).
+// (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fcx.h"
+#include "fcx_repair_file.h"
 
 namespace fcx_cli {
 
@@ -168,6 +169,106 @@ inline int host_compare(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t block
     return verify_totals(s[1], s[0], s[4]);
 }
 
+// ---- --repair: the printout, and the FCXR file over stdio ----
+inline void repair_totals(uint64_t entries, uint64_t data_bytes, uint64_t records) {
+    printf("repair: %llu entries, %llu data bytes for %llu blocks\n", (unsigned long long)entries,
+           (unsigned long long)data_bytes, (unsigned long long)records);
+}
+inline int64_t stdio_read(void *u, uint8_t *buf, uint64_t cap) {
+    FILE *f = (FILE *)u;
+    const size_t n = fread(buf, 1, (size_t)cap, f);
+    return ferror(f) ? -1 : (int64_t)n;
+}
+inline int stdio_write(void *u, const uint8_t *buf, uint64_t n) { return fwrite(buf, 1, (size_t)n, (FILE *)u) == n ? 0 : -1; }
+
+// --compare --repair without a device: the FCXR file of the FCX7 records behind the header of fin
+// against forig, to frep; the bytes fcx_repair_build_stream writes.  A record the original has no
+// bytes for, or original bytes behind the last record, cannot be expressed: -1 after a message, as for
+// a damaged record.  stats: FCX_REPAIR_FILE_STATS values.
+inline int host_repair_build(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t block, FILE *frep, uint64_t *stats) {
+    fcx_repair_file::Writer W;
+    W.wr = stdio_write;
+    W.user = frep;
+    if (W.begin('7', block)) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    std::vector<uint8_t> orig(block);
+    uint64_t n = 0, records = 0;
+    bool ok = true;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t k, uint32_t, const uint8_t *plain, uint64_t dlen) {
+        const size_t blen = fread(orig.data(), 1, block, forig);
+        if (blen == 0 || n != (uint64_t)k * block) {   // (a block before this one was short)
+            fprintf(stderr, "fcx: repair: the original has no bytes for record %u\n", k);
+            return ok = false;
+        }
+        fcx_repair_entry e;
+        if (fcx_repair_file::plan_entry(k, plain, dlen, orig.data(), blen, &e) && W.add(e, orig.data() + e.from)) {
+            fprintf(stderr, "fcx: %s\n", W.err.c_str());
+            return ok = false;
+        }
+        n += blen;
+        records++;
+        return true;
+    });
+    if (r || !ok) return -1;
+    if (fread(orig.data(), 1, 1, forig)) {
+        fprintf(stderr, "fcx: repair: the original has bytes after the last record\n");
+        return -1;
+    }
+    if (W.finish(n, records)) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    const uint64_t s[FCX_REPAIR_FILE_STATS] = {n, records, W.entries, W.data_bytes};
+    if (stats) memcpy(stats, s, sizeof(s));
+    return 0;
+}
+
+// decompress with --repair without a device: every FCX7 record through the host decoder, its entry
+// applied, to fout; the checks of fcx_repair_apply_stream.  *written: bytes written.
+inline int host_repair_apply(FILE *fin, FILE *frep, FILE *fout, uint16_t nblocks, uint64_t *written) {
+    fcx_repair_file::Reader F;
+    F.rd = stdio_read;
+    F.user = frep;
+    if (F.open()) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+    if (F.kind != '7') { fprintf(stderr, "fcx: repair file: made for the other codec\n"); return -1; }
+    const uint32_t B = F.block_bytes;
+    std::vector<uint8_t> fillbuf;
+    uint64_t n = 0, records = 0;
+    bool ok = true, short_seen = false;
+    auto bad = [&](uint32_t k, const char *why) {
+        fprintf(stderr, "fcx: repair: record %u %s\n", k, why);
+        return ok = false;
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t k, uint32_t, const uint8_t *plain, uint64_t dlen) {
+        if (short_seen) return bad(k - 1, "gives a block shorter than the block size and is not the last");
+        fcx_repair_entry e;
+        const uint8_t *raw = nullptr;
+        const int g = F.next(k, (uint64_t)k + 1, &e, &raw);
+        if (g < 0) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return ok = false; }
+        uint64_t blen = dlen;
+        if (g) {
+            if (e.from > dlen) return bad(k, "decodes to fewer bytes than its entry keeps");
+            blen = (uint64_t)e.from + e.len;
+        }
+        if (blen == 0 || blen > B) return bad(k, "does not decode to its block's length and has no entry that mends it");
+        if (blen < B) short_seen = true;
+        const uint64_t keep = g ? e.from : dlen;
+        bool w = fwrite(plain, 1, (size_t)keep, fout) == keep;
+        if (g && e.len) {
+            if (e.kind == FCX_REPAIR_FILL) {
+                fillbuf.assign(e.len, (uint8_t)e.fill);
+                raw = fillbuf.data();
+            }
+            w = w && fwrite(raw, 1, e.len, fout) == e.len;
+        }
+        if (!w) { fprintf(stderr, "write error\n"); return ok = false; }
+        n += blen;
+        records++;
+        return true;
+    });
+    *written = n;
+    if (r || !ok) return -1;
+    if (F.finish(n, records)) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+    return 0;
+}
+
 }  // namespace fcx_cli
+
 
 #endif  // FCX_CLI_HOST_H

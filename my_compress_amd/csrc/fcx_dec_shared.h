@@ -418,6 +418,10 @@ int verify_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, u
                uint64_t n, uint32_t block_bytes, uint32_t *d_blocks, uint64_t *stats, hipStream_t st, uint64_t rec_base);
 
 // scratch of the verification (fcx_verify.hip)
+struct VerifyScratch;
+// the end of the record group that starts at g0 (fcx_verify.hip: the bound of fcx_dctx_set_verify_group
+// over doff, the run's dec_off on the host); fcx_repair_apply_shard forms its groups with it too
+uint32_t verify_group_end(const VerifyScratch &V, const uint64_t *doff, uint32_t nblocks, uint32_t g0);
 struct VerifyScratch {
     DevBuf<uint8_t> buf;             // a group's decoded bytes, grown on demand up to the group bound
     DevBuf<uint32_t> first_diff;     // per record: the first differing byte k_vcompare found
@@ -426,6 +430,38 @@ struct VerifyScratch {
     PinnedBuf<uint64_t> host_words;
     uint64_t group_bytes = 0;        // fcx_dctx_set_verify_group (0: 256 MiB)
     uint32_t groups = 0;             // groups of the last call
+};
+
+// ---- status words of a repair call (fcx_dctx's rp.words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kRpEntries = 0;     // entries (k_rscan; an apply: the caller's count)
+constexpr uint32_t kRpData = 1;        // RAW bytes (k_rscan)
+constexpr uint32_t kRpFills = 2;       // FILL entries (k_rscan, k_rmap)
+constexpr uint32_t kRpBadEntry = 3;    // an apply: the first entry that fails k_rmap's checks (preset to ~0)
+constexpr uint32_t kRpBadRecord = 4;   // ... and the first record without an entry whose size is not its block's
+constexpr uint32_t kRpWords = 8;
+
+// fcx_repair_build_shard / fcx_repair_apply_shard behind their argument checks (fcx_repair.hip), for
+// the stream path's groups of a longer file: messages number the records from rec_base.  An apply with
+// n == kRepairLastFromRun takes the last block's length from the run itself (its entry's from + len,
+// or without one its decoded bytes) and reports the n it used in *out_len.
+constexpr uint64_t kRepairLastFromRun = ~0ull;
+int repair_build_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *d_orig,
+                     uint64_t n, uint32_t block_bytes, fcx_repair_entry *d_entries, uint8_t *d_data, uint64_t data_cap,
+                     uint32_t *nentries, uint64_t *data_bytes, uint64_t *stats, hipStream_t st, uint64_t rec_base);
+int repair_apply_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
+                     uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
+                     uint64_t data_bytes, uint8_t *d_out, uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
+
+// scratch of the repair calls (fcx_repair.hip); the stream forms' device copies of a group's entries and data
+struct RepairScratch {
+    DevBuf<uint32_t> pairs;          // verify_run's (decoded, first difference) per record
+    DevBuf<fcx_repair_entry> plan;   // k_rplan's entry per record, before the compaction
+    DevBuf<uint32_t> entry_of;       // an apply: per record its entry, or ~0
+    DevBuf<uint64_t> words;          // kRp*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<fcx_repair_entry> entries;
+    DevBuf<uint8_t> data;
+    uint64_t stats[FCX_REPAIR_STATS] = {};
 };
 
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
@@ -457,6 +493,7 @@ struct fcx_dctx {
     std::unique_ptr<fcx::Scratch78, fcx::Calls<fcx::free_scratch78>> d78;
     fcx::RangeScratch rg;
     fcx::VerifyScratch vf;
+    fcx::RepairScratch rp;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

@@ -18,6 +18,7 @@
 #include "fcx_dec_shared.h"   // lz78_decompress_shard_at
 #include "fcx_device.h"       // the compress status words a slot's hlen mirrors
 #include "fcx_host.h"
+#include "fcx_repair_file.h"
 
 using namespace fcx;
 
@@ -470,6 +471,190 @@ int fcx_decompress_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint
     if (r) return r;
     if (out_len) *out_len = m.out_pos;
     return FCX_OK;
+}
+
+}  // extern "C"
+
+// ---- the repair sidecar's stream and host forms (include/fcx.h) ----------------------
+
+namespace {
+
+// passes a read callback through and keeps the first bytes that went by: the FCX file's header, for the
+// kind of a file without records (stream_groups calls no group then)
+struct PeekRead {
+    fcx_read_fn rd;
+    void *user;
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint64_t seen;
+};
+int64_t peek_read(void *u, uint8_t *buf, uint64_t cap) {
+    PeekRead *p = (PeekRead *)u;
+    const int64_t r = p->rd(p->user, buf, cap);
+    for (int64_t i = 0; i < r && p->seen < sizeof(p->hdr); i++) p->hdr[p->seen++] = buf[i];
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fcx_repair_build_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_orig, void *user_orig,
+                            uint32_t block_bytes, uint64_t max_in, fcx_write_fn wr, void *user_wr, uint64_t *stats) {
+    if (!dctx || !rd || !rd_orig || !wr) return fail(FCX_ERR_ARG, "fcx_repair_build_stream: NULL argument");
+    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
+        return fail(FCX_ERR_ARG, "fcx_repair_build_stream: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
+    const uint64_t B = block_bytes;
+    fcx_repair_file::Writer W;
+    W.wr = wr;
+    W.user = user_wr;
+    PeekRead pk{rd, user, {}, 0};
+    bool begun = false, orig_end = false;
+    uint64_t total_n = 0, records = 0;
+    std::vector<fcx_repair_entry> ents;
+    std::vector<uint8_t> raw;
+    const int r = stream_groups(dctx, peek_read, &pk, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
+                                    hipStream_t st) -> int {
+        if (!begun) {
+            if (const int w = W.begin(lz78 ? '8' : '7', block_bytes)) return fail(w, W.err);
+            begun = true;
+        }
+        // the group's blocks of the original, staged where a decompress stages the decoded bytes
+        const uint64_t want = (uint64_t)nb * B;
+        if (want > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_repair_build_stream: staging too small");
+        const int64_t got = orig_end ? 0 : read_full(rd_orig, user_orig, x.hout, want);
+        if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
+        if ((uint64_t)got < want) orig_end = true;
+        if (((uint64_t)got + B - 1) / B != nb)
+            return fail(FCX_ERR_ARG, "fcx_repair_build_stream: the original has no bytes for record " +
+                                         std::to_string(before + ((uint64_t)got + B - 1) / B));
+        FCX_HIP(hipMemcpyAsync(x.dout, x.hout, (uint64_t)got, hipMemcpyHostToDevice, st));
+        RepairScratch &P = dctx->rp;
+        FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * (uint64_t)nb, "repair entries"));
+        FCX_TRY(P.data.reserve((uint64_t)got, "repair data"));   // (the RAW bytes are bytes of the group's blocks)
+        uint32_t ne = 0;
+        uint64_t nd = 0;
+        FCX_TRY(fcx::repair_build_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, (uint64_t)got, block_bytes, P.entries,
+                                      P.data, (uint64_t)got, &ne, &nd, nullptr, st, before));
+        ents.resize(ne);
+        raw.resize(nd);
+        if (ne) FCX_HIP(hipMemcpy(ents.data(), P.entries, sizeof(fcx_repair_entry) * (uint64_t)ne, hipMemcpyDeviceToHost));
+        if (nd) FCX_HIP(hipMemcpy(raw.data(), P.data, nd, hipMemcpyDeviceToHost));
+        for (fcx_repair_entry e : ents) {
+            const uint8_t *bytes = e.kind == FCX_REPAIR_RAW ? raw.data() + e.data_off : nullptr;
+            e.block += before;
+            if (const int w = W.add(e, bytes)) return fail(w, W.err);
+        }
+        total_n += (uint64_t)got;
+        records += nb;
+        return FCX_OK;
+    });
+    if (r) return r;
+    if (!orig_end) {
+        uint8_t one;
+        const int64_t got = rd_orig(user_orig, &one, 1);
+        if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
+        if (got) return fail(FCX_ERR_ARG, "fcx_repair_build_stream: the original has bytes after the last record");
+    }
+    if (!begun)
+        if (const int w = W.begin(pk.hdr[3] == '7' ? '7' : '8', block_bytes)) return fail(w, W.err);
+    if (const int w = W.finish(total_n, records)) return fail(w, W.err);
+    if (stats) {
+        stats[0] = total_n;
+        stats[1] = records;
+        stats[2] = W.entries;
+        stats[3] = W.data_bytes;
+    }
+    return FCX_OK;
+}
+
+int fcx_repair_apply_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_rep, void *user_rep, fcx_write_fn wr,
+                            void *user_out, uint64_t max_in, uint64_t *total_out) {
+    if (!dctx || !rd || !rd_rep || !wr) return fail(FCX_ERR_ARG, "fcx_repair_apply_stream: NULL argument");
+    fcx_repair_file::Reader F;
+    F.rd = rd_rep;
+    F.user = user_rep;
+    if (const int f = F.open()) return fail(f, F.err);
+    const uint32_t B = F.block_bytes;
+    PeekRead pk{rd, user, {}, 0};
+    uint64_t tout = 0, records = 0;
+    bool short_seen = false;
+    std::vector<fcx_repair_entry> ents;
+    std::vector<uint8_t> raw;
+    const int r = stream_groups(dctx, peek_read, &pk, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
+                                    hipStream_t st) -> int {
+        if ((lz78 ? '8' : '7') != F.kind) return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        if (short_seen)
+            return fail(FCX_ERR_FORMAT, "repair: record " + std::to_string(before - 1) +
+                                            " gives a block shorter than the block size and is not the last");
+        if ((uint64_t)nb * B > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_repair_apply_stream: staging too small");
+        // the group's entries: the sections that hold them are read now, and no further
+        ents.clear();
+        raw.clear();
+        for (;;) {
+            fcx_repair_entry e;
+            const uint8_t *bytes = nullptr;
+            const int g = F.next(before, before + nb, &e, &bytes);
+            if (g < 0) return fail(g, F.err);
+            if (g == 0) break;
+            e.block -= before;
+            e.data_off = 0;
+            if (e.kind == FCX_REPAIR_RAW) {
+                e.data_off = raw.size();
+                raw.insert(raw.end(), bytes, bytes + e.len);
+            }
+            ents.push_back(e);
+        }
+        RepairScratch &P = dctx->rp;
+        FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * ents.size(), "repair entries"));
+        FCX_TRY(P.data.reserve(raw.size(), "repair data"));
+        if (!ents.empty())
+            FCX_HIP(hipMemcpyAsync(P.entries, ents.data(), sizeof(fcx_repair_entry) * ents.size(), hipMemcpyHostToDevice, st));
+        if (!raw.empty()) FCX_HIP(hipMemcpyAsync(P.data, raw.data(), raw.size(), hipMemcpyHostToDevice, st));
+        uint64_t n = 0;
+        FCX_TRY(fcx::repair_apply_run(dctx, lz78 ? '8' : '7', x.din, used, nb, fcx::kRepairLastFromRun, B, P.entries,
+                                      (uint32_t)ents.size(), P.data, raw.size(), x.dout, out_cap, &n, st, before));
+        if (n < (uint64_t)nb * B) short_seen = true;
+        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, n, hipMemcpyDeviceToHost, st));
+        FCX_HIP(hipStreamSynchronize(st));
+        const int w = wr(user_out, x.hout, n);
+        if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
+        tout += n;
+        records += nb;
+        return FCX_OK;
+    });
+    if (r) return r;
+    if (records == 0 && pk.seen == sizeof(pk.hdr) && (pk.hdr[3] == '7' ? '7' : '8') != F.kind)
+        return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+    if (const int f = F.finish(tout, records)) return fail(f, F.err);
+    if (total_out) *total_out = tout;
+    return FCX_OK;
+}
+
+int fcx_repair_build_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *orig, uint64_t n,
+                          uint32_t block_bytes, uint8_t *repair, uint64_t cap, uint64_t *repair_len) {
+    if (!dctx || !in || (n && !orig) || !repair_len || (cap && !repair))
+        return fail(FCX_ERR_ARG, "fcx_repair_build_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0}, org{orig, n, 0, nullptr, 0, 0}, out{nullptr, 0, 0, repair, cap, 0};
+    const int r = fcx_repair_build_stream(dctx, mem_read, &comp, mem_read, &org, block_bytes, in_len - FCX_HEADER_BYTES, mem_write,
+                                          &out, nullptr);
+    *repair_len = out.out_pos;
+    if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_repair_build_host: repair capacity too small");
+    return r;
+}
+
+int fcx_repair_apply_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
+                          uint8_t *out, uint64_t cap, uint64_t *out_len) {
+    if (!dctx || !in || !repair || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_repair_apply_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0}, rep{repair, repair_len, 0, nullptr, 0, 0}, dst{nullptr, 0, 0, out, cap, 0};
+    const int r = fcx_repair_apply_stream(dctx, mem_read, &comp, mem_read, &rep, mem_write, &dst, in_len - FCX_HEADER_BYTES,
+                                          nullptr);
+    *out_len = dst.out_pos;
+    if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_repair_apply_host: output capacity too small");
+    return r;
 }
 
 }  // extern "C"

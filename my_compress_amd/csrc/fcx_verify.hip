@@ -21,6 +21,7 @@
 #include "fcx.h"
 #include "fcx_dec_shared.h"
 #include "fcx_device.h"   // wave_max_dpp, wave_sum_u64
+#include "fcx_ld16.h"     // ld16_shifted
 
 namespace fcx {
 
@@ -30,28 +31,22 @@ constexpr uint32_t kVSteps = kVChunk / (16 * kVThreads);  // 16-byte pieces per 
 constexpr uint32_t kVGroupRecords = 1u << 20;             // records per group at most (the grid)
 constexpr uint64_t kVGroupBytes = 256ull << 20;           // decoded bytes per group by default
 
+// groups of consecutive records whose decoded bytes fit the bound, a record of no bytes counted
+// as one (so a bound of 1 makes every record a group); a record larger than the bound is a group
+// of its own.  doff: the run's dec_off on the host; returns the end of the group that starts at g0.
+uint32_t verify_group_end(const VerifyScratch &V, const uint64_t *doff, uint32_t nblocks, uint32_t g0) {
+    const uint64_t bound = V.group_bytes ? V.group_bytes : kVGroupBytes;
+    uint32_t g1 = g0;
+    uint64_t cost = 0;
+    do {
+        cost += std::max<uint64_t>(doff[g1 + 1] - doff[g1], 1);
+        g1++;
+    } while (g1 < nblocks && g1 - g0 < kVGroupRecords && cost + std::max<uint64_t>(doff[g1 + 1] - doff[g1], 1) <= bound);
+    return g1;
+}
+
 // minimum over the 64 lanes (uniform); every lane of the wave must be active
 __device__ inline uint32_t wave_min_dpp(uint32_t v) { return ~wave_max_dpp(~v); }
-
-// the 16 bytes at p + i of a byte range that starts at p (any alignment): two aligned 16-byte loads and
-// a funnel shift.  `sh` = (address of p + i) & 15 is the same for every piece of a block, since
-// pieces are 16 bytes apart.  The caller has checked that the aligned 32 bytes lie inside the block.
-__device__ inline uint4 ld16_shifted(const uint8_t *a, uint32_t sh) {
-    const uint4 *q = (const uint4 *)(a - sh);
-    const uint4 lo = q[0];
-    if (sh == 0) return lo;
-    const uint4 hi = q[1];
-    const uint32_t bs = sh & 3;
-    uint32_t w0, w1, w2, w3, w4;
-    switch (sh >> 2) {   // (uniform over the workgroup)
-    case 0: w0 = lo.x; w1 = lo.y; w2 = lo.z; w3 = lo.w; w4 = hi.x; break;
-    case 1: w0 = lo.y; w1 = lo.z; w2 = lo.w; w3 = hi.x; w4 = hi.y; break;
-    case 2: w0 = lo.z; w1 = lo.w; w2 = hi.x; w3 = hi.y; w4 = hi.z; break;
-    default: w0 = lo.w; w1 = hi.x; w2 = hi.y; w3 = hi.z; w4 = hi.w; break;
-    }
-    return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, bs), __builtin_amdgcn_alignbyte(w2, w1, bs),
-                      __builtin_amdgcn_alignbyte(w3, w2, bs), __builtin_amdgcn_alignbyte(w4, w3, bs));
-}
 
 // index of the first differing byte of two 16-byte pieces, 16 if none
 __device__ inline uint32_t first_diff16(uint4 a, uint4 b) {
@@ -189,19 +184,7 @@ int verify_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, u
     FCX_HIP(hipMemsetAsync(V.words, 0, 8 * kVwWords, st));
     FCX_HIP(hipMemsetAsync(V.words + kVwFirst, 0xFF, 8, st));
     FCX_HIP(hipStreamSynchronize(st));
-    // groups of consecutive records whose decoded bytes fit the bound, a record of no bytes counted
-    // as one (so a bound of 1 makes every record a group); a record larger than the bound is a group
-    // of its own
-    const uint64_t bound = V.group_bytes ? V.group_bytes : kVGroupBytes;
-    auto group_end = [&](uint32_t g0) {
-        uint32_t g1 = g0;
-        uint64_t cost = 0;
-        do {
-            cost += std::max<uint64_t>(doff[g1 + 1] - doff[g1], 1);
-            g1++;
-        } while (g1 < nblocks && g1 - g0 < kVGroupRecords && cost + std::max<uint64_t>(doff[g1 + 1] - doff[g1], 1) <= bound);
-        return g1;
-    };
+    auto group_end = [&](uint32_t g0) { return verify_group_end(V, doff.data(), nblocks, g0); };
     uint64_t need = 0;
     uint32_t ngroups = 0;
     for (uint32_t g0 = 0; g0 < nblocks; g0 = group_end(g0), ngroups++) need = std::max(need, doff[group_end(g0)] - doff[g0]);
