@@ -438,7 +438,8 @@ int fcx_repair_build_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint6
  * straight to its place in d_out, a group with entries into the context's bounded buffer, from where
  * its blocks are assembled.  On an error d_out[0, n) is unspecified; d_out[n, cap) is never written.
  * What these checks cannot see: a repair made for another file whose entries happen to fit gives wrong
- * bytes.  The FCXR file's header and trailer (kind, block size, n, records) guard the file forms.
+ * bytes.  The FCXR file's header and trailer (kind, block size, n, records) guard the file forms, and a
+ * content digest (fcx_check_*, below) tells such a repair from the right one.
  * Stage table with profiling: index, check, decode, assemble. */
 int fcx_repair_apply_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
                            uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries,
@@ -479,6 +480,95 @@ int fcx_repair_build_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, con
                           uint32_t block_bytes, uint8_t *repair, uint64_t cap, uint64_t *repair_len);
 int fcx_repair_apply_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
                           uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* ---- content digests: one CRC-32 per block of the original, and a test that needs no original ----
+ * The verification and the repair above read the original again.  A digest is what stays of it: the
+ * CRC-32 (CRC-32/ISO-HDLC, zlib's crc32) of every block, made while the bytes are at hand.  With it the
+ * records, and a repair if there is one, can be tested at any later time: does block k, decoded and
+ * repaired, still have its length and its CRC-32?  The values are computed on the device; only compressed
+ * bytes cross to it for a test, and no decoded byte leaves it. */
+
+/* CRC-32 (zlib's) of every block of n device bytes cut at block_bytes: d_crc[0, ceil(n/B)); *whole (host,
+ * may be NULL) = the CRC-32 of all n bytes.  n == 0: no block, *whole = 0, no device memory touched.
+ * Only [d_data, d_data + n) is read.  With whole the call synchronises `stream`; without, the values are
+ * ready when the stream's work is.  FCX_ERR_ARG for a NULL ctx, d_data or d_crc with n > 0, block_bytes
+ * outside [1, FCX_MAX_BLOCK_BYTES], more than 2^31 - 1 blocks. */
+int fcx_digest_shard(fcx_dctx *ctx, const uint8_t *d_data, uint64_t n, uint32_t block_bytes, uint32_t *d_crc,
+                     uint32_t *whole, void *stream);
+
+/* The same sum over nseg segments [d_off[k], d_off[k + 1]) of d_data (d_off: nseg + 1 ascending u64 on the
+ * device; a segment starts at any byte and holds fewer than 2^32): d_crc[k], 0 for an empty segment.  Only
+ * the bytes of the segments are read.  Reads the offsets back first (synchronises `stream`), then enqueues. */
+int fcx_digest_segments(fcx_dctx *ctx, const uint8_t *d_data, const uint64_t *d_off, uint32_t nseg, uint32_t *d_crc,
+                        void *stream);
+/* The host mirror: zlib's crc32(crc, p, n) (start with 0; the sum continues) and crc32_combine, the CRC-32
+ * of A | B from those of A and B and the length of B.  No device. */
+uint32_t fcx_crc32(uint32_t crc, const uint8_t *p, uint64_t n);
+uint32_t fcx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* fcx_verify_shard with digests in place of the original.  Record k, decoded, and when an entry of the
+ * given repair names block k, repaired as fcx_repair_apply_shard would, is block k.  It passes when its
+ * length is the block's length (from n and block_bytes) and its CRC-32 equals d_crc[k].
+ * d_blocks (2*nblocks u32 or NULL): the block's resulting length, its CRC-32.
+ * stats[FCX_VERIFY_STATS]: blocks, failing blocks, first failing block (UINT64_MAX: none), blocks whose
+ * length is wrong, original bytes in failing blocks, decoded bytes in total.
+ * nentries == 0: no repair.  Entries are validated exactly as fcx_repair_apply_shard validates them
+ * (same FCX_ERR_FORMAT texts).  But a record without an entry whose size is wrong is a failing block here,
+ * not an error: that is what a test is for.  FCX_ERR_ARG / FCX_ERR_FORMAT otherwise as fcx_verify_shard.
+ * The records are indexed and decoded in fcx_verify_shard's groups into the context's bounded buffer
+ * (fcx_dctx_set_verify_group applies; the result does not depend on it); nothing is assembled: a repaired
+ * block's CRC-32 is combined from that of its decoded prefix and that of its RAW bytes, or of its fill
+ * byte, which is computed without memory.  Only d_blocks is written.  Synchronises `stream`.  Stage table
+ * with profiling: index, decode, digest, summary. */
+int fcx_check_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
+                    uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries,
+                    const uint8_t *d_data, uint64_t data_bytes, const uint32_t *d_crc,
+                    uint32_t *d_blocks, uint64_t *stats, void *stream);
+/* Counters of the last fcx_digest_shard / fcx_check_shard call on the context (the host and stream forms:
+ * of their last shard or group), min(n, FCX_DIGEST_STATS) values: segments digested, bytes digested (a
+ * check: the decoded bytes and the repair's data, of which a repaired record's kept prefix is a part),
+ * groups decoded, blocks repaired before digesting. */
+#define FCX_DIGEST_STATS 4
+int fcx_dctx_digest_stats(fcx_dctx *ctx, uint64_t *out, int n);
+/* Testing and timing: the bytes a lane puts through the slicing tables per round in later digest and check
+ * calls: 4 (the default, also for 0), 8 or 16, with as many 1 KiB tables in LDS.  The values are the same. */
+int fcx_dctx_set_digest_slice(fcx_dctx *ctx, uint32_t bytes);
+
+/* The FCXD file, all fields little endian.  Header, 16 bytes: "FCXD", u8 version 1, u8 0, u16 0, u32
+ * block_bytes, u32 0.  Sections: u32 count (1..4096), u32 0, then count u32 CRC-32 values in block order;
+ * a count of 0 (with its u32 0) ends the sections.  Trailer: u64 n, u64 blocks, u32 CRC-32 of the whole
+ * original (what crc32, zip and zlib.crc32 give for it), u32 CRC-32 of the values as written.  The writer is
+ * canonical: every section but the last holds exactly 4096 values.  The reader takes any sectioning within
+ * 1..4096, needs no seek and holds one section at a time; FCX_ERR_FORMAT for a bad magic or version,
+ * nonzero reserved fields, a count above 4096, truncation anywhere, a trailer whose n, blocks or CRCs
+ * disagree with what was read, blocks != ceil(n / block_bytes), bytes behind the trailer. */
+#define FCX_DIGEST_HEADER_BYTES 16u
+#define FCX_DIGEST_TRAILER_BYTES 24u
+#define FCX_DIGEST_SECTION 4096u
+#define FCX_DIGEST_FILE_STATS 3   /* the trailer: original bytes, blocks, CRC-32 of the whole */
+/* Reads the original to its end in shards of whole blocks, digests each on the device and writes the
+ * canonical FCXD file.  stats (FCX_DIGEST_FILE_STATS values, may be NULL): the trailer's. */
+int fcx_digest_stream(fcx_dctx *ctx, fcx_read_fn read_orig, void *user_orig, uint32_t block_bytes,
+                      fcx_write_fn write_digest, void *user_digest, uint64_t *stats);
+/* fcx_verify_stream's twin without the original: reads the FCX7 / FCX8 file in its record groups, for each
+ * group the FCXD values of its blocks and, when read_repair is given, the FCXR sections that hold its
+ * entries, and checks the group (fcx_check_shard).  on_block (may be NULL) is called for every failing
+ * block in order with the block's number, its length by the digest file, its resulting length and, in the
+ * place of the first difference, its CRC-32.  A record behind the digest file's last block fails, with
+ * block length 0.  Blocks of the digest file behind the last record are reported as fcx_verify_stream
+ * reports bytes behind the last record: their bytes are added to stats[4], and on_block is called once more,
+ * last, with block = stats[0], their bytes as block_len, 0 and 0.  So the file passes exactly when
+ * stats[1] == 0 and stats[4] == 0.  FCX_ERR_FORMAT for a malformed FCXD or FCXR file, an FCXR file of the
+ * other codec or of another block size than the FCXD file's, or a trailer of either that disagrees. */
+int fcx_check_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, fcx_read_fn read_repair, void *user_repair,
+                     fcx_read_fn read_digest, void *user_digest, uint64_t max_in, fcx_verify_fn on_block, void *user_cb,
+                     uint64_t *stats);
+/* on memory, through the stream forms: `orig` the original, `in` a whole FCX7 / FCX8 file, `repair` a whole
+ * FCXR file or NULL, `digest` a whole FCXD file */
+int fcx_digest_host(fcx_dctx *ctx, const uint8_t *orig, uint64_t n, uint32_t block_bytes, uint8_t *digest, uint64_t cap,
+                    uint64_t *digest_len);
+int fcx_check_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
+                   const uint8_t *digest, uint64_t digest_len, fcx_verify_fn on_block, void *user_cb, uint64_t *stats);
 
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so

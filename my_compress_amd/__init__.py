@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -152,6 +152,27 @@ def lib():
                                             c_u8p, ctypes.c_uint64, P64]
         L.fcx_repair_apply_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64, c_u8p,
                                             ctypes.c_uint64, P64]
+    if hasattr(L, "fcx_digest_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        P32 = ctypes.POINTER(ctypes.c_uint32)
+        L.fcx_digest_shard.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, P32,
+                                       ctypes.c_void_p]
+        L.fcx_check_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                      ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, P64, ctypes.c_void_p]
+        L.fcx_digest_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+        L.fcx_crc32.argtypes = [ctypes.c_uint32, c_u8p, ctypes.c_uint64]
+        L.fcx_crc32.restype = ctypes.c_uint32
+        L.fcx_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+        L.fcx_crc32_combine.restype = ctypes.c_uint32
+        L.fcx_dctx_digest_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+        L.fcx_dctx_set_digest_slice.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.fcx_digest_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint32, WRITE_FN, ctypes.c_void_p, P64]
+        L.fcx_check_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, READ_FN, ctypes.c_void_p, READ_FN,
+                                       ctypes.c_void_p, ctypes.c_uint64, VERIFY_FN, ctypes.c_void_p, P64]
+        L.fcx_digest_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint32, c_u8p, ctypes.c_uint64, P64]
+        L.fcx_check_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64,
+                                     VERIFY_FN, ctypes.c_void_p, P64]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -247,6 +268,37 @@ def parse_repair(blob: bytes) -> dict:
         raise ValueError("bytes behind the FCXR trailer")
     return {"kind": chr(kind), "block_bytes": block_bytes, "sections": sections,
             "trailer": dict(zip(("n", "records", "entries", "data_bytes"), trailer))}
+
+
+# the content digest (include/fcx.h): the FCXD file
+DIGEST_HEADER_BYTES, DIGEST_TRAILER_BYTES, DIGEST_SECTION = 16, 24, 4096
+
+
+def parse_digest(blob: bytes) -> dict:
+    """an FCXD file taken apart, for tests: block_bytes, the sections as lists of CRC-32 values, and the
+    trailer (n, blocks, crc32 of the whole original, crc32 of the values).  Checks the layout only
+    (ValueError), not the rules of the reader."""
+    if len(blob) < DIGEST_HEADER_BYTES or blob[:4] != b"FCXD":
+        raise ValueError("not an FCXD file")
+    version, zero, zero1, block_bytes, zero2 = struct.unpack_from("<BBHII", blob, 4)
+    if version != 1 or zero or zero1 or zero2:
+        raise ValueError("bad FCXD header")
+    q, sections = DIGEST_HEADER_BYTES, []
+    while True:
+        if q + 8 > len(blob):
+            raise ValueError("truncated FCXD file")
+        count, zero = struct.unpack_from("<II", blob, q)
+        q += 8
+        if count == 0:
+            break
+        if zero or count > DIGEST_SECTION or q + 4 * count > len(blob):
+            raise ValueError("bad FCXD section")
+        sections.append(list(struct.unpack_from("<%dI" % count, blob, q)))
+        q += 4 * count
+    if q + DIGEST_TRAILER_BYTES != len(blob):
+        raise ValueError("the FCXD trailer is not the last %d bytes" % DIGEST_TRAILER_BYTES)
+    return {"block_bytes": block_bytes, "sections": sections,
+            "trailer": dict(zip(("n", "blocks", "crc32", "values_crc32"), struct.unpack_from("<QQII", blob, q)))}
 
 
 def _stream_fns(src, sink):
@@ -607,6 +659,90 @@ class DContext:
                "fcx_repair_apply_host")
         return out.raw[:got.value]
 
+    # ---- content digests (fcx_digest_* / fcx_check_*): a CRC-32 per block, and the test without the original ----
+    DIGEST_STATS = ("segments", "bytes", "groups", "repaired")
+
+    def digest_shard(self, d_data: int, n: int, block_bytes: int, d_crc: int, stream: int = 0, whole: bool = True):
+        """the CRC-32 (zlib's) of every block of the n device bytes at d_data to d_crc (ceil(n / block_bytes)
+        u32 on the device); returns the CRC-32 of all n bytes, or with whole=False None without waiting"""
+        w = ctypes.c_uint32(0)
+        _check(lib().fcx_digest_shard(self._h, ctypes.c_void_p(d_data or None), n, block_bytes, ctypes.c_void_p(d_crc or None),
+                                      ctypes.byref(w) if whole else None, ctypes.c_void_p(stream)), "fcx_digest_shard")
+        return int(w.value) if whole else None
+
+    def digest_segments(self, d_data: int, d_off: int, nseg: int, d_crc: int, stream: int = 0):
+        """the CRC-32 of the nseg segments [off[k], off[k + 1]) of d_data (d_off: nseg + 1 u64 on the device) to
+        d_crc (nseg u32 on the device); enqueued on the stream"""
+        _check(lib().fcx_digest_segments(self._h, ctypes.c_void_p(d_data or None), ctypes.c_void_p(d_off or None), nseg,
+                                         ctypes.c_void_p(d_crc or None), ctypes.c_void_p(stream)), "fcx_digest_segments")
+
+    def check_shard(self, d_rec: int, rec_len: int, nblocks: int, kind: str, n: int, block_bytes: int, d_crc: int,
+                    d_entries: int = 0, nentries: int = 0, d_data: int = 0, data_bytes: int = 0, d_blocks: int = 0,
+                    stream: int = 0) -> dict:
+        """device records (no header), repaired by the given entries when there are any, against the CRC-32
+        of the nblocks blocks of the n bytes they were compressed from (d_crc, u32 on the device); d_blocks
+        (2 * nblocks u32 on the device, or 0) receives per record the resulting length and CRC-32.  Returns
+        the stats: blocks, differ (the failing blocks), first, size_differs, bytes, decoded."""
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        _check(lib().fcx_check_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, n, block_bytes,
+                                     ctypes.c_void_p(d_entries or None), nentries, ctypes.c_void_p(d_data or None), data_bytes,
+                                     ctypes.c_void_p(d_crc or None), ctypes.c_void_p(d_blocks or None), vals,
+                                     ctypes.c_void_p(stream)), "fcx_check_shard")
+        return self._verify_stats(vals)
+
+    def digest_stats(self) -> dict:
+        """counters of the last digest or check call (fcx_dctx_digest_stats)"""
+        n = len(self.DIGEST_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_digest_stats(self._h, vals, n), "fcx_dctx_digest_stats")
+        return dict(zip(self.DIGEST_STATS, [int(v) for v in vals]))
+
+    def set_digest_slice(self, nbytes: int):
+        """testing and timing: bytes per slicing round of the CRC kernel in later calls (4, 8, 16; 0: the default)"""
+        _check(lib().fcx_dctx_set_digest_slice(self._h, nbytes), "fcx_dctx_set_digest_slice")
+
+    def digest_stream(self, orig, sink, block_bytes: int = BLOCK_BYTES) -> dict:
+        """the original from orig (a binary reader) -> its canonical FCXD file to sink (a binary writer);
+        returns the trailer: n, blocks, crc32"""
+        ro, _ = _stream_fns(orig, None)
+        _, wr = _stream_fns(None, sink)
+        vals = (ctypes.c_uint64 * 3)()
+        _check(lib().fcx_digest_stream(self._h, ro, None, block_bytes, wr, None, vals), "fcx_digest_stream")
+        return dict(zip(("n", "blocks", "crc32"), [int(v) for v in vals]))
+
+    def check_stream(self, src, digest, repair=None, max_in: int = 0):
+        """a whole FCX7 or FCX8 file from src, its FCXD file from digest and, when given, its FCXR file from
+        repair (binary readers); returns (stats, [(block, its length by the digest file, resulting length,
+        resulting CRC-32)] of the failing blocks).  Blocks of the digest file behind the last record come
+        last, as block number stats["blocks"] with their bytes.  The file passes when stats["differ"] == 0 and
+        stats["bytes"] == 0."""
+        rd, _ = _stream_fns(src, None)
+        rg, _ = _stream_fns(digest, None)
+        rr = _stream_fns(repair, None)[0] if repair is not None else ctypes.cast(None, READ_FN)
+        bad = []
+        cb = VERIFY_FN(lambda _u, k, blen, got, crc: bad.append((int(k), int(blen), int(got), int(crc))))
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        _check(lib().fcx_check_stream(self._h, rd, None, rr, None, rg, None, max_in, cb, None, vals), "fcx_check_stream")
+        return self._verify_stats(vals), bad
+
+    def digest_host(self, data: bytes, block_bytes: int = BLOCK_BYTES) -> bytes:
+        """the FCXD file of `data` in blocks of block_bytes"""
+        nb = (len(data) + block_bytes - 1) // block_bytes
+        cap = DIGEST_HEADER_BYTES + DIGEST_TRAILER_BYTES + 8 + 4 * nb + 8 * (nb // DIGEST_SECTION + 1)
+        out = ctypes.create_string_buffer(cap)
+        got = ctypes.c_uint64()
+        _check(lib().fcx_digest_host(self._h, data, len(data), block_bytes, out, cap, ctypes.byref(got)), "fcx_digest_host")
+        return out.raw[:got.value]
+
+    def check_host(self, blob: bytes, digest: bytes, repair: bytes = None):
+        """check_stream on memory: the whole file `blob`, its FCXD file and, when given, its FCXR file"""
+        bad = []
+        cb = VERIFY_FN(lambda _u, k, blen, got, crc: bad.append((int(k), int(blen), int(got), int(crc))))
+        vals = (ctypes.c_uint64 * len(self.VERIFY_STATS))()
+        _check(lib().fcx_check_host(self._h, blob, len(blob), repair, len(repair) if repair is not None else 0, digest,
+                                    len(digest), cb, None, vals), "fcx_check_host")
+        return self._verify_stats(vals), bad
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -682,6 +818,37 @@ def decompress_repaired(blob: bytes, repair: bytes, device: int = 0) -> bytes:
     ctx = DContext(device)
     try:
         return ctx.repair_apply_host(blob, repair)
+    finally:
+        ctx.close()
+
+
+def crc32(data: bytes, crc: int = 0) -> int:
+    """the host mirror of the device digest: zlib.crc32(data, crc)"""
+    return int(lib().fcx_crc32(crc, data, len(data)))
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """the CRC-32 of A + B from those of A and B and len(B)"""
+    return int(lib().fcx_crc32_combine(crc_a, crc_b, len_b))
+
+
+def digest(data: bytes, block_bytes: int = BLOCK_BYTES, device: int = 0) -> bytes:
+    """the content digest (an FCXD file) of `data` in blocks of block_bytes: the CRC-32 of every block and of the
+    whole, computed on the GPU; with it check(blob, ...) tests a compressed file without `data`"""
+    ctx = DContext(device)
+    try:
+        return ctx.digest_host(data, block_bytes)
+    finally:
+        ctx.close()
+
+
+def check(blob: bytes, digest: bytes, repair: bytes = None, device: int = 0):
+    """does the FCX7 or FCX8 file `blob`, mended by its FCXR file when one is given, still give the bytes the FCXD
+    file `digest` was made from?  Returns (stats, failing blocks) as DContext.check_stream; it does when
+    stats["differ"] == 0 and stats["bytes"] == 0"""
+    ctx = DContext(device)
+    try:
+        return ctx.check_host(blob, digest, repair)
     finally:
         ctx.close()
 

@@ -32,6 +32,17 @@
 //                   otherwise (decompress): read the sidecar and write the repaired output, the original bytes.
 //                   Not with --range or --list.  Prints "repair: E entries, D data bytes for R blocks" when
 //                   it writes one.  Without a HIP device both run on the host decoder for FCX7 and fail for FCX8.
+// Content digest (an FCXD file: the CRC-32 of every block of the original, and of the whole as crc32 and zip
+// print it), and the test that needs no original (fcx_check_stream: every record decoded on the device, a
+// repair applied in the sum, each block's CRC-32 against the file's):
+//   --digest FILE   with -c: after the output is closed (and after --verify's and --repair's passes), a pass
+//                   over the input writes the file; with --compare ORIGINAL: also writes ORIGINAL's;
+//                   otherwise (decompress, [--repair R]): the ordinary decompress to -o, then the test in a
+//                   second pass over -i.  Prints "digest: B blocks, crc32 XXXXXXXX" when it writes one.
+//   --test          decompress mode with --digest FILE [--repair R]: the test alone, no -o file.
+//                   Not with -c, --compare, --range or --list; --digest not with --range or --list.
+// One line per failing block, then the verdict; exit status 0 for OK, 1 for FAIL.  Without a HIP device the
+// FCX7 directions run on the host decoder and the host CRC-32, with the same file bytes and lines; FCX8 fails.
 #include <getopt.h>
 
 #include <chrono>
@@ -51,7 +62,9 @@ static int usage() {
             "usage: ./my_compress -i[or --file_in] <input file name> [-o[or --file_out] <output file name>] "
             "[-c (or --compress) <lz77/lz78>] [-b (or --block) <bytes>] [-d (or --device) <hip device>] "
             "[-g (or --gpus) <count>] [--verify (with -c)] [--range <offset>:<length> | --list | --compare <original> "
-            "(decompress only)] [--repair <sidecar file> (written with -c or --compare, read by a decompress)]\n");
+            "(decompress only)] [--repair <sidecar file> (written with -c or --compare, read by a decompress)] "
+            "[--digest <digest file> (written with -c or --compare, checked by a decompress)] "
+            "[--test (decompress with --digest: check only, no output file)]\n");
     return -1;
 }
 
@@ -382,6 +395,82 @@ static int do_repair_build(FILE *fcomp, const char *orig_path, int device, uint3
     return r;
 }
 
+// --digest with -c or --compare: the FCXD file of the original, by fcx_digest_stream on the device, or
+// without one by the host CRC-32
+static int do_digest_build(const char *orig_path, int device, uint32_t block, const char *digest_path) {
+    FILE *forig = fopen(orig_path, "rb");
+    if (!forig) { printf("open: %s Fail!!\n", orig_path); return -1; }
+    FILE *fdig = fopen(digest_path, "wb");
+    if (!fdig) { printf("open: %s Fail!!\n", digest_path); fclose(forig); return -1; }
+    uint64_t stats[FCX_DIGEST_FILE_STATS] = {};
+    fcx_dctx *d = nullptr;
+    int r;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        fprintf(stderr, "fcx: %s; digesting on the host\n", fcx_last_error());
+        r = fcx_cli::host_digest_build(forig, block, fdig, stats);
+    } else {
+        r = fcx_digest_stream(d, file_read, forig, block, fcx_cli::stdio_write, fdig, stats);
+        fcx_dctx_destroy(d);
+        if (r) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            r = -1;
+        }
+    }
+    fclose(forig);
+    if (fclose(fdig) != 0 && r == 0) { fprintf(stderr, "write error\n"); r = -1; }
+    if (r == 0) fcx_cli::digest_totals(stats[1], (uint32_t)stats[2]);
+    return r;
+}
+
+// --test, and the second pass of a decompress with --digest: the compressed file fcomp (and its repair
+// frep, may be null) against the FCXD file, by fcx_check_stream on the device, or for an FCX7 file
+// without one by the host decoder
+static int do_check(FILE *fcomp, FILE *frep, const char *digest_path, int device) {
+    FILE *fdig = fopen(digest_path, "rb");
+    if (!fdig) { printf("open: %s Fail!!\n", digest_path); return -1; }
+    std::vector<uint32_t> expected;
+    if (fcx_cli::load_digest(fdig, &expected)) { fclose(fdig); return -1; }
+    rewind(fcomp);
+    if (frep) rewind(frep);
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    int r = -1;
+    fcx_dctx *d = nullptr;
+    if (fread(hdr, 1, sizeof(hdr), fcomp) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+    } else if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+    } else if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        } else {
+            fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+            r = fcx_cli::host_check(fcomp, frep, fdig, nblocks, nullptr);
+        }
+    } else {
+        uint64_t max_in = 0, stats[FCX_VERIFY_STATS];
+        if (fseek(fcomp, 0, SEEK_END) == 0 && ftell(fcomp) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fcomp) - FCX_HEADER_BYTES;
+        rewind(fcomp);
+        std::vector<Differing> bad;
+        const int v = fcx_check_stream(d, file_read, fcomp, frep ? file_read : nullptr, frep, file_read, fdig, max_in, on_differing,
+                                       &bad, stats);
+        fcx_dctx_destroy(d);
+        if (v) {
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        } else {
+            for (const Differing &b : bad) {
+                if (b.block == stats[0]) fcx_cli::check_extra(b.len);   // (blocks of the digest file behind the last record)
+                else fcx_cli::check_line(b.block, b.dec, b.len, b.first, b.block < expected.size() ? &expected[b.block] : nullptr);
+            }
+            r = fcx_cli::check_totals(stats[1], stats[0], stats[4]);
+        }
+    }
+    fclose(fdig);
+    return r;
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -460,14 +549,16 @@ int main(int argc, char **argv) {
                                            {"verify", no_argument, nullptr, 'V'},
                                            {"compare", required_argument, nullptr, 'C'},
                                            {"repair", required_argument, nullptr, 'P'},
+                                           {"digest", required_argument, nullptr, 'D'},
+                                           {"test", no_argument, nullptr, 'T'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
     uint32_t block = FCX_DEFAULT_BLOCK_BYTES;
     int device = 0, ngpus = 1, opt;
     bool dist = false;   // -g given: the RCCL multi-GPU path (also at -g 1)
-    bool verify = false, compare = false;
-    std::string original, repair;
+    bool verify = false, compare = false, test = false;
+    std::string original, repair, digest;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -489,6 +580,8 @@ int main(int argc, char **argv) {
         case 'V': verify = true; break;
         case 'C': compare = true; original = optarg; break;
         case 'P': repair = optarg; break;
+        case 'D': digest = optarg; break;
+        case 'T': test = true; break;
         default: return usage();
         }
     }
@@ -496,13 +589,15 @@ int main(int argc, char **argv) {
     if ((want.range || want.list) && (compress || (want.range && want.list))) return usage();
     if ((compare && (compress || want.range || want.list || verify)) || (verify && !compress)) return usage();
     if (!repair.empty() && (want.range || want.list)) return usage();
+    if (!digest.empty() && (want.range || want.list)) return usage();
+    if (test && (digest.empty() || compress || compare || want.range || want.list)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    const bool no_out = want.list || compare;   // (--list and --compare write no file)
+    const bool no_out = want.list || compare || test;   // (--list, --compare and --test write no file)
     FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
     if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
@@ -516,6 +611,7 @@ int main(int argc, char **argv) {
             rewind(fin);
             if (do_repair_build(fin, original.c_str(), device, block, repair.c_str())) r = -1;
         }
+        if (!digest.empty() && r >= 0 && do_digest_build(original.c_str(), device, block, digest.c_str())) r = -1;
         fclose(fin);
         return r;
     }
@@ -527,7 +623,12 @@ int main(int argc, char **argv) {
     int r = compress ? (lz77 ? (dist ? do_compress_dist(fin, fout, block, device, ngpus)
                                      : do_compress(fin, fout, block, device))
                              : compress_lz78(fin, fout, block))
-                     : do_decompress(fin, fout, device, want, frep);
+                     : test ? 0 : do_decompress(fin, fout, device, want, frep);
+    if (!compress && !digest.empty() && r >= 0) {   // the test: alone, or the second pass over -i after the decompress
+        if (fout) fflush(fout);
+        const int v = do_check(fin, frep, digest.c_str(), device);
+        if (v) r = v;   // (a decompress whose sizes differ keeps its status when the test could pass)
+    }
     fclose(fin);
     if (fout) fclose(fout);
     if (frep) fclose(frep);
@@ -544,6 +645,10 @@ int main(int argc, char **argv) {
         (void)hipSetDevice(device);
         if (do_repair_build(fcomp, file_in.c_str(), device, block, repair.c_str())) r = -1;
         fclose(fcomp);
+    }
+    if (compress && !digest.empty() && r >= 0) {   // the digest of the input, after the passes above
+        (void)hipSetDevice(device);
+        if (do_digest_build(file_in.c_str(), device, block, digest.c_str())) r = -1;
     }
     return r;
 }

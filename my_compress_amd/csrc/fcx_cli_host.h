@@ -1,7 +1,7 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
-// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare and --repair.  Host code
+// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair and --digest.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
-// (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp).
+// (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -12,6 +12,8 @@
 #include <vector>
 
 #include "fcx.h"
+#include "fcx_crc32.h"
+#include "fcx_digest_file.h"
 #include "fcx_repair_file.h"
 
 namespace fcx_cli {
@@ -266,6 +268,129 @@ inline int host_repair_apply(FILE *fin, FILE *frep, FILE *fout, uint16_t nblocks
     if (r || !ok) return -1;
     if (F.finish(n, records)) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
     return 0;
+}
+
+// ---- --digest / --test: the printout, the same on the GPU and on the host, and the FCXD file over stdio ----
+inline void digest_totals(uint64_t blocks, uint32_t whole) {
+    printf("digest: %llu blocks, crc32 %08X\n", (unsigned long long)blocks, whole);
+}
+// a failing block: its resulting bytes of the block's, its CRC-32 and the digest file's (none: a record
+// behind the digest file's last block)
+inline void check_line(uint64_t k, uint64_t got, uint64_t blen, uint32_t crc, const uint32_t *expected) {
+    printf("block %llu: %llu of %llu bytes, crc32 %08X, expected ", (unsigned long long)k, (unsigned long long)got,
+           (unsigned long long)blen, crc);
+    if (expected) printf("%08X\n", *expected);
+    else printf("none\n");
+}
+inline void check_extra(uint64_t extra) {
+    printf("digest: %llu bytes after the last block\n", (unsigned long long)extra);
+}
+// the verdict: 0 (OK) when no block fails and the digest file has no block left, else 1 (FAIL)
+inline int check_totals(uint64_t bad, uint64_t blocks, uint64_t bytes) {
+    const bool ok = bad == 0 && bytes == 0;
+    printf("test: %llu of %llu blocks fail, %llu input bytes in them [%s]\n", (unsigned long long)bad,
+           (unsigned long long)blocks, (unsigned long long)bytes, ok ? "OK" : "FAIL");
+    return ok ? 0 : 1;
+}
+
+// the values of a whole FCXD file (the reader's checks apply), for the expected value a failing block's
+// line shows; the file is left at its start.  -1 after a message.
+inline int load_digest(FILE *fdig, std::vector<uint32_t> *vals) {
+    fcx_digest_file::Reader G;
+    G.rd = stdio_read;
+    G.user = fdig;
+    vals->clear();
+    if (G.open() || G.take(UINT64_MAX, vals) < 0 || G.finish()) {
+        fprintf(stderr, "fcx: %s\n", G.err.c_str());
+        return -1;
+    }
+    rewind(fdig);
+    return 0;
+}
+
+// --digest without a device: the FCXD file of forig in blocks of `block` bytes to fdig, the bytes
+// fcx_digest_stream writes.  stats: FCX_DIGEST_FILE_STATS values.
+inline int host_digest_build(FILE *forig, uint32_t block, FILE *fdig, uint64_t *stats) {
+    fcx_digest_file::Writer W;
+    W.wr = stdio_write;
+    W.user = fdig;
+    std::vector<uint8_t> buf(block);
+    int w = W.begin(block);
+    for (size_t got; !w && (got = fread(buf.data(), 1, block, forig)) > 0;) w = W.add(fcx_crc::crc32(0, buf.data(), got), got);
+    if (!w && ferror(forig)) { fprintf(stderr, "read error\n"); return -1; }
+    if (!w) w = W.finish();
+    if (w) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    const uint64_t s[FCX_DIGEST_FILE_STATS] = {W.n, W.blocks, W.whole};
+    if (stats) memcpy(stats, s, sizeof(s));
+    return 0;
+}
+
+// --test / --digest of a decompress without a device: every FCX7 record through the host decoder, its
+// entry of frep (may be null) applied in the sum only, against the FCXD file fdig; the checks and the
+// lines of fcx_check_stream.  Returns the verdict (0 / 1), or -1 after a message.
+inline int host_check(FILE *fin, FILE *frep, FILE *fdig, uint16_t nblocks, uint64_t *stats) {
+    fcx_digest_file::Reader G;
+    G.rd = stdio_read;
+    G.user = fdig;
+    if (G.open()) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return -1; }
+    const uint64_t B = G.block_bytes;
+    fcx_repair_file::Reader F;
+    if (frep) {
+        F.rd = stdio_read;
+        F.user = frep;
+        if (F.open()) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+        if (F.kind != '7') { fprintf(stderr, "fcx: repair file: made for the other codec\n"); return -1; }
+        if (F.block_bytes != B) { fprintf(stderr, "fcx: repair file: made for another block size than the digest file's\n"); return -1; }
+    }
+    uint64_t s[6] = {0, 0, UINT64_MAX, 0, 0, 0}, result_bytes = 0;
+    bool ok = true;
+    std::vector<uint32_t> want;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t k, uint32_t, const uint8_t *plain, uint64_t dlen) {
+        want.clear();
+        const int64_t got = G.take(1, &want);
+        const int m = got < 0 ? (int)got : G.more();
+        if (m < 0) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return ok = false; }
+        const uint64_t blen = got ? (m ? B : G.block_len(k)) : 0;
+        fcx_repair_entry e;
+        const uint8_t *raw = nullptr;
+        const int g = frep ? F.next(k, (uint64_t)k + 1, &e, &raw) : 0;
+        if (g < 0) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return ok = false; }
+        uint64_t rlen = dlen;
+        uint32_t c;
+        if (g) {
+            if (e.from > dlen || (uint64_t)e.from + e.len != blen) {
+                fprintf(stderr, "fcx: repair: the entry of record %u does not fit its record\n", k);
+                return ok = false;
+            }
+            rlen = blen;
+            c = fcx_crc::crc32(0, plain, e.from);
+            c = e.kind == FCX_REPAIR_RAW ? fcx_crc::crc32(c, raw, e.len)
+                                         : fcx_crc::combine(c, fcx_crc::crc32_fill((uint8_t)e.fill, e.len), e.len);
+        } else {
+            c = fcx_crc::crc32(0, plain, dlen);
+        }
+        s[0]++;
+        s[3] += rlen != blen;
+        s[5] += dlen;
+        result_bytes += rlen;
+        if (!got || rlen != blen || c != want[0]) {
+            check_line(k, rlen, blen, c, got ? &want[0] : nullptr);
+            if (s[1]++ == 0) s[2] = k;
+            s[4] += blen;
+        }
+        return true;
+    });
+    if (r || !ok) return -1;
+    if (frep && F.finish(result_bytes, s[0])) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+    const int64_t left = G.take(UINT64_MAX, nullptr);
+    if (left < 0 || G.finish()) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return -1; }
+    if (left) {
+        const uint64_t extra = G.n - std::min(G.n, s[0] * B);
+        check_extra(extra);
+        s[4] += extra;
+    }
+    if (stats) memcpy(stats, s, sizeof(s));
+    return check_totals(s[1], s[0], s[4]);
 }
 
 }  // namespace fcx_cli

@@ -464,6 +464,32 @@ struct RepairScratch {
     uint64_t stats[FCX_REPAIR_STATS] = {};
 };
 
+// ---- status words of a check (fcx_dctx's dg.words, u64 each; host_words mirrors them): the first
+// FCX_VERIFY_STATS are the call's stats in the order of fcx.h (kVw*), written by k_dgsummary ----
+constexpr uint32_t kDgwWords = 8;
+
+// fcx_check_shard behind its argument checks (fcx_digest.hip), for the stream path's groups of a longer
+// file: d_crc holds ncrc <= nblocks values, a record from ncrc on has no block and fails with block
+// length 0; n: the bytes of the ncrc blocks; messages number the records from rec_base
+int check_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint32_t ncrc, uint64_t n,
+              uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
+              uint64_t data_bytes, const uint32_t *d_crc, uint32_t *d_blocks, uint64_t *stats, hipStream_t st,
+              uint64_t rec_base);
+
+// scratch of the digest calls (fcx_digest.hip); the stream forms' device copies of a shard or a group
+struct DigestScratch {
+    DevBuf<uint32_t> tables;         // the slicing, folding and power tables (made on the host once)
+    DevBuf<uint64_t> seg_at;         // a check: per record two segments, their device addresses ...
+    DevBuf<uint32_t> seg_len;        // ... and lengths: the decoded prefix, the RAW bytes
+    DevBuf<uint32_t> part;           // their CRC-32
+    DevBuf<uint64_t> words;          // kVw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint8_t> stage;           // digest_stream: a shard of the original
+    DevBuf<uint32_t> crc, blocks;    // the stream forms: a shard's or group's values, a group's pairs
+    uint32_t slice = 4;              // fcx_dctx_set_digest_slice
+    uint64_t stats[FCX_DIGEST_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -494,6 +520,7 @@ struct fcx_dctx {
     fcx::RangeScratch rg;
     fcx::VerifyScratch vf;
     fcx::RepairScratch rp;
+    fcx::DigestScratch dg;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

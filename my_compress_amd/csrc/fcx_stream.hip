@@ -18,6 +18,7 @@
 #include "fcx_dec_shared.h"   // lz78_decompress_shard_at
 #include "fcx_device.h"       // the compress status words a slot's hlen mirrors
 #include "fcx_host.h"
+#include "fcx_digest_file.h"
 #include "fcx_repair_file.h"
 
 using namespace fcx;
@@ -655,6 +656,116 @@ int fcx_repair_apply_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, co
     *out_len = dst.out_pos;
     if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_repair_apply_host: output capacity too small");
     return r;
+}
+
+}  // extern "C"
+
+// ---- the content digest's check, stream and host forms (include/fcx.h) ---------------
+
+extern "C" {
+
+int fcx_check_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_rep, void *user_rep, fcx_read_fn rd_dig,
+                     void *user_dig, uint64_t max_in, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
+    if (!dctx || !rd || !rd_dig || !stats) return fail(FCX_ERR_ARG, "fcx_check_stream: NULL argument");
+    fcx_digest_file::Reader G;
+    G.rd = rd_dig;
+    G.user = user_dig;
+    if (const int g = G.open()) return fail(g, G.err);
+    const uint32_t block_bytes = G.block_bytes;
+    const uint64_t B = block_bytes;
+    fcx_repair_file::Reader F;
+    if (rd_rep) {
+        F.rd = rd_rep;
+        F.user = user_rep;
+        if (const int f = F.open()) return fail(f, F.err);
+        if (F.block_bytes != block_bytes) return fail(FCX_ERR_FORMAT, "repair file: made for another block size than the digest file's");
+    }
+    PeekRead pk{rd, user, {}, 0};
+    uint64_t sum[FCX_VERIFY_STATS] = {0, 0, ~0ull, 0, 0, 0};
+    uint64_t result_bytes = 0, records = 0;
+    std::vector<uint32_t> want, pairs;
+    std::vector<fcx_repair_entry> ents;
+    std::vector<uint8_t> raw;
+    const int r = stream_groups(dctx, peek_read, &pk, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        if (rd_rep && (lz78 ? '8' : '7') != F.kind) return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        // the group's values: the sections that hold them are read now, and no further; whether the
+        // group's last block is the file's last, and so shorter, shows once the sections have ended
+        want.clear();
+        const int64_t got = G.take(nb, &want);
+        if (got < 0) return fail((int)got, G.err);
+        const int m = G.more();
+        if (m < 0) return fail(m, G.err);
+        uint64_t n = (uint64_t)got * B;
+        if (m == 0 && got) n = (uint64_t)(got - 1) * B + G.block_len(before + (uint64_t)got - 1);
+        ents.clear();
+        raw.clear();
+        while (rd_rep) {
+            fcx_repair_entry e;
+            const uint8_t *bytes = nullptr;
+            const int g = F.next(before, before + nb, &e, &bytes);
+            if (g < 0) return fail(g, F.err);
+            if (g == 0) break;
+            e.block -= before;
+            e.data_off = 0;
+            if (e.kind == FCX_REPAIR_RAW) {
+                e.data_off = raw.size();
+                raw.insert(raw.end(), bytes, bytes + e.len);
+            }
+            ents.push_back(e);
+        }
+        RepairScratch &P = dctx->rp;
+        DigestScratch &D = dctx->dg;
+        FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * ents.size(), "repair entries"));
+        FCX_TRY(P.data.reserve(raw.size(), "repair data"));
+        FCX_TRY(D.crc.reserve(4ull * nb, "digest values"));
+        FCX_TRY(D.blocks.reserve(8ull * nb, "digest pairs"));
+        if (!ents.empty())
+            FCX_HIP(hipMemcpyAsync(P.entries, ents.data(), sizeof(fcx_repair_entry) * ents.size(), hipMemcpyHostToDevice, st));
+        if (!raw.empty()) FCX_HIP(hipMemcpyAsync(P.data, raw.data(), raw.size(), hipMemcpyHostToDevice, st));
+        if (got) FCX_HIP(hipMemcpyAsync(D.crc, want.data(), 4ull * (uint64_t)got, hipMemcpyHostToDevice, st));
+        uint64_t gs[FCX_VERIFY_STATS];
+        FCX_TRY(fcx::check_run(dctx, lz78 ? '8' : '7', x.din, used, nb, (uint32_t)got, n, block_bytes, P.entries,
+                               (uint32_t)ents.size(), P.data, raw.size(), D.crc, D.blocks, gs, st, before));
+        pairs.resize(2ull * nb);
+        FCX_HIP(hipMemcpy(pairs.data(), D.blocks, 8ull * nb, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < nb; k++) {
+            const uint64_t o0 = (uint64_t)k * B, blen = k < (uint64_t)got && o0 < n ? std::min(B, n - o0) : 0;
+            result_bytes += pairs[2 * k];
+            if (on_block && (k >= (uint64_t)got || pairs[2 * k] != blen || pairs[2 * k + 1] != want[k]))
+                on_block(user_cb, before + k, blen, pairs[2 * k], pairs[2 * k + 1]);
+        }
+        if (gs[2] != ~0ull && sum[2] == ~0ull) sum[2] = before + gs[2];
+        for (int i : {0, 1, 3, 4, 5}) sum[i] += gs[i];
+        records += nb;
+        return FCX_OK;
+    });
+    if (r) return r;
+    if (rd_rep) {
+        if (records == 0 && pk.seen == sizeof(pk.hdr) && (pk.hdr[3] == '7' ? '7' : '8') != F.kind)
+            return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        if (const int f = F.finish(result_bytes, records)) return fail(f, F.err);
+    }
+    // blocks of the digest file behind the last record
+    const int64_t left = G.take(~0ull, nullptr);
+    if (left < 0) return fail((int)left, G.err);
+    if (const int g = G.finish()) return fail(g, G.err);
+    if (left) {
+        const uint64_t extra = G.n - std::min(G.n, records * B);
+        sum[4] += extra;
+        if (on_block) on_block(user_cb, sum[0], extra, 0, 0);
+    }
+    for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = sum[i];
+    return FCX_OK;
+}
+
+int fcx_check_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
+                   const uint8_t *digest, uint64_t digest_len, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
+    if (!dctx || !in || !digest || !stats) return fail(FCX_ERR_ARG, "fcx_check_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0}, rep{repair, repair_len, 0, nullptr, 0, 0}, dig{digest, digest_len, 0, nullptr, 0, 0};
+    return fcx_check_stream(dctx, mem_read, &comp, repair ? mem_read : nullptr, &rep, mem_read, &dig, in_len - FCX_HEADER_BYTES,
+                            on_block, user_cb, stats);
 }
 
 }  // extern "C"
