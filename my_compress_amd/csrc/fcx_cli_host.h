@@ -182,16 +182,32 @@ inline int64_t stdio_read(void *u, uint8_t *buf, uint64_t cap) {
     return ferror(f) ? -1 : (int64_t)n;
 }
 inline int stdio_write(void *u, const uint8_t *buf, uint64_t n) { return fwrite(buf, 1, (size_t)n, (FILE *)u) == n ? 0 : -1; }
+// the reason a sidecar file's reader or writer gave, to stderr; -1
+template <typename T>
+inline int say_err(const T &x) {
+    fprintf(stderr, "fcx: %s\n", x.err.c_str());
+    return -1;
+}
+// Record k's entry of F (null: no repair file) against the dlen bytes the record decodes to.  1: *e and
+// *raw, *rlen = the bytes the entry makes of the record; 0: none, *rlen = dlen; -1 after F's message;
+// -2: the entry keeps more than the record decodes to (the message is the caller's).
+inline int host_entry(fcx_repair_file::Reader *F, uint32_t k, uint64_t dlen, fcx_repair_entry *e, const uint8_t **raw,
+                      uint64_t *rlen) {
+    *rlen = dlen;
+    const int g = F ? F->next(k, (uint64_t)k + 1, e, raw) : 0;
+    if (g < 0) return say_err(*F);
+    if (g && e->from > dlen) return -2;
+    if (g) *rlen = (uint64_t)e->from + e->len;
+    return g;
+}
 
 // --compare --repair without a device: the FCXR file of the FCX7 records behind the header of fin
 // against forig, to frep; the bytes fcx_repair_build_stream writes.  A record the original has no
 // bytes for, or original bytes behind the last record, cannot be expressed: -1 after a message, as for
 // a damaged record.  stats: FCX_REPAIR_FILE_STATS values.
 inline int host_repair_build(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t block, FILE *frep, uint64_t *stats) {
-    fcx_repair_file::Writer W;
-    W.wr = stdio_write;
-    W.user = frep;
-    if (W.begin('7', block)) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    fcx_repair_file::Writer W(stdio_write, frep);
+    if (W.begin('7', block)) return say_err(W);
     std::vector<uint8_t> orig(block);
     uint64_t n = 0, records = 0;
     bool ok = true;
@@ -202,10 +218,8 @@ inline int host_repair_build(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t 
             return ok = false;
         }
         fcx_repair_entry e;
-        if (fcx_repair_file::plan_entry(k, plain, dlen, orig.data(), blen, &e) && W.add(e, orig.data() + e.from)) {
-            fprintf(stderr, "fcx: %s\n", W.err.c_str());
-            return ok = false;
-        }
+        if (fcx_repair_file::plan_entry(k, plain, dlen, orig.data(), blen, &e) && W.add(e, orig.data() + e.from))
+            return ok = say_err(W) == 0;
         n += blen;
         records++;
         return true;
@@ -215,7 +229,7 @@ inline int host_repair_build(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t 
         fprintf(stderr, "fcx: repair: the original has bytes after the last record\n");
         return -1;
     }
-    if (W.finish(n, records)) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    if (W.finish(n, records)) return say_err(W);
     const uint64_t s[FCX_REPAIR_FILE_STATS] = {n, records, W.entries, W.data_bytes};
     if (stats) memcpy(stats, s, sizeof(s));
     return 0;
@@ -224,10 +238,8 @@ inline int host_repair_build(FILE *fin, FILE *forig, uint16_t nblocks, uint32_t 
 // decompress with --repair without a device: every FCX7 record through the host decoder, its entry
 // applied, to fout; the checks of fcx_repair_apply_stream.  *written: bytes written.
 inline int host_repair_apply(FILE *fin, FILE *frep, FILE *fout, uint16_t nblocks, uint64_t *written) {
-    fcx_repair_file::Reader F;
-    F.rd = stdio_read;
-    F.user = frep;
-    if (F.open()) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+    fcx_repair_file::Reader F(stdio_read, frep);
+    if (F.open()) return say_err(F);
     if (F.kind != '7') { fprintf(stderr, "fcx: repair file: made for the other codec\n"); return -1; }
     const uint32_t B = F.block_bytes;
     std::vector<uint8_t> fillbuf;
@@ -241,13 +253,10 @@ inline int host_repair_apply(FILE *fin, FILE *frep, FILE *fout, uint16_t nblocks
         if (short_seen) return bad(k - 1, "gives a block shorter than the block size and is not the last");
         fcx_repair_entry e;
         const uint8_t *raw = nullptr;
-        const int g = F.next(k, (uint64_t)k + 1, &e, &raw);
-        if (g < 0) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return ok = false; }
-        uint64_t blen = dlen;
-        if (g) {
-            if (e.from > dlen) return bad(k, "decodes to fewer bytes than its entry keeps");
-            blen = (uint64_t)e.from + e.len;
-        }
+        uint64_t blen;
+        const int g = host_entry(&F, k, dlen, &e, &raw, &blen);
+        if (g == -2) return bad(k, "decodes to fewer bytes than its entry keeps");
+        if (g < 0) return ok = false;
         if (blen == 0 || blen > B) return bad(k, "does not decode to its block's length and has no entry that mends it");
         if (blen < B) short_seen = true;
         const uint64_t keep = g ? e.from : dlen;
@@ -266,8 +275,7 @@ inline int host_repair_apply(FILE *fin, FILE *frep, FILE *fout, uint16_t nblocks
     });
     *written = n;
     if (r || !ok) return -1;
-    if (F.finish(n, records)) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
-    return 0;
+    return F.finish(n, records) ? say_err(F) : 0;
 }
 
 // ---- --digest / --test: the printout, the same on the GPU and on the host, and the FCXD file over stdio ----
@@ -296,14 +304,9 @@ inline int check_totals(uint64_t bad, uint64_t blocks, uint64_t bytes) {
 // the values of a whole FCXD file (the reader's checks apply), for the expected value a failing block's
 // line shows; the file is left at its start.  -1 after a message.
 inline int load_digest(FILE *fdig, std::vector<uint32_t> *vals) {
-    fcx_digest_file::Reader G;
-    G.rd = stdio_read;
-    G.user = fdig;
+    fcx_digest_file::Reader G(stdio_read, fdig);
     vals->clear();
-    if (G.open() || G.take(UINT64_MAX, vals) < 0 || G.finish()) {
-        fprintf(stderr, "fcx: %s\n", G.err.c_str());
-        return -1;
-    }
+    if (G.open() || G.take(UINT64_MAX, vals) < 0 || G.finish()) return say_err(G);
     rewind(fdig);
     return 0;
 }
@@ -311,15 +314,13 @@ inline int load_digest(FILE *fdig, std::vector<uint32_t> *vals) {
 // --digest without a device: the FCXD file of forig in blocks of `block` bytes to fdig, the bytes
 // fcx_digest_stream writes.  stats: FCX_DIGEST_FILE_STATS values.
 inline int host_digest_build(FILE *forig, uint32_t block, FILE *fdig, uint64_t *stats) {
-    fcx_digest_file::Writer W;
-    W.wr = stdio_write;
-    W.user = fdig;
+    fcx_digest_file::Writer W(stdio_write, fdig);
     std::vector<uint8_t> buf(block);
     int w = W.begin(block);
     for (size_t got; !w && (got = fread(buf.data(), 1, block, forig)) > 0;) w = W.add(fcx_crc::crc32(0, buf.data(), got), got);
     if (!w && ferror(forig)) { fprintf(stderr, "read error\n"); return -1; }
     if (!w) w = W.finish();
-    if (w) { fprintf(stderr, "fcx: %s\n", W.err.c_str()); return -1; }
+    if (w) return say_err(W);
     const uint64_t s[FCX_DIGEST_FILE_STATS] = {W.n, W.blocks, W.whole};
     if (stats) memcpy(stats, s, sizeof(s));
     return 0;
@@ -329,16 +330,12 @@ inline int host_digest_build(FILE *forig, uint32_t block, FILE *fdig, uint64_t *
 // entry of frep (may be null) applied in the sum only, against the FCXD file fdig; the checks and the
 // lines of fcx_check_stream.  Returns the verdict (0 / 1), or -1 after a message.
 inline int host_check(FILE *fin, FILE *frep, FILE *fdig, uint16_t nblocks, uint64_t *stats) {
-    fcx_digest_file::Reader G;
-    G.rd = stdio_read;
-    G.user = fdig;
-    if (G.open()) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return -1; }
+    fcx_digest_file::Reader G(stdio_read, fdig);
+    if (G.open()) return say_err(G);
     const uint64_t B = G.block_bytes;
-    fcx_repair_file::Reader F;
+    fcx_repair_file::Reader F(stdio_read, frep);
     if (frep) {
-        F.rd = stdio_read;
-        F.user = frep;
-        if (F.open()) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+        if (F.open()) return say_err(F);
         if (F.kind != '7') { fprintf(stderr, "fcx: repair file: made for the other codec\n"); return -1; }
         if (F.block_bytes != B) { fprintf(stderr, "fcx: repair file: made for another block size than the digest file's\n"); return -1; }
     }
@@ -349,20 +346,16 @@ inline int host_check(FILE *fin, FILE *frep, FILE *fdig, uint16_t nblocks, uint6
         want.clear();
         const int64_t got = G.take(1, &want);
         const int m = got < 0 ? (int)got : G.more();
-        if (m < 0) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return ok = false; }
+        if (m < 0) return ok = say_err(G) == 0;
         const uint64_t blen = got ? (m ? B : G.block_len(k)) : 0;
         fcx_repair_entry e;
         const uint8_t *raw = nullptr;
-        const int g = frep ? F.next(k, (uint64_t)k + 1, &e, &raw) : 0;
-        if (g < 0) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return ok = false; }
-        uint64_t rlen = dlen;
+        uint64_t rlen;
+        const int g = host_entry(frep ? &F : nullptr, k, dlen, &e, &raw, &rlen);
+        if (g == -2 || (g > 0 && rlen != blen)) fprintf(stderr, "fcx: repair: the entry of record %u does not fit its record\n", k);
+        if (g < 0 || (g > 0 && rlen != blen)) return ok = false;
         uint32_t c;
         if (g) {
-            if (e.from > dlen || (uint64_t)e.from + e.len != blen) {
-                fprintf(stderr, "fcx: repair: the entry of record %u does not fit its record\n", k);
-                return ok = false;
-            }
-            rlen = blen;
             c = fcx_crc::crc32(0, plain, e.from);
             c = e.kind == FCX_REPAIR_RAW ? fcx_crc::crc32(c, raw, e.len)
                                          : fcx_crc::combine(c, fcx_crc::crc32_fill((uint8_t)e.fill, e.len), e.len);
@@ -381,9 +374,9 @@ inline int host_check(FILE *fin, FILE *frep, FILE *fdig, uint16_t nblocks, uint6
         return true;
     });
     if (r || !ok) return -1;
-    if (frep && F.finish(result_bytes, s[0])) { fprintf(stderr, "fcx: %s\n", F.err.c_str()); return -1; }
+    if (frep && F.finish(result_bytes, s[0])) return say_err(F);
     const int64_t left = G.take(UINT64_MAX, nullptr);
-    if (left < 0 || G.finish()) { fprintf(stderr, "fcx: %s\n", G.err.c_str()); return -1; }
+    if (left < 0 || G.finish()) return say_err(G);
     if (left) {
         const uint64_t extra = G.n - std::min(G.n, s[0] * B);
         check_extra(extra);

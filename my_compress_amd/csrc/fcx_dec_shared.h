@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
+#include <vector>
 
 #include "fcx_host.h"
 
@@ -418,10 +420,6 @@ int verify_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, u
                uint64_t n, uint32_t block_bytes, uint32_t *d_blocks, uint64_t *stats, hipStream_t st, uint64_t rec_base);
 
 // scratch of the verification (fcx_verify.hip)
-struct VerifyScratch;
-// the end of the record group that starts at g0 (fcx_verify.hip: the bound of fcx_dctx_set_verify_group
-// over doff, the run's dec_off on the host); fcx_repair_apply_shard forms its groups with it too
-uint32_t verify_group_end(const VerifyScratch &V, const uint64_t *doff, uint32_t nblocks, uint32_t g0);
 struct VerifyScratch {
     DevBuf<uint8_t> buf;             // a group's decoded bytes, grown on demand up to the group bound
     DevBuf<uint32_t> first_diff;     // per record: the first differing byte k_vcompare found
@@ -431,6 +429,33 @@ struct VerifyScratch {
     uint64_t group_bytes = 0;        // fcx_dctx_set_verify_group (0: 256 MiB)
     uint32_t groups = 0;             // groups of the last call
 };
+
+// ---- the run core (fcx_run.hip): what verify_run, repair_apply_run and check_run do
+// alike with a device-resident run of records ----
+// the checks every entry point over a run and its blocks makes first, `fn` its name in the messages
+int run_args(const char *fn, fcx_dctx *c, char kind, const void *d_rec, uint32_t nblocks, uint64_t n, uint32_t block_bytes);
+struct RunTimes;
+// A run's index: rg.rec_off and rg.dec_off through fcx_index_shard (stage 0 of T), and their copies to
+// roff and doff (nblocks + 1 each) issued on st: the caller synchronises before it reads them.
+struct RunIndex {
+    std::vector<uint64_t> roff, doff;
+};
+int run_index(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, hipStream_t st, RunTimes &T,
+              RunIndex *ix);
+// the end of the record group that starts at g0: the bound of fcx_dctx_set_verify_group over doff
+uint32_t verify_group_end(const VerifyScratch &V, const uint64_t *doff, uint32_t nblocks, uint32_t g0);
+// the run's groups in order, vf.groups set and vf.buf reserved for the largest of them that `staged`
+// (records [g0, g1); none given: every group) says goes through the buffer
+struct RunGroup {
+    uint32_t g0, g1;
+    uint64_t gbytes;   // decoded bytes of its records
+};
+int run_groups(fcx_dctx *c, const RunIndex &ix, uint32_t nblocks, std::vector<RunGroup> *groups,
+               const std::function<bool(uint32_t, uint32_t)> &staged = nullptr);
+// records [g0, g0 + nrec) of the run through their codec's decoder to dst, which must give `want` bytes;
+// `who` names the entry point in the message, FCX8 messages number the records from rec_base
+int decode_group(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, const std::vector<uint64_t> &roff, uint32_t g0,
+                 uint32_t nrec, uint8_t *dst, uint64_t want, hipStream_t st, uint64_t rec_base, const char *who);
 
 // ---- status words of a repair call (fcx_dctx's rp.words, u64 each; host_words mirrors them) ----
 constexpr uint32_t kRpEntries = 0;     // entries (k_rscan; an apply: the caller's count)
@@ -451,6 +476,13 @@ int repair_build_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_
 int repair_apply_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
                      uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
                      uint64_t data_bytes, uint8_t *d_out, uint64_t cap, uint64_t *out_len, hipStream_t st, uint64_t rec_base);
+// The entry map of an apply or a check (fcx_repair.hip): rp.entry_of preset to kNoEntry, k_rmap over the
+// entries against rg.dec_off, k_rcheck too when with_check, and the status words on their way to
+// rp.host_words.  After the caller's synchronisation entry_map_result turns the first entry or record
+// that failed into the call's error (records numbered from rec_base).
+int launch_entry_map(fcx_dctx *c, const fcx_repair_entry *d_entries, uint32_t nentries, uint32_t nblocks, uint64_t n,
+                     uint32_t block_bytes, uint64_t data_bytes, bool with_check, hipStream_t st);
+int entry_map_result(fcx_dctx *c, uint64_t rec_base);
 
 // scratch of the repair calls (fcx_repair.hip); the stream forms' device copies of a group's entries and data
 struct RepairScratch {
@@ -475,6 +507,9 @@ int check_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, ui
               uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
               uint64_t data_bytes, const uint32_t *d_crc, uint32_t *d_blocks, uint64_t *stats, hipStream_t st,
               uint64_t rec_base);
+// fcx_digest_shard behind its argument checks
+int digest_run(fcx_dctx *c, const uint8_t *d_data, uint64_t n, uint32_t block_bytes, uint32_t *d_crc, uint32_t *whole,
+               hipStream_t st);
 
 // scratch of the digest calls (fcx_digest.hip); the stream forms' device copies of a shard or a group
 struct DigestScratch {
@@ -524,5 +559,27 @@ struct fcx_dctx {
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };
+
+namespace fcx {
+
+// the stage times of a call over a run: events only when the context profiles; publish() makes the
+// call's own table the context's (it replaces the last inner decode's)
+struct RunTimes {
+    std::unique_ptr<StageTimes> T;
+    hipStream_t st;
+    RunTimes(fcx_dctx *c, int stages, hipStream_t s) : T(c->profiling ? new StageTimes(stages) : nullptr), st(s) {}
+    void mark(int i) {
+        if (T) T->mark(i, st);
+    }
+    int add(int first, int last) { return T ? T->add(first, last) : FCX_OK; }
+    void publish(fcx_dctx *c, const char *const *names, int n) {
+        c->times.reset();
+        if (!T) return;
+        for (int i = 0; i < n; i++) c->times.ms[i] = T->ms[i];
+        c->times.publish(names, n);
+    }
+};
+
+}  // namespace fcx
 
 #endif  // FCX_DEC_SHARED_H

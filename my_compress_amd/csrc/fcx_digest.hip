@@ -1,5 +1,5 @@
 // fcx_digest.hip — content digests (gfx950): the CRC-32 (zlib's) of many byte segments of a device
-// buffer, fcx_digest_shard and fcx_check_shard of include/fcx.h, and the digest's stream and host forms.
+// buffer, fcx_digest_shard and fcx_check_shard of include/fcx.h (their stream and host forms: fcx_stream.hip).
 // DESIGN.md §9f.
 //
 // gfx950 has no carry-less multiply, so the sum is table-driven, and a segment is not one lane's walk:
@@ -14,27 +14,24 @@
 //                < 16 bytes, multiplies by x^(8 * bytes behind the chunk in its segment), folds in init
 //                and xorout from the segment's length (chunk 0 only) and XORs the word into the
 //                segment's with one atomic.  XOR commutes: no order among workgroups matters.
-//   reads        16-byte loads through ld16_shifted (fcx_ld16.h) where the aligned 32-byte window lies
-//                inside the segment, byte by byte at its head and tail, as k_vcompare and k_rplan do:
-//                nothing outside a segment is read.
+//   reads        16 bytes through ld16_bounded (fcx_ld16.h), as k_vcompare and k_rplan do: nothing outside a
+//                segment is read.
 //   segments     three forms of one kernel: strided (block k at k B, the last ragged to n), a u64 offsets
 //                array (the run's dec_off), and a list of device addresses and lengths (a check's
 //                decoded prefixes and RAW bytes).
-//   a check      index, then per record group: decode into the verification's bounded buffer, k_dgplan
-//                (per record its two segments), k_dgcrc; at the end k_dgsummary: a repaired block's
-//                CRC-32 combined from its parts, the compare with the expected values, the totals.
+//   a check      the run core: index, the entry map of fcx_repair.hip, then per record group
+//                the decode into the verification's bounded buffer, k_dgplan (per record its two
+//                segments), k_dgcrc; at the end k_dgsummary: a repaired block's CRC-32 combined from its
+//                parts, the compare with the expected values, the totals.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "fcx.h"
 #include "fcx_crc32.h"
 #include "fcx_dec_shared.h"
-#include "fcx_device.h"   // wave_sum_u64
-#include "fcx_digest_file.h"
 #include "fcx_ld16.h"
 
 namespace fcx {
@@ -46,7 +43,6 @@ constexpr uint32_t kDgPieces = kDgRows * kDgThreads;
 constexpr uint32_t kDgChunk = kDgRows * kDgRowBytes;      // bytes of a segment one workgroup sums (64 KiB)
 constexpr uint32_t kDgSlice = 4;                          // bytes per slicing round by default: 4 tables in LDS
 constexpr uint64_t kDgMaxGrid = 0x7FFFFFFFull;
-constexpr uint32_t kDgNone = 0xFFFFFFFFu;                 // entry_of: the record has no entry
 // the tables, u32 each: 16 slicing tables (T[0] the byte table), the fold over a row less a piece, a
 // lane's distance to the chunk's end, x^(8 b 2^(8k)) for the four bytes b of a length
 constexpr uint32_t kDgtSlice = 0, kDgtFold = 16 * 256, kDgtLane = kDgtFold + 4 * 256, kDgtPow = kDgtLane + 256,
@@ -119,9 +115,8 @@ __global__ __launch_bounds__(kDgThreads) void k_dgcrc(const uint8_t *__restrict_
     const uint8_t *p;
     uint32_t len;
     if (FORM == kDgStrided) {
-        const uint64_t o0 = (uint64_t)seg * B;
-        len = o0 < n ? (uint32_t)min((uint64_t)B, n - o0) : 0u;
-        p = data + o0;
+        len = block_len(seg, n, B);
+        p = data + (uint64_t)seg * B;
     } else if (FORM == kDgOffsets) {
         const uint64_t a = off[seg];
         len = (uint32_t)(off[seg + 1] - a);
@@ -143,18 +138,8 @@ __global__ __launch_bounds__(kDgThreads) void k_dgcrc(const uint8_t *__restrict_
         const uint32_t v = s * kDgThreads + t;
         if (v < skip) continue;
         const uint32_t i = c0 + 16 * (v - skip);
-        // inside: the aligned window [i - sh, i - sh + 32) within [0, len)
-        const bool wide = i >= sh && (uint64_t)i - sh + 32 <= len;
-        uint32_t x[4];
-        if (wide) {
-            const uint4 w = ld16_shifted(p + i, sh);
-            x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
-        } else {
-            for (uint32_t q = 0; q < 4; q++) {
-                const uint8_t *b = p + i + 4 * q;
-                x[q] = b[0] | (b[1] << 8) | (b[2] << 16) | ((uint32_t)b[3] << 24);
-            }
-        }
+        const uint4 w = ld16_bounded(p, i, sh, len);
+        uint32_t x[4] = {w.x, w.y, w.z, w.w};
         // the remainder so far, kDgRowBytes further: folded over all but the piece's 16 bytes, which the
         // slicing rounds then cross with the piece
         r = sF[r & 0xFFu] ^ sF[256 + ((r >> 8) & 0xFFu)] ^ sF[512 + ((r >> 16) & 0xFFu)] ^ sF[768 + (r >> 24)];
@@ -178,34 +163,9 @@ __global__ __launch_bounds__(kDgThreads) void k_dgcrc(const uint8_t *__restrict_
     atomicXor(crc + seg, r);
 }
 
-// One thread per entry: the checks of fcx_repair_apply_shard against the index (k_rmap of fcx_repair.hip,
-// whose text stays as it is); the first entry that fails one by atomicMin into kRpBadEntry, entry_of[block]
-// for the others (preset to kDgNone).
-__global__ __launch_bounds__(kDgThreads) void k_dgmap(const fcx_repair_entry *__restrict__ entries, uint32_t nentries,
-                                                      uint32_t nblocks, const uint64_t *__restrict__ dec_off, uint64_t n,
-                                                      uint32_t B, uint64_t data_bytes, uint32_t *__restrict__ entry_of,
-                                                      uint64_t *__restrict__ words) {
-    const uint32_t i = blockIdx.x * kDgThreads + threadIdx.x;
-    if (i >= nentries) return;
-    const fcx_repair_entry e = entries[i];
-    bool ok = e.block < nblocks && e.kind <= FCX_REPAIR_FILL && (i == 0 || entries[i - 1].block < e.block);
-    if (ok) {
-        const uint64_t dlen = dec_off[e.block + 1] - dec_off[e.block], o0 = e.block * B;
-        const uint32_t blen = o0 < n ? (uint32_t)min((uint64_t)B, n - o0) : 0u;
-        ok = e.from <= dlen && (uint64_t)e.from + e.len == blen;
-        if (ok && e.kind == FCX_REPAIR_RAW) ok = e.data_off <= data_bytes && e.len <= data_bytes - e.data_off;
-    }
-    if (!ok) {
-        atomicMin((unsigned long long *)words + kRpBadEntry, (unsigned long long)i);
-        return;
-    }
-    entry_of[e.block] = i;
-    if (e.kind == FCX_REPAIR_FILL) atomicAdd((unsigned long long *)words + kRpFills, 1ull);
-}
-
 // One thread per record of the group [k0, k0 + nrec), decoded back to back at dec (gbytes bytes; byte 0
 // is decoded offset dec_base of the run): its two segments.  2k: the decoded record, or below an entry's
-// `from` only; 2k + 1: a RAW entry's bytes.  The entries passed k_dgmap, and still nothing they say moves
+// `from` only; 2k + 1: a RAW entry's bytes.  The entries passed k_rmap, and still nothing they say moves
 // a segment out of dec[0, gbytes) or data[0, data_bytes).
 __global__ __launch_bounds__(kDgThreads) void k_dgplan(const uint8_t *__restrict__ dec, uint64_t dec_base, uint64_t gbytes,
                                                        const uint64_t *__restrict__ dec_off, uint32_t k0, uint32_t nrec,
@@ -220,7 +180,7 @@ __global__ __launch_bounds__(kDgThreads) void k_dgplan(const uint8_t *__restrict
     uint32_t keep = (uint32_t)min(dec_off[k + 1] - dec_off[k], gbytes - d0), raw = 0;
     uint64_t raw_at = 0;
     const uint32_t ei = entry_of[k];
-    if (ei != kDgNone) {
+    if (ei != kNoEntry) {
         const fcx_repair_entry e = entries[ei];
         keep = min(keep, e.from);
         if (e.kind == FCX_REPAIR_RAW && e.data_off <= data_bytes && e.len <= data_bytes - e.data_off) {
@@ -248,11 +208,10 @@ __global__ __launch_bounds__(1024) void k_dgsummary(uint32_t nblocks, uint32_t n
                                                     uint64_t *__restrict__ words) {
     uint64_t failing = 0, first = ~0ull, sized = 0, bytes = 0;
     for (uint32_t k = threadIdx.x; k < nblocks; k += 1024) {
-        const uint64_t o0 = (uint64_t)k * B;
-        const uint32_t blen = k < ncrc && o0 < n ? (uint32_t)min((uint64_t)B, n - o0) : 0u;
+        const uint32_t blen = k < ncrc ? block_len(k, n, B) : 0u;
         uint32_t rlen = (uint32_t)(dec_off[k + 1] - dec_off[k]), c = part[pstride * k];
         const uint32_t ei = entry_of[k];
-        if (ei != kDgNone) {
+        if (ei != kNoEntry) {
             const fcx_repair_entry e = entries[ei];
             const uint32_t tail = e.kind == FCX_REPAIR_FILL ? crc_fill(tables, e.fill & 0xFFu, e.len) : part[2 * k + 1];
             c = gf_mul(c, gf_xpow8(tables, e.len)) ^ tail;
@@ -269,26 +228,7 @@ __global__ __launch_bounds__(1024) void k_dgsummary(uint32_t nblocks, uint32_t n
             first = min(first, (uint64_t)k);
         }
     }
-    failing = wave_sum_u64(failing);
-    sized = wave_sum_u64(sized);
-    bytes = wave_sum_u64(bytes);
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)first, o, 64), hi = __shfl_xor((uint32_t)(first >> 32), o, 64);
-        first = min(first, ((uint64_t)hi << 32) | lo);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned long long *w = (unsigned long long *)words;
-        if (failing) {
-            atomicAdd(w + kVwDiffer, (unsigned long long)failing);
-            atomicAdd(w + kVwBytes, (unsigned long long)bytes);
-            atomicMin(w + kVwFirst, (unsigned long long)first);
-        }
-        if (sized) atomicAdd(w + kVwSized, (unsigned long long)sized);
-    }
-    if (threadIdx.x == 0) {
-        words[kVwBlocks] = nblocks;
-        words[kVwDecoded] = dec_off[nblocks];
-    }
+    publish_verdict(failing, first, sized, bytes, nblocks, dec_off, words);
 }
 
 namespace {
@@ -352,9 +292,7 @@ int launch_crc(fcx_dctx *c, const uint8_t *data, const uint64_t *off, uint64_t o
 }
 }  // namespace
 
-// fcx_digest_shard behind its argument checks
-static int digest_run(fcx_dctx *c, const uint8_t *d_data, uint64_t n, uint32_t B, uint32_t *d_crc, uint32_t *whole,
-                      hipStream_t st) {
+int digest_run(fcx_dctx *c, const uint8_t *d_data, uint64_t n, uint32_t B, uint32_t *d_crc, uint32_t *whole, hipStream_t st) {
     if (whole) *whole = 0;
     if (n == 0) {
         for (uint64_t &v : c->dg.stats) v = 0;
@@ -392,125 +330,61 @@ int check_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, ui
     RepairScratch &P = c->rp;
     VerifyScratch &V = c->vf;
     RangeScratch &R = c->rg;
-    if (!P.host_words) {
-        FCX_TRY(P.words.reserve(8 * kRpWords, "repair words"));
-        FCX_HIP(P.host_words.alloc(8 * kRpWords));
-    }
-    const bool prof = c->profiling;
-    std::unique_ptr<StageTimes> T(prof ? new StageTimes(kDgStages) : nullptr);
-    auto mark = [&](int i) { if (prof) T->mark(i, st); };
-    // the index of the run, in the range API's scratch, and a copy of it for the grouping
-    FCX_TRY(R.rec_off.reserve(8ull * nblocks + 8, "index"));
-    FCX_TRY(R.dec_off.reserve(8ull * nblocks + 8, "index"));
-    FCX_TRY(P.entry_of.reserve(4ull * nblocks, "repair map"));
+    RunTimes T(c, kDgStages, st);
+    RunIndex ix;
     FCX_TRY(D.seg_at.reserve(16ull * nblocks, "digest segments"));
     FCX_TRY(D.seg_len.reserve(8ull * nblocks, "digest segments"));
     FCX_TRY(D.part.reserve(8ull * nblocks, "digest parts"));
-    mark(0);
-    FCX_TRY(fcx_index_shard(c, kind, d_rec, rec_len, nblocks, R.rec_off, R.dec_off, nullptr, st));
-    mark(1);
-    if (prof) FCX_TRY(T->add(0, 1));
-    std::vector<uint64_t> roff(nblocks + 1), doff(nblocks + 1);
-    FCX_HIP(hipMemcpyAsync(roff.data(), R.rec_off, 8ull * nblocks + 8, hipMemcpyDeviceToHost, st));
-    FCX_HIP(hipMemcpyAsync(doff.data(), R.dec_off, 8ull * nblocks + 8, hipMemcpyDeviceToHost, st));
+    FCX_TRY(run_index(c, kind, d_rec, rec_len, nblocks, st, T, &ix));
+    FCX_TRY(T.add(0, 1));
+    const std::vector<uint64_t> &doff = ix.doff;
     // the entries against the index, as an apply checks them
-    FCX_HIP(hipMemsetAsync(P.words, 0, 8 * kRpWords, st));
-    FCX_HIP(hipMemsetAsync(P.words + kRpBadEntry, 0xFF, 16, st));
-    FCX_HIP(hipMemsetAsync(P.entry_of, 0xFF, 4ull * nblocks, st));
-    if (nentries)
-        hipLaunchKernelGGL(k_dgmap, dim3((nentries + kDgThreads - 1) / kDgThreads), dim3(kDgThreads), 0, st, d_entries, nentries,
-                           nblocks, R.dec_off, n, B, data_bytes, P.entry_of, P.words);
-    FCX_HIP(hipGetLastError());
-    FCX_HIP(hipMemcpyAsync(P.host_words, P.words, 8 * kRpWords, hipMemcpyDeviceToHost, st));
+    FCX_TRY(launch_entry_map(c, d_entries, nentries, nblocks, n, B, data_bytes, false, st));
     FCX_HIP(hipMemsetAsync(D.words, 0, 8 * kDgwWords, st));
     FCX_HIP(hipMemsetAsync(D.words + kVwFirst, 0xFF, 8, st));
     FCX_HIP(hipMemsetAsync(D.part, 0, 8ull * nblocks, st));
     FCX_HIP(hipStreamSynchronize(st));
-    if (P.host_words[kRpBadEntry] != ~0ull)
-        return fail(FCX_ERR_FORMAT, "repair: entry " + std::to_string(P.host_words[kRpBadEntry]) + " of the records from " +
-                                        std::to_string(rec_base) + " does not fit its record");
-    auto group_end = [&](uint32_t g0) { return verify_group_end(V, doff.data(), nblocks, g0); };
-    uint64_t need = 0;
-    uint32_t ngroups = 0;
-    for (uint32_t g0 = 0; g0 < nblocks; g0 = group_end(g0), ngroups++) need = std::max(need, doff[group_end(g0)] - doff[g0]);
-    FCX_TRY(V.buf.reserve(need + 64, "verify buffer"));
-    V.groups = ngroups;
-    for (uint32_t g0 = 0; g0 < nblocks;) {
-        const uint32_t g1 = group_end(g0), nrec = g1 - g0;
-        const uint64_t gbytes = doff[g1] - doff[g0];
-        uint64_t got = 0, longest = nentries ? B : 0;
-        for (uint32_t k = g0; k < g1; k++) longest = std::max(longest, doff[k + 1] - doff[k]);
-        mark(1);
-        // (an index entry can only lie inside the run: the index was built from it just now)
-        if (kind == '7')
-            FCX_TRY(fcx_decompress_shard(c, d_rec + roff[g0], rec_len - roff[g0], nrec, V.buf, gbytes, &got, st));
-        else
-            FCX_TRY(lz78_decompress_shard_at(c, d_rec + roff[g0], rec_len - roff[g0], nrec, V.buf, gbytes, &got, st,
-                                             rec_base + g0));
-        if (got != gbytes) return fail(FCX_ERR_INTERNAL, "fcx_check_shard: the decode of a group disagrees with the index");
-        mark(2);
+    FCX_TRY(entry_map_result(c, rec_base));
+    std::vector<RunGroup> groups;
+    FCX_TRY(run_groups(c, ix, nblocks, &groups));
+    for (const RunGroup &g : groups) {
+        const uint32_t g0 = g.g0, nrec = g.g1 - g0;
+        uint64_t longest = nentries ? B : 0;
+        for (uint32_t k = g0; k < g.g1; k++) longest = std::max(longest, doff[k + 1] - doff[k]);
+        T.mark(1);
+        FCX_TRY(decode_group(c, kind, d_rec, rec_len, ix.roff, g0, nrec, V.buf, g.gbytes, st, rec_base, "fcx_check_shard"));
+        T.mark(2);
         if (nentries == 0) {   // the records as they are: the index's offsets are the segments
             FCX_TRY(launch_crc<kDgOffsets>(c, V.buf, R.dec_off + g0, doff[g0], nullptr, 0, 0, nrec, longest, D.part + g0, st));
         } else {
             hipLaunchKernelGGL(k_dgplan, dim3((nrec + kDgThreads - 1) / kDgThreads), dim3(kDgThreads), 0, st, V.buf, doff[g0],
-                               gbytes, R.dec_off, g0, nrec, P.entry_of, d_entries, d_data, data_bytes, D.seg_at, D.seg_len);
+                               g.gbytes, R.dec_off, g0, nrec, P.entry_of, d_entries, d_data, data_bytes, D.seg_at, D.seg_len);
             FCX_TRY(launch_crc<kDgList>(c, nullptr, D.seg_at + 2ull * g0, 0, D.seg_len + 2ull * g0, 0, 0, 2 * nrec, longest,
                                         D.part + 2ull * g0, st));
         }
-        mark(3);
-        if (prof) FCX_TRY(T->add(1, 3));
+        T.mark(3);
+        FCX_TRY(T.add(1, 3));
         D.stats[0] += nentries ? 2ull * nrec : nrec;
         D.stats[2]++;
-        g0 = g1;
     }
-    mark(3);
+    T.mark(3);
     hipLaunchKernelGGL(k_dgsummary, dim3(1), dim3(1024), 0, st, nblocks, ncrc, R.dec_off, n, B, P.entry_of, d_entries, D.part,
                        nentries ? 2u : 1u, d_crc, (const uint32_t *)D.tables, d_blocks, D.words);
-    mark(4);
+    T.mark(4);
     FCX_HIP(hipGetLastError());
     FCX_HIP(hipMemcpyAsync(D.host_words, D.words, 8 * kDgwWords, hipMemcpyDeviceToHost, st));
     FCX_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = D.host_words[i];
     D.stats[1] = doff[nblocks] + data_bytes;   // (at most: what is kept of a repaired record is a prefix)
     D.stats[3] = nentries;
-    c->times.reset();
-    if (prof) {   // the call's own table replaces the last inner decode's
-        FCX_TRY(T->add(3, 4));
-        for (int i = 0; i < kDgStages; i++) c->times.ms[i] = T->ms[i];
-        c->times.publish(kDgStageNames, kDgStages);
-    }
+    FCX_TRY(T.add(3, 4));
+    T.publish(c, kDgStageNames, kDgStages);
     return FCX_OK;
 }
 
 }  // namespace fcx
 
 using namespace fcx;
-
-namespace {
-struct MemSrc {
-    const uint8_t *p;
-    uint64_t len, pos;
-};
-int64_t mem_src_read(void *u, uint8_t *buf, uint64_t cap) {
-    MemSrc *m = (MemSrc *)u;
-    const uint64_t n = std::min(m->len - m->pos, cap);
-    memcpy(buf, m->p + m->pos, n);
-    m->pos += n;
-    return (int64_t)n;
-}
-struct MemDst {
-    uint8_t *p;
-    uint64_t cap, pos;
-};
-int mem_dst_write(void *u, const uint8_t *buf, uint64_t n) {
-    MemDst *m = (MemDst *)u;
-    if (n > m->cap - m->pos) return FCX_ERR_CAPACITY;
-    memcpy(m->p + m->pos, buf, n);
-    m->pos += n;
-    return 0;
-}
-constexpr uint64_t kDgShard = 64ull << 20;   // bytes of the original per device call of fcx_digest_stream
-}  // namespace
 
 extern "C" {
 
@@ -553,13 +427,9 @@ uint32_t fcx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { ret
 int fcx_check_shard(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint64_t n,
                     uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
                     uint64_t data_bytes, const uint32_t *d_crc, uint32_t *d_blocks, uint64_t *stats, void *stream) {
-    if (!c || !stats) return fail(FCX_ERR_ARG, "fcx_check_shard: NULL argument");
-    if (kind != '7' && kind != '8') return fail(FCX_ERR_ARG, "fcx_check_shard: kind must be '7' or '8'");
-    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail(FCX_ERR_ARG, "fcx_check_shard: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
-    if ((n + block_bytes - 1) / block_bytes != nblocks)
-        return fail(FCX_ERR_ARG, "fcx_check_shard: nblocks is not ceil(n / block_bytes)");
-    if ((nblocks && (!d_rec || !d_crc)) || (nentries && !d_entries) || (data_bytes && !d_data))
+    if (!stats) return fail(FCX_ERR_ARG, "fcx_check_shard: NULL argument");
+    FCX_TRY(run_args("fcx_check_shard", c, kind, d_rec, nblocks, n, block_bytes));
+    if ((nblocks && !d_crc) || (nentries && !d_entries) || (data_bytes && !d_data))
         return fail(FCX_ERR_ARG, "fcx_check_shard: NULL argument");
     return check_run(c, kind, d_rec, rec_len, nblocks, nblocks, n, block_bytes, d_entries, nentries, d_data, data_bytes, d_crc,
                      d_blocks, stats, (hipStream_t)stream, 0);
@@ -575,61 +445,6 @@ int fcx_dctx_set_digest_slice(fcx_dctx *c, uint32_t bytes) {
     if (!c || (bytes != 0 && bytes != 4 && bytes != 8 && bytes != 16)) return fail(FCX_ERR_ARG, "fcx_dctx_set_digest_slice: bad argument");
     c->dg.slice = bytes ? bytes : kDgSlice;
     return FCX_OK;
-}
-
-int fcx_digest_stream(fcx_dctx *c, fcx_read_fn rd, void *user, uint32_t block_bytes, fcx_write_fn wr, void *user_wr,
-                      uint64_t *stats) {
-    if (!c || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_digest_stream: NULL argument");
-    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail(FCX_ERR_ARG, "fcx_digest_stream: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
-    FCX_HIP(hipSetDevice(c->device));
-    const uint64_t B = block_bytes, shard = kDgShard / B * B;
-    fcx_digest_file::Writer W;
-    W.wr = wr;
-    W.user = user_wr;
-    if (const int w = W.begin(block_bytes)) return fail(w, W.err);
-    DigestScratch &D = c->dg;
-    std::vector<uint8_t> host;
-    std::vector<uint32_t> vals;
-    for (bool end = false; !end;) {
-        host.resize(shard);
-        uint64_t got = 0;
-        while (got < shard) {
-            const int64_t r = rd(user, host.data() + got, shard - got);
-            if (r < 0) return fail(FCX_ERR_ARG, "read callback failed");
-            if (r == 0) break;
-            got += (uint64_t)r;
-        }
-        end = got < shard;
-        if (got == 0) break;
-        const uint32_t nb = (uint32_t)((got + B - 1) / B);
-        FCX_TRY(D.stage.reserve(shard, "digest staging"));
-        FCX_TRY(D.crc.reserve(4ull * (shard / B), "digest values"));
-        FCX_HIP(hipMemcpyAsync(D.stage, host.data(), got, hipMemcpyHostToDevice, nullptr));
-        FCX_TRY(digest_run(c, D.stage, got, block_bytes, D.crc, nullptr, nullptr));
-        vals.resize(nb);
-        FCX_HIP(hipMemcpy(vals.data(), D.crc, 4ull * nb, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < nb; k++)
-            if (const int w = W.add(vals[k], std::min<uint64_t>(B, got - k * B))) return fail(w, W.err);
-    }
-    if (const int w = W.finish()) return fail(w, W.err);
-    if (stats) {
-        stats[0] = W.n;
-        stats[1] = W.blocks;
-        stats[2] = W.whole;
-    }
-    return FCX_OK;
-}
-
-int fcx_digest_host(fcx_dctx *c, const uint8_t *orig, uint64_t n, uint32_t block_bytes, uint8_t *digest, uint64_t cap,
-                    uint64_t *digest_len) {
-    if (!c || (n && !orig) || !digest_len || (cap && !digest)) return fail(FCX_ERR_ARG, "fcx_digest_host: NULL argument");
-    MemSrc src{orig, n, 0};
-    MemDst dst{digest, cap, 0};
-    const int r = fcx_digest_stream(c, mem_src_read, &src, block_bytes, mem_dst_write, &dst, nullptr);
-    *digest_len = dst.pos;
-    if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_digest_host: digest capacity too small");
-    return r;
 }
 
 }  // extern "C"

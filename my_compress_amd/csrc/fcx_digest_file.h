@@ -1,6 +1,6 @@
 // fcx_digest_file.h — the FCXD file (include/fcx.h): its canonical writer and its
 // streaming reader, over the read / write callbacks of the stream paths.  Host code only, shared by the
-// library's stream forms (fcx_digest.hip, fcx_stream.hip) and the command line's no-device path
+// library's stream forms (fcx_stream.hip) and the command line's no-device path
 // (fcx_cli_host.h), so both write the same bytes and reject the same files.
 #ifndef FCX_DIGEST_FILE_H
 #define FCX_DIGEST_FILE_H
@@ -13,34 +13,23 @@
 
 #include "fcx.h"
 #include "fcx_crc32.h"
+#include "fcx_sidecar_io.h"
 
 namespace fcx_digest_file {
 
-constexpr uint32_t kSection = FCX_DIGEST_SECTION;   // values of a section at most; the writer's: exactly, but the last
+using namespace fcx_sidecar;
 
-inline void put32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }
-inline void put64(uint8_t *p, uint64_t v) { memcpy(p, &v, 8); }
-inline uint32_t get32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline uint64_t get64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
+constexpr uint32_t kSection = FCX_DIGEST_SECTION;   // values of a section at most; the writer's: exactly, but the last
 
 // Canonical writer.  add() takes the blocks' CRC-32 and lengths in block order; a section is written
 // when it holds kSection values, or at finish().  Every function returns 0, or a negative code with the
 // reason in `err`.
-struct Writer {
-    fcx_write_fn wr = nullptr;
-    void *user = nullptr;
+struct Writer : WriteBase {
     std::vector<uint8_t> sec;   // the values of the section in hand, as written
     uint64_t n = 0, blocks = 0;
     uint32_t whole = 0, self = 0;   // the CRC-32 of the bytes so far, of the values so far
-    std::string err;
 
-    int put(const void *p, uint64_t len) {
-        if (len == 0) return 0;
-        const int w = wr(user, (const uint8_t *)p, len);
-        if (w == 0) return 0;
-        err = "write callback failed";
-        return w < 0 ? w : FCX_ERR_ARG;
-    }
+    using WriteBase::WriteBase;
     int begin(uint32_t block_bytes) {
         uint8_t h[FCX_DIGEST_HEADER_BYTES] = {'F', 'C', 'X', 'D', 1, 0, 0, 0};
         put32(h + 8, block_bytes);
@@ -85,39 +74,15 @@ struct Writer {
 // read; finish() expects the end of the file.  One section is in memory at a time.  The block lengths
 // follow from the trailer's n: every block holds block_bytes but the last.  Returns as noted, or
 // FCX_ERR_FORMAT (or the read callback's error) with the reason in `err`.
-struct Reader {
-    fcx_read_fn rd = nullptr;
-    void *user = nullptr;
+struct Reader : ReadBase {
     uint32_t block_bytes = 0;
     std::vector<uint32_t> sec;
     size_t cur = 0;
     bool at_trailer = false, held = false;
     uint64_t n = 0, blocks = 0, seen = 0;
     uint32_t whole = 0, self = 0, acc = 0, last = 0;   // (acc: the CRC-32 of the blocks before `last`)
-    std::string err;
 
-    int bad(const char *why) {
-        err = std::string("digest file: ") + why;
-        return FCX_ERR_FORMAT;
-    }
-    // exactly len bytes, or an error; *eof (when given) is set instead when not one byte is left
-    int get(uint8_t *p, uint64_t len, bool *eof = nullptr) {
-        uint64_t got = 0;
-        while (got < len) {
-            const int64_t r = rd(user, p + got, len - got);
-            if (r < 0) {
-                err = "read callback failed";
-                return FCX_ERR_ARG;
-            }
-            if (r == 0) break;
-            got += (uint64_t)r;
-        }
-        if (got == 0 && eof) {
-            *eof = true;
-            return 0;
-        }
-        return got == len ? 0 : bad("truncated");
-    }
+    Reader(fcx_read_fn r, void *u) : ReadBase("digest file: ", r, u) {}
     int open() {
         uint8_t h[FCX_DIGEST_HEADER_BYTES];
         int r = get(h, sizeof(h));
@@ -193,12 +158,7 @@ struct Reader {
         const int m = more();
         if (m < 0) return m;
         if (m > 0) return bad("values behind the ones that were asked for");
-        uint8_t one;
-        bool eof = false;
-        const int g = get(&one, 1, &eof);
-        if (g && g != FCX_ERR_FORMAT) return g;
-        if (!eof) return bad("bytes behind the trailer");
-        return 0;
+        return expect_end();
     }
     // length of block k of the file (needs the trailer: more() == 0)
     uint64_t block_len(uint64_t k) const {

@@ -10,7 +10,7 @@
 //     k_rscan    one workgroup: the entries compacted in block order, the exclusive u64 sum of the
 //                RAW lengths as data_off, the counts into the status words;
 //     k_rgather  (entry x 16 KiB chunk): a RAW suffix of the original to d_data + data_off.
-//   apply   the index, then
+//   apply   the index, then the entry map (launch_entry_map, which a check of fcx_digest.hip calls too)
 //     k_rmap     one thread per entry: the checks of fcx.h against the index, entry_of[block];
 //     k_rcheck   one thread per record: a record without an entry decodes to its block's length;
 //     the decode: a group of records without entries straight to its place in d_out, a group with
@@ -18,11 +18,10 @@
 //     k_rapply   (record x 16 KiB chunk): the decoded prefix, then the RAW bytes or the fill byte.
 //
 // Both copies store 16 aligned bytes per lane on the destination and read the source, which sits
-// anywhere, through ld16_shifted; the pieces at a range's head and tail go byte by byte.
+// anywhere, through ld16_bounded (fcx_ld16.h).  The host half of an apply is the run core's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <memory>
 #include <string>
 #include <vector>
 
@@ -38,18 +37,11 @@ static_assert(sizeof(fcx_repair_entry) == 32, "the entry is 32 bytes on the devi
 constexpr uint32_t kRThreads = 256;
 constexpr uint32_t kRChunk = 16384;                    // bytes of a block one workgroup copies
 constexpr uint32_t kRRound = 16 * kRThreads * 16;      // bytes k_rplan tests between two votes (64 KiB)
-constexpr uint32_t kRNone = 0xFFFFFFFFu;               // entry_of: the record has no entry
 constexpr uint64_t kRMaxGrid = 0x7FFFFFFFull;
 
-__device__ inline uint32_t block_len(uint64_t k, uint64_t n, uint32_t B) {
-    const uint64_t o0 = k * B;
-    return o0 < n ? (uint32_t)min((uint64_t)B, n - o0) : 0u;
-}
-
 // cnt bytes from src to dst by the workgroup, both anywhere.  Head (to the destination's next 16-byte
-// boundary) and tail go byte by byte; in between every lane stores 16 aligned bytes, loaded through the
-// funnel shift where the aligned window of the source lies inside [rlo, rhi) and byte by byte
-// otherwise, so nothing outside [rlo, rhi) is read and nothing outside [dst, dst + cnt) is written.
+// boundary) and tail go byte by byte; in between every lane stores 16 aligned bytes, read by ld16_bounded
+// within [rlo, rhi), so nothing outside [rlo, rhi) is read and nothing outside [dst, dst + cnt) is written.
 __device__ inline void copy_aligned(uint8_t *dst, const uint8_t *src, uint32_t cnt, const uint8_t *rlo, const uint8_t *rhi) {
     const uint32_t t = threadIdx.x;
     const uint32_t head = min(cnt, (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15));
@@ -58,21 +50,8 @@ __device__ inline void copy_aligned(uint8_t *dst, const uint8_t *src, uint32_t c
     uint8_t *d = dst + head;
     const uint8_t *s = src + head;
     const uint32_t sh = (uint32_t)((uintptr_t)s & 15);
-    for (uint32_t i = 16 * t; i < body; i += 16 * kRThreads) {
-        const uintptr_t w = (uintptr_t)(s + i) - sh;
-        uint4 v;
-        if (w >= (uintptr_t)rlo && w + (sh ? 32 : 16) <= (uintptr_t)rhi) {
-            v = ld16_shifted(s + i, sh);
-        } else {
-            uint32_t x[4];
-            for (uint32_t q = 0; q < 4; q++) {
-                const uint8_t *b = s + i + 4 * q;
-                x[q] = b[0] | (b[1] << 8) | (b[2] << 16) | ((uint32_t)b[3] << 24);
-            }
-            v = make_uint4(x[0], x[1], x[2], x[3]);
-        }
-        *(uint4 *)(d + i) = v;
-    }
+    const uint64_t s0 = (uint64_t)(s - rlo), rlen = (uint64_t)(rhi - rlo);
+    for (uint32_t i = 16 * t; i < body; i += 16 * kRThreads) *(uint4 *)(d + i) = ld16_bounded(rlo, s0 + i, sh, rlen);
     const uint32_t tail = cnt - head - body;   // < 16
     if (t < tail) d[body + t] = s[body + t];
 }
@@ -91,8 +70,8 @@ __device__ inline void fill_aligned(uint8_t *dst, uint32_t cnt, uint32_t v) {
 
 // One workgroup per record.  A record that comes back leaves at once.  Of the others: from = the
 // first difference, len = the rest of the block, and whether those len bytes of the original are all
-// the value of the first of them.  16-byte loads where the aligned 32-byte window lies inside the
-// block, bytes at the suffix's head and tail, as in k_vcompare: nothing outside the block is read.
+// the value of the first of them.  Whole pieces through ld16_bounded within the block, the suffix's last
+// piece, cut short, byte by byte: nothing outside the block is read.
 // The workgroup votes every kRRound bytes and stops at the first piece that differs.
 __global__ __launch_bounds__(kRThreads) void k_rplan(const uint32_t *__restrict__ pairs, const uint8_t *__restrict__ orig,
                                                      uint64_t n, uint32_t B, fcx_repair_entry *__restrict__ plan) {
@@ -100,7 +79,7 @@ __global__ __launch_bounds__(kRThreads) void k_rplan(const uint32_t *__restrict_
     if (fd == FCX_VERIFY_SAME) return;   // (the whole workgroup)
     const uint32_t blen = block_len(k, n, B);
     const uint32_t from = min(fd, blen), len = blen - from;   // (fd <= min(decoded, blen): k_vsummary)
-    const uint8_t *p = orig + (uint64_t)k * B + from;         // read only when len > 0
+    const uint8_t *blk = orig + (uint64_t)k * B, *p = blk + from;   // read only when len > 0
     const uint32_t v = len ? p[0] : 0u, vv = v * 0x01010101u;
     const uint32_t sp = (uint32_t)((uintptr_t)p & 15);
     bool raw = false;
@@ -110,14 +89,11 @@ __global__ __launch_bounds__(kRThreads) void k_rplan(const uint32_t *__restrict_
         for (uint32_t s = 0; s < kRRound / (16 * kRThreads); s++) {
             const uint32_t j = base + 16 * (s * kRThreads + threadIdx.x);
             if (j >= len) continue;
-            // inside: all 16 bytes in the suffix, the aligned window [from + j - sp, + 32) in [0, blen)
-            const bool wide = j + 16 <= len && from + j >= sp && from + j - sp + 32 <= blen;
-            if (wide) {
-                const uint4 x = ld16_shifted(p + j, sp);
+            if (j + 16 <= len) {
+                const uint4 x = ld16_bounded(blk, from + j, sp, blen);
                 bad |= ((x.x ^ vv) | (x.y ^ vv) | (x.z ^ vv) | (x.w ^ vv)) != 0;
             } else {
-                const uint32_t e = min(16u, len - j);
-                for (uint32_t i = 0; i < e; i++) bad |= p[j + i] != v;
+                for (uint32_t i = 0; i < len - j; i++) bad |= p[j + i] != v;
             }
         }
         if (__syncthreads_or(bad)) {   // (uniform)
@@ -210,7 +186,7 @@ __global__ __launch_bounds__(kRThreads) void k_rgather(const fcx_repair_entry *_
 }
 
 // One thread per entry: the checks of fcx.h against the index; the first entry that fails one by
-// atomicMin into kRpBadEntry, entry_of[block] for the others (preset to kRNone).
+// atomicMin into kRpBadEntry, entry_of[block] for the others (preset to kNoEntry).
 __global__ __launch_bounds__(kRThreads) void k_rmap(const fcx_repair_entry *__restrict__ entries, uint32_t nentries,
                                                     uint32_t nblocks, const uint64_t *__restrict__ dec_off, uint64_t n,
                                                     uint32_t B, uint64_t data_bytes, uint32_t *__restrict__ entry_of,
@@ -237,7 +213,7 @@ __global__ __launch_bounds__(kRThreads) void k_rcheck(uint32_t nblocks, const ui
                                                       uint32_t B, const uint32_t *__restrict__ entry_of,
                                                       uint64_t *__restrict__ words) {
     const uint32_t k = blockIdx.x * kRThreads + threadIdx.x;
-    if (k >= nblocks || entry_of[k] != kRNone) return;
+    if (k >= nblocks || entry_of[k] != kNoEntry) return;
     if (dec_off[k + 1] - dec_off[k] != block_len(k, n, B))
         atomicMin((unsigned long long *)words + kRpBadRecord, (unsigned long long)k);
 }
@@ -263,11 +239,11 @@ __global__ __launch_bounds__(kRThreads) void k_rapply(const uint8_t *__restrict_
     const uint32_t dlen = (uint32_t)min(dec_off[k + 1] - dec_off[k], gbytes - min(gbytes, d0));
     const uint32_t ei = entry_of[k];
     fcx_repair_entry e = {};
-    if (ei != kRNone) e = entries[ei];
-    const uint32_t from = ei == kRNone ? min(blen, dlen) : min(e.from, min(blen, dlen));
+    if (ei != kNoEntry) e = entries[ei];
+    const uint32_t from = ei == kNoEntry ? min(blen, dlen) : min(e.from, min(blen, dlen));
     uint8_t *dst = out + (uint64_t)k * B;
     if (lo < from) copy_aligned(dst + lo, dec + d0 + lo, min(hi, from) - lo, dec, dec + gbytes);
-    if (ei == kRNone || hi <= from || from != e.from || (uint64_t)e.from + e.len != blen) return;
+    if (ei == kNoEntry || hi <= from || from != e.from || (uint64_t)e.from + e.len != blen) return;
     const uint32_t a = max(lo, from);
     if (e.kind == FCX_REPAIR_FILL) {
         fill_aligned(dst + a, hi - a, e.fill);
@@ -280,16 +256,48 @@ namespace {
 const char *kRBuildStages[] = {"index", "decode", "compare", "summary", "plan", "gather"};
 const char *kRApplyStages[] = {"index", "check", "decode", "assemble"};
 
-int ready(fcx_dctx *c) {
-    RepairScratch &P = c->rp;
+int ready_words(RepairScratch &P) {
     if (!P.host_words) {
         FCX_TRY(P.words.reserve(8 * kRpWords, "repair words"));
         FCX_HIP(P.host_words.alloc(8 * kRpWords));
     }
-    for (uint64_t &v : P.stats) v = 0;
     return FCX_OK;
 }
+int ready(fcx_dctx *c) {
+    for (uint64_t &v : c->rp.stats) v = 0;
+    return ready_words(c->rp);
+}
 }  // namespace
+
+int launch_entry_map(fcx_dctx *c, const fcx_repair_entry *d_entries, uint32_t nentries, uint32_t nblocks, uint64_t n, uint32_t B,
+                     uint64_t data_bytes, bool with_check, hipStream_t st) {
+    RepairScratch &P = c->rp;
+    FCX_TRY(ready_words(P));
+    FCX_TRY(P.entry_of.reserve(4ull * nblocks, "repair map"));
+    FCX_HIP(hipMemsetAsync(P.words, 0, 8 * kRpWords, st));
+    FCX_HIP(hipMemsetAsync(P.words + kRpBadEntry, 0xFF, 16, st));
+    FCX_HIP(hipMemsetAsync(P.entry_of, 0xFF, 4ull * nblocks, st));
+    if (nentries)
+        hipLaunchKernelGGL(k_rmap, dim3((nentries + kRThreads - 1) / kRThreads), dim3(kRThreads), 0, st, d_entries, nentries,
+                           nblocks, c->rg.dec_off, n, B, data_bytes, P.entry_of, P.words);
+    if (with_check)
+        hipLaunchKernelGGL(k_rcheck, dim3((nblocks + kRThreads - 1) / kRThreads), dim3(kRThreads), 0, st, nblocks, c->rg.dec_off, n,
+                           B, P.entry_of, P.words);
+    FCX_HIP(hipGetLastError());
+    FCX_HIP(hipMemcpyAsync(P.host_words, P.words, 8 * kRpWords, hipMemcpyDeviceToHost, st));
+    return FCX_OK;
+}
+
+int entry_map_result(fcx_dctx *c, uint64_t rec_base) {
+    const uint64_t *w = c->rp.host_words;
+    if (w[kRpBadEntry] != ~0ull)
+        return fail(FCX_ERR_FORMAT, "repair: entry " + std::to_string(w[kRpBadEntry]) + " of the records from " +
+                                        std::to_string(rec_base) + " does not fit its record");
+    if (w[kRpBadRecord] != ~0ull)
+        return fail(FCX_ERR_FORMAT, "repair: record " + std::to_string(rec_base + w[kRpBadRecord]) +
+                                        " does not decode to its block's length and has no entry");
+    return FCX_OK;
+}
 
 int repair_build_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *d_orig,
                      uint64_t n, uint32_t B, fcx_repair_entry *d_entries, uint8_t *d_data, uint64_t data_cap,
@@ -357,19 +365,10 @@ int repair_apply_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_
     RepairScratch &P = c->rp;
     VerifyScratch &V = c->vf;
     RangeScratch &R = c->rg;
-    const bool prof = c->profiling;
-    std::unique_ptr<StageTimes> T(prof ? new StageTimes(4) : nullptr);
-    auto mark = [&](int i) { if (prof) T->mark(i, st); };
-    // the index of the run, in the range API's scratch
-    FCX_TRY(R.rec_off.reserve(8ull * nblocks + 8, "index"));
-    FCX_TRY(R.dec_off.reserve(8ull * nblocks + 8, "index"));
-    FCX_TRY(P.entry_of.reserve(4ull * nblocks, "repair map"));
-    mark(0);
-    FCX_TRY(fcx_index_shard(c, kind, d_rec, rec_len, nblocks, R.rec_off, R.dec_off, nullptr, st));
-    mark(1);
-    std::vector<uint64_t> roff(nblocks + 1), doff(nblocks + 1);
-    std::vector<uint32_t> eof_(nentries ? nblocks : 0);
-    FCX_HIP(hipMemcpyAsync(doff.data(), R.dec_off, 8ull * nblocks + 8, hipMemcpyDeviceToHost, st));
+    RunTimes T(c, 4, st);
+    RunIndex ix;
+    FCX_TRY(run_index(c, kind, d_rec, rec_len, nblocks, st, T, &ix));
+    const std::vector<uint64_t> &doff = ix.doff;
     if (n == kRepairLastFromRun) {   // the last block's length from the run: its entry's, or its decoded bytes
         fcx_repair_entry last = {};
         if (nentries) FCX_HIP(hipMemcpyAsync(&last, d_entries + (nentries - 1), sizeof(last), hipMemcpyDeviceToHost, st));
@@ -383,86 +382,56 @@ int repair_apply_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_
     }
     *out_len = n;
     if (cap < n) return fail(FCX_ERR_CAPACITY, "fcx_repair_apply_shard: output capacity too small");
-    FCX_HIP(hipMemsetAsync(P.words, 0, 8 * kRpWords, st));
-    FCX_HIP(hipMemsetAsync(P.words + kRpBadEntry, 0xFF, 16, st));
-    FCX_HIP(hipMemsetAsync(P.entry_of, 0xFF, 4ull * nblocks, st));
-    if (nentries)
-        hipLaunchKernelGGL(k_rmap, dim3((nentries + kRThreads - 1) / kRThreads), dim3(kRThreads), 0, st, d_entries, nentries,
-                           nblocks, R.dec_off, n, B, data_bytes, P.entry_of, P.words);
-    hipLaunchKernelGGL(k_rcheck, dim3((nblocks + kRThreads - 1) / kRThreads), dim3(kRThreads), 0, st, nblocks, R.dec_off, n, B,
-                       P.entry_of, P.words);
-    mark(2);
-    FCX_HIP(hipGetLastError());
-    FCX_HIP(hipMemcpyAsync(P.host_words, P.words, 8 * kRpWords, hipMemcpyDeviceToHost, st));
-    if (nentries) {
-        FCX_HIP(hipMemcpyAsync(roff.data(), R.rec_off, 8ull * nblocks + 8, hipMemcpyDeviceToHost, st));
-        FCX_HIP(hipMemcpyAsync(eof_.data(), P.entry_of, 4ull * nblocks, hipMemcpyDeviceToHost, st));
-    }
+    FCX_TRY(launch_entry_map(c, d_entries, nentries, nblocks, n, B, data_bytes, true, st));
+    T.mark(2);
+    std::vector<uint32_t> eof_(nentries ? nblocks : 0);
+    if (nentries) FCX_HIP(hipMemcpyAsync(eof_.data(), P.entry_of, 4ull * nblocks, hipMemcpyDeviceToHost, st));
     FCX_HIP(hipStreamSynchronize(st));
-    if (P.host_words[kRpBadEntry] != ~0ull)
-        return fail(FCX_ERR_FORMAT, "repair: entry " + std::to_string(P.host_words[kRpBadEntry]) + " of the records from " +
-                                        std::to_string(rec_base) + " does not fit its record");
-    if (P.host_words[kRpBadRecord] != ~0ull)
-        return fail(FCX_ERR_FORMAT, "repair: record " + std::to_string(rec_base + P.host_words[kRpBadRecord]) +
-                                        " does not decode to its block's length and has no entry");
+    FCX_TRY(entry_map_result(c, rec_base));
     P.stats[0] = nentries;
     P.stats[1] = P.host_words[kRpFills];
     P.stats[2] = data_bytes;
-    if (prof) FCX_TRY(T->add(0, 2));
-    auto decode = [&](uint32_t g0, uint32_t nrec, uint8_t *to, uint64_t want, uint64_t at) -> int {
-        uint64_t got = 0;
-        if (kind == '7') FCX_TRY(fcx_decompress_shard(c, d_rec + at, rec_len - at, nrec, to, want, &got, st));
-        else FCX_TRY(lz78_decompress_shard_at(c, d_rec + at, rec_len - at, nrec, to, want, &got, st, rec_base + g0));
-        if (got != want) return fail(FCX_ERR_INTERNAL, "fcx_repair_apply_shard: the decode of a group disagrees with the index");
-        return FCX_OK;
-    };
+    FCX_TRY(T.add(0, 2));
+    const char *who = "fcx_repair_apply_shard";
     if (nentries == 0) {   // every record decodes to its block: one full decode straight into d_out
-        mark(2);
-        FCX_TRY(decode(0, nblocks, d_out, n, 0));
-        mark(3);
-        if (prof) FCX_TRY(T->add(2, 3));
+        T.mark(2);
+        FCX_TRY(decode_group(c, kind, d_rec, rec_len, ix.roff, 0, nblocks, d_out, n, st, rec_base, who));
+        T.mark(3);
+        FCX_TRY(T.add(2, 3));
         P.stats[3] = 1;
     } else {
-        auto group_end = [&](uint32_t g0) { return verify_group_end(V, doff.data(), nblocks, g0); };
         auto staged = [&](uint32_t g0, uint32_t g1) {
             for (uint32_t k = g0; k < g1; k++)
-                if (eof_[k] != kRNone) return true;
+                if (eof_[k] != kNoEntry) return true;
             return false;
         };
-        uint64_t need = 0;
-        for (uint32_t g0 = 0; g0 < nblocks; g0 = group_end(g0))
-            if (staged(g0, group_end(g0))) need = std::max(need, doff[group_end(g0)] - doff[g0]);
-        FCX_TRY(V.buf.reserve(need + 64, "verify buffer"));
+        std::vector<RunGroup> groups;
+        FCX_TRY(run_groups(c, ix, nblocks, &groups, staged));
         const uint32_t cpb = (B + kRChunk - 1) / kRChunk;
-        for (uint32_t g0 = 0; g0 < nblocks;) {
-            const uint32_t g1 = group_end(g0), nrec = g1 - g0;
-            const uint64_t gbytes = doff[g1] - doff[g0];
-            mark(2);
-            if (!staged(g0, g1)) {   // (each of its records decodes to its block's length: back to back is in place)
-                FCX_TRY(decode(g0, nrec, d_out + (uint64_t)g0 * B, gbytes, roff[g0]));
-                mark(3);
-                mark(4);
+        for (const RunGroup &g : groups) {
+            const uint32_t nrec = g.g1 - g.g0;
+            T.mark(2);
+            if (!staged(g.g0, g.g1)) {   // (each of its records decodes to its block's length: back to back is in place)
+                FCX_TRY(decode_group(c, kind, d_rec, rec_len, ix.roff, g.g0, nrec, d_out + (uint64_t)g.g0 * B, g.gbytes, st,
+                                     rec_base, who));
+                T.mark(3);
+                T.mark(4);
                 P.stats[3]++;
             } else {
                 if ((uint64_t)nrec * cpb > kRMaxGrid) return fail(FCX_ERR_ARG, "fcx_repair_apply_shard: group too large");
-                FCX_TRY(decode(g0, nrec, V.buf, gbytes, roff[g0]));
-                mark(3);
-                hipLaunchKernelGGL(k_rapply, dim3(nrec * cpb), dim3(kRThreads), 0, st, V.buf, doff[g0], gbytes, R.dec_off, g0, cpb,
-                                   P.entry_of, d_entries, d_data, data_bytes, n, B, d_out);
-                mark(4);
+                FCX_TRY(decode_group(c, kind, d_rec, rec_len, ix.roff, g.g0, nrec, V.buf, g.gbytes, st, rec_base, who));
+                T.mark(3);
+                hipLaunchKernelGGL(k_rapply, dim3(nrec * cpb), dim3(kRThreads), 0, st, V.buf, doff[g.g0], g.gbytes, R.dec_off, g.g0,
+                                   cpb, P.entry_of, d_entries, d_data, data_bytes, n, B, d_out);
+                T.mark(4);
                 FCX_HIP(hipGetLastError());
                 P.stats[4]++;
             }
-            if (prof) FCX_TRY(T->add(2, 4));
-            g0 = g1;
+            FCX_TRY(T.add(2, 4));
         }
     }
     FCX_HIP(hipStreamSynchronize(st));
-    c->times.reset();
-    if (prof) {
-        for (int i = 0; i < 4; i++) c->times.ms[i] = T->ms[i];
-        c->times.publish(kRApplyStages, 4);
-    }
+    T.publish(c, kRApplyStages, 4);
     return FCX_OK;
 }
 
@@ -470,25 +439,13 @@ int repair_apply_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_
 
 using namespace fcx;
 
-namespace {
-int check_args(const char *fn, fcx_dctx *c, char kind, const void *d_rec, uint32_t nblocks, uint64_t n, uint32_t B) {
-    const std::string f(fn);
-    if (!c) return fail(FCX_ERR_ARG, f + ": NULL argument");
-    if (kind != '7' && kind != '8') return fail(FCX_ERR_ARG, f + ": kind must be '7' or '8'");
-    if (B == 0 || B > FCX_MAX_BLOCK_BYTES) return fail(FCX_ERR_ARG, f + ": block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
-    if ((n + B - 1) / B != nblocks) return fail(FCX_ERR_ARG, f + ": nblocks is not ceil(n / block_bytes)");
-    if (nblocks && !d_rec) return fail(FCX_ERR_ARG, f + ": NULL argument");
-    return FCX_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int fcx_repair_build_shard(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
                            const uint8_t *d_orig, uint64_t n, uint32_t block_bytes, fcx_repair_entry *d_entries, uint8_t *d_data,
                            uint64_t data_cap, uint32_t *nentries, uint64_t *data_bytes, uint64_t *stats, void *stream) {
     if (!nentries || !data_bytes) return fail(FCX_ERR_ARG, "fcx_repair_build_shard: NULL argument");
-    FCX_TRY(check_args("fcx_repair_build_shard", c, kind, d_rec, nblocks, n, block_bytes));
+    FCX_TRY(run_args("fcx_repair_build_shard", c, kind, d_rec, nblocks, n, block_bytes));
     if (nblocks && !d_orig) return fail(FCX_ERR_ARG, "fcx_repair_build_shard: NULL argument");
     if ((!d_entries && d_data) || (!d_data && data_cap))
         return fail(FCX_ERR_ARG, "fcx_repair_build_shard: d_data without d_entries, or a capacity without d_data");
@@ -500,7 +457,7 @@ int fcx_repair_apply_shard(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_
                            uint32_t block_bytes, const fcx_repair_entry *d_entries, uint32_t nentries, const uint8_t *d_data,
                            uint64_t data_bytes, uint8_t *d_out, uint64_t cap, uint64_t *out_len, void *stream) {
     if (!out_len) return fail(FCX_ERR_ARG, "fcx_repair_apply_shard: NULL argument");
-    FCX_TRY(check_args("fcx_repair_apply_shard", c, kind, d_rec, nblocks, n, block_bytes));
+    FCX_TRY(run_args("fcx_repair_apply_shard", c, kind, d_rec, nblocks, n, block_bytes));
     if ((nentries && !d_entries) || (data_bytes && !d_data) || (n && cap && !d_out))
         return fail(FCX_ERR_ARG, "fcx_repair_apply_shard: NULL argument");
     if (cap < n) {

@@ -11,35 +11,24 @@
 #include <vector>
 
 #include "fcx.h"
+#include "fcx_sidecar_io.h"
 
 namespace fcx_repair_file {
+
+using namespace fcx_sidecar;
 
 constexpr uint32_t kWindow = 256;          // entries of a section at most; the writer's sections: block >> 8
 constexpr uint32_t kTrailerMark = 0xFFFFFFFFu;
 
-inline void put32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }
-inline void put64(uint8_t *p, uint64_t v) { memcpy(p, &v, 8); }
-inline uint32_t get32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline uint64_t get64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
-
 // Canonical writer.  add() takes the entries in ascending file-wide block order with their RAW bytes;
 // a section is written when an entry of the next window arrives, or at finish().  Every function
 // returns 0, or a negative code with the reason in `err`.
-struct Writer {
-    fcx_write_fn wr = nullptr;
-    void *user = nullptr;
+struct Writer : WriteBase {
     std::vector<fcx_repair_entry> sec;
     std::vector<uint8_t> data;
     uint64_t entries = 0, data_bytes = 0, last_block = 0;
-    std::string err;
 
-    int put(const void *p, uint64_t n) {
-        if (n == 0) return 0;
-        const int w = wr(user, (const uint8_t *)p, n);
-        if (w == 0) return 0;
-        err = "write callback failed";
-        return w < 0 ? w : FCX_ERR_ARG;
-    }
+    using WriteBase::WriteBase;
     int begin(char kind, uint32_t block_bytes) {
         uint8_t h[FCX_REPAIR_HEADER_BYTES] = {'F', 'C', 'X', 'R', 1, (uint8_t)kind, 0, 0};
         put32(h + 8, block_bytes);
@@ -99,9 +88,7 @@ struct Writer {
 // at a time: <= 256 entries and <= 256 blocks of data.  Blocks must ascend strictly over the whole
 // file; where the section boundaries fall does not matter.  Returns as noted, or FCX_ERR_FORMAT (or
 // the read callback's error) with the reason in `err`.
-struct Reader {
-    fcx_read_fn rd = nullptr;
-    void *user = nullptr;
+struct Reader : ReadBase {
     char kind = 0;
     uint32_t block_bytes = 0;
     std::vector<fcx_repair_entry> sec;
@@ -110,30 +97,8 @@ struct Reader {
     bool at_trailer = false, any = false;
     uint64_t last_block = 0, entries = 0, data_bytes = 0;
     uint8_t trailer[FCX_REPAIR_TRAILER_BYTES];
-    std::string err;
 
-    int bad(const char *why) {
-        err = std::string("repair file: ") + why;
-        return FCX_ERR_FORMAT;
-    }
-    // exactly n bytes, or an error; *eof (when given) is set instead when not one byte is left
-    int get(uint8_t *p, uint64_t n, bool *eof = nullptr) {
-        uint64_t got = 0;
-        while (got < n) {
-            const int64_t r = rd(user, p + got, n - got);
-            if (r < 0) {
-                err = "read callback failed";
-                return FCX_ERR_ARG;
-            }
-            if (r == 0) break;
-            got += (uint64_t)r;
-        }
-        if (got == 0 && eof) {
-            *eof = true;
-            return 0;
-        }
-        return got == n ? 0 : bad("truncated");
-    }
+    Reader(fcx_read_fn r, void *u) : ReadBase("repair file: ", r, u) {}
     int open() {
         uint8_t h[FCX_REPAIR_HEADER_BYTES];
         int r = get(h, sizeof(h));
@@ -204,12 +169,7 @@ struct Reader {
         if (get64(trailer + 16) != records) return bad("the trailer's record count is not the file's");
         if (get64(trailer + 8) != n) return bad("the trailer's byte count is not what was written");
         if (get64(trailer + 24) != entries || get64(trailer + 32) != data_bytes) return bad("the trailer's entry counts are not the sections'");
-        uint8_t one;
-        bool eof = false;
-        const int g = get(&one, 1, &eof);
-        if (g && g != FCX_ERR_FORMAT) return g;
-        if (!eof) return bad("bytes behind the trailer");
-        return 0;
+        return expect_end();
     }
 };
 

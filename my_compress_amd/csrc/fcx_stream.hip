@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "fcx.h"
-#include "fcx_dec_shared.h"   // lz78_decompress_shard_at
+#include "fcx_dec_shared.h"   // lz78_decompress_shard_at, the *_run forms and run_args
 #include "fcx_device.h"       // the compress status words a slot's hlen mirrors
 #include "fcx_host.h"
 #include "fcx_digest_file.h"
@@ -316,6 +316,104 @@ int stream_groups(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, u
     return FCX_OK;
 }
 
+// ---- what the group functions of the stream forms share ----
+
+// a group's got decoded bytes at x.dout to the write callback
+int write_group(Slot &x, uint64_t got, fcx_write_fn wr, void *user, hipStream_t st, uint64_t *tout) {
+    FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, st));
+    FCX_HIP(hipStreamSynchronize(st));
+    const int w = wr(user, x.hout, got);
+    if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
+    *tout += got;
+    return FCX_OK;
+}
+
+// a stream form's checks of run_args: it has no run in hand yet
+int block_arg(const char *fn, fcx_dctx *c, uint32_t block_bytes) { return run_args(fn, c, '7', nullptr, 0, 0, block_bytes); }
+
+// The group's nb blocks of the original to x.dout, staged where a decompress stages the decoded bytes (every
+// record is >= 7 bytes of a staging that holds 1 MiB of output per 7 bytes of input); *got: their bytes.
+int stage_original(const char *fn, fcx_read_fn rd_orig, void *user_orig, Slot &x, uint32_t nb, uint64_t B, uint64_t out_cap,
+                   bool *orig_end, uint64_t *got, hipStream_t st) {
+    const uint64_t want = (uint64_t)nb * B;
+    if (want > out_cap) return fail(FCX_ERR_INTERNAL, std::string(fn) + ": staging too small");
+    const int64_t g = *orig_end ? 0 : read_full(rd_orig, user_orig, x.hout, want);
+    if (g < 0) return fail(FCX_ERR_ARG, "read callback failed");
+    if ((uint64_t)g < want) *orig_end = true;
+    if (g) FCX_HIP(hipMemcpyAsync(x.dout, x.hout, (uint64_t)g, hipMemcpyHostToDevice, st));
+    *got = (uint64_t)g;
+    return FCX_OK;
+}
+
+// The entries of records [before, before + nb) (F null: none), their sections read now and no further:
+// block and data_off rebased to the group, to rp.entries, their RAW bytes to rp.data.
+int load_entries(fcx_dctx *dctx, fcx_repair_file::Reader *F, uint64_t before, uint32_t nb, std::vector<fcx_repair_entry> *ents,
+                 std::vector<uint8_t> *raw, hipStream_t st) {
+    ents->clear();
+    raw->clear();
+    while (F) {
+        fcx_repair_entry e;
+        const uint8_t *bytes = nullptr;
+        const int g = F->next(before, before + nb, &e, &bytes);
+        if (g < 0) return fail(g, F->err);
+        if (g == 0) break;
+        e.block -= before;
+        e.data_off = 0;
+        if (e.kind == FCX_REPAIR_RAW) {
+            e.data_off = raw->size();
+            raw->insert(raw->end(), bytes, bytes + e.len);
+        }
+        ents->push_back(e);
+    }
+    RepairScratch &P = dctx->rp;
+    FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * ents->size(), "repair entries"));
+    FCX_TRY(P.data.reserve(raw->size(), "repair data"));
+    if (!ents->empty())
+        FCX_HIP(hipMemcpyAsync(P.entries, ents->data(), sizeof(fcx_repair_entry) * ents->size(), hipMemcpyHostToDevice, st));
+    if (!raw->empty()) FCX_HIP(hipMemcpyAsync(P.data, raw->data(), raw->size(), hipMemcpyHostToDevice, st));
+    return FCX_OK;
+}
+
+// a group's six stats into the running sum of the file's, the first failing block numbered file-wide
+void fold_stats(uint64_t *sum, const uint64_t *gs, uint64_t before) {
+    if (gs[2] != ~0ull && sum[2] == ~0ull) sum[2] = before + gs[2];
+    for (int i : {0, 1, 3, 4, 5}) sum[i] += gs[i];
+}
+
+// the end of a verify or check stream: bytes of the original behind the last record count as differing
+// and are reported last, with block = the number of records
+int finish_stats(uint64_t *sum, uint64_t extra, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
+    sum[4] += extra;
+    if (extra && on_block) on_block(user_cb, sum[0], extra, 0, 0);
+    for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = sum[i];
+    return FCX_OK;
+}
+
+// passes a read callback through and keeps the first bytes that went by: the FCX file's header, for the
+// kind of a file without records (stream_groups calls no group then)
+struct PeekRead {
+    fcx_read_fn rd;
+    void *user;
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint64_t seen;
+};
+int64_t peek_read(void *u, uint8_t *buf, uint64_t cap) {
+    PeekRead *p = (PeekRead *)u;
+    const int64_t r = p->rd(p->user, buf, cap);
+    for (int64_t i = 0; i < r && p->seen < sizeof(p->hdr); i++) p->hdr[p->seen++] = buf[i];
+    return r;
+}
+
+// the repair file's codec against a group's `kind`; kind 0, behind the last group: a file without records
+// has its header to go by
+int codec_check(const fcx_repair_file::Reader &F, char kind, const PeekRead &pk, uint64_t records) {
+    if (!kind && records == 0 && pk.seen == sizeof(pk.hdr)) kind = pk.hdr[3] == '7' ? '7' : '8';
+    if (kind && kind != F.kind) return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+    return FCX_OK;
+}
+
+constexpr uint64_t kDgShard = 64ull << 20;   // bytes of the original per device call of fcx_digest_stream
+
 }  // namespace
 
 extern "C" {
@@ -330,12 +428,7 @@ int fcx_decompress_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void 
         uint64_t got = 0;
         if (lz78) FCX_TRY(fcx::lz78_decompress_shard_at(dctx, x.din, used, nb, x.dout, out_cap, &got, st, before));
         else FCX_TRY(fcx_decompress_shard(dctx, x.din, used, nb, x.dout, out_cap, &got, st));
-        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, st));
-        FCX_HIP(hipStreamSynchronize(st));
-        const int w = wr(user, x.hout, got);
-        if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
-        tout += got;
-        return FCX_OK;
+        return write_group(x, got, wr, user, st, &tout);
     });
     if (r) return r;
     if (total_out) *total_out = tout;
@@ -356,13 +449,7 @@ int fcx_decompress_range_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr,
         uint64_t got = 0, gtotal = 0;
         FCX_TRY(fcx::range_shard(dctx, lz78 ? '8' : '7', x.din, used, nb, nullptr, nullptr, lo, n, x.dout, out_cap, &got, st,
                                  before, &gtotal));
-        if (got) {
-            FCX_HIP(hipMemcpyAsync(x.hout, x.dout, got, hipMemcpyDeviceToHost, st));
-            FCX_HIP(hipStreamSynchronize(st));
-            const int w = wr(user, x.hout, got);
-            if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
-            tout += got;
-        }
+        if (got) FCX_TRY(write_group(x, got, wr, user, st, &tout));
         pos += gtotal;
         return pos >= end ? kStopReading : FCX_OK;
     });
@@ -386,8 +473,7 @@ int fcx_decompress_range_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len
 int fcx_verify_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_orig, void *user_orig,
                       uint32_t block_bytes, uint64_t max_in, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
     if (!dctx || !rd || !rd_orig || !stats) return fail(FCX_ERR_ARG, "fcx_verify_stream: NULL argument");
-    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail(FCX_ERR_ARG, "fcx_verify_stream: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
+    FCX_TRY(block_arg("fcx_verify_stream", dctx, block_bytes));
     const uint64_t B = block_bytes;
     uint64_t sum[FCX_VERIFY_STATS] = {0, 0, ~0ull, 0, 0, 0};
     std::vector<uint32_t> pairs;
@@ -399,27 +485,20 @@ int fcx_verify_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd
                                     hipStream_t st) -> int {
         spare = x.hout;
         spare_cap = out_cap;
-        // the group's blocks of the original, staged where a decompress stages the decoded bytes
-        // (every record is >= 7 bytes of a staging that holds 1 MiB of output per 7 bytes of input)
-        const uint64_t want = (uint64_t)nb * B;
-        if (want > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_verify_stream: staging too small");
-        int64_t got = orig_end ? 0 : read_full(rd_orig, user_orig, x.hout, want);
-        if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
-        if ((uint64_t)got < want) orig_end = true;
-        if (got) FCX_HIP(hipMemcpyAsync(x.dout, x.hout, (uint64_t)got, hipMemcpyHostToDevice, st));
+        uint64_t got = 0;
+        FCX_TRY(stage_original("fcx_verify_stream", rd_orig, user_orig, x, nb, B, out_cap, &orig_end, &got, st));
         FCX_TRY(dctx->vf.blocks.reserve(8ull * nb, "verify pairs"));
         uint64_t gs[FCX_VERIFY_STATS];
-        FCX_TRY(fcx::verify_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, (uint64_t)got, block_bytes, dctx->vf.blocks,
-                                gs, st, before));
+        FCX_TRY(fcx::verify_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, got, block_bytes, dctx->vf.blocks, gs, st,
+                                before));
         pairs.resize(2ull * nb);
         FCX_HIP(hipMemcpy(pairs.data(), dctx->vf.blocks, 8ull * nb, hipMemcpyDeviceToHost));
         for (uint32_t k = 0; k < nb && on_block; k++) {
             if (pairs[2 * k + 1] == FCX_VERIFY_SAME) continue;
-            const uint64_t o0 = (uint64_t)k * B, blen = o0 < (uint64_t)got ? ((uint64_t)got - o0 < B ? (uint64_t)got - o0 : B) : 0;
+            const uint64_t o0 = (uint64_t)k * B, blen = o0 < got ? std::min(B, got - o0) : 0;
             on_block(user_cb, before + k, blen, pairs[2 * k], pairs[2 * k + 1]);
         }
-        if (gs[2] != ~0ull && sum[2] == ~0ull) sum[2] = before + gs[2];
-        for (int i : {0, 1, 3, 4, 5}) sum[i] += gs[i];
+        fold_stats(sum, gs, before);
         return FCX_OK;
     });
     if (r) return r;
@@ -435,12 +514,7 @@ int fcx_verify_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd
             extra += (uint64_t)got;
         }
     }
-    if (extra) {
-        sum[4] += extra;
-        if (on_block) on_block(user_cb, sum[0], extra, 0, 0);
-    }
-    for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = sum[i];
-    return FCX_OK;
+    return finish_stats(sum, extra, on_block, user_cb, stats);
 }
 
 int fcx_verify_host(fcx_dctx *dctx, char kind, const uint8_t *rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *orig,
@@ -474,40 +548,14 @@ int fcx_decompress_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint
     return FCX_OK;
 }
 
-}  // extern "C"
-
 // ---- the repair sidecar's stream and host forms (include/fcx.h) ----------------------
-
-namespace {
-
-// passes a read callback through and keeps the first bytes that went by: the FCX file's header, for the
-// kind of a file without records (stream_groups calls no group then)
-struct PeekRead {
-    fcx_read_fn rd;
-    void *user;
-    uint8_t hdr[FCX_HEADER_BYTES];
-    uint64_t seen;
-};
-int64_t peek_read(void *u, uint8_t *buf, uint64_t cap) {
-    PeekRead *p = (PeekRead *)u;
-    const int64_t r = p->rd(p->user, buf, cap);
-    for (int64_t i = 0; i < r && p->seen < sizeof(p->hdr); i++) p->hdr[p->seen++] = buf[i];
-    return r;
-}
-
-}  // namespace
-
-extern "C" {
 
 int fcx_repair_build_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_orig, void *user_orig,
                             uint32_t block_bytes, uint64_t max_in, fcx_write_fn wr, void *user_wr, uint64_t *stats) {
     if (!dctx || !rd || !rd_orig || !wr) return fail(FCX_ERR_ARG, "fcx_repair_build_stream: NULL argument");
-    if (block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
-        return fail(FCX_ERR_ARG, "fcx_repair_build_stream: block_bytes outside [1, FCX_MAX_BLOCK_BYTES]");
+    FCX_TRY(block_arg("fcx_repair_build_stream", dctx, block_bytes));
     const uint64_t B = block_bytes;
-    fcx_repair_file::Writer W;
-    W.wr = wr;
-    W.user = user_wr;
+    fcx_repair_file::Writer W(wr, user_wr);
     PeekRead pk{rd, user, {}, 0};
     bool begun = false, orig_end = false;
     uint64_t total_n = 0, records = 0;
@@ -520,23 +568,18 @@ int fcx_repair_build_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read
             if (const int w = W.begin(lz78 ? '8' : '7', block_bytes)) return fail(w, W.err);
             begun = true;
         }
-        // the group's blocks of the original, staged where a decompress stages the decoded bytes
-        const uint64_t want = (uint64_t)nb * B;
-        if (want > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_repair_build_stream: staging too small");
-        const int64_t got = orig_end ? 0 : read_full(rd_orig, user_orig, x.hout, want);
-        if (got < 0) return fail(FCX_ERR_ARG, "read callback failed");
-        if ((uint64_t)got < want) orig_end = true;
-        if (((uint64_t)got + B - 1) / B != nb)
+        uint64_t got = 0;
+        FCX_TRY(stage_original("fcx_repair_build_stream", rd_orig, user_orig, x, nb, B, out_cap, &orig_end, &got, st));
+        if ((got + B - 1) / B != nb)
             return fail(FCX_ERR_ARG, "fcx_repair_build_stream: the original has no bytes for record " +
-                                         std::to_string(before + ((uint64_t)got + B - 1) / B));
-        FCX_HIP(hipMemcpyAsync(x.dout, x.hout, (uint64_t)got, hipMemcpyHostToDevice, st));
+                                         std::to_string(before + (got + B - 1) / B));
         RepairScratch &P = dctx->rp;
         FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * (uint64_t)nb, "repair entries"));
-        FCX_TRY(P.data.reserve((uint64_t)got, "repair data"));   // (the RAW bytes are bytes of the group's blocks)
+        FCX_TRY(P.data.reserve(got, "repair data"));   // (the RAW bytes are bytes of the group's blocks)
         uint32_t ne = 0;
         uint64_t nd = 0;
-        FCX_TRY(fcx::repair_build_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, (uint64_t)got, block_bytes, P.entries,
-                                      P.data, (uint64_t)got, &ne, &nd, nullptr, st, before));
+        FCX_TRY(fcx::repair_build_run(dctx, lz78 ? '8' : '7', x.din, used, nb, x.dout, got, block_bytes, P.entries, P.data, got,
+                                      &ne, &nd, nullptr, st, before));
         ents.resize(ne);
         raw.resize(nd);
         if (ne) FCX_HIP(hipMemcpy(ents.data(), P.entries, sizeof(fcx_repair_entry) * (uint64_t)ne, hipMemcpyDeviceToHost));
@@ -546,7 +589,7 @@ int fcx_repair_build_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read
             e.block += before;
             if (const int w = W.add(e, bytes)) return fail(w, W.err);
         }
-        total_n += (uint64_t)got;
+        total_n += got;
         records += nb;
         return FCX_OK;
     });
@@ -572,9 +615,7 @@ int fcx_repair_build_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read
 int fcx_repair_apply_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_rep, void *user_rep, fcx_write_fn wr,
                             void *user_out, uint64_t max_in, uint64_t *total_out) {
     if (!dctx || !rd || !rd_rep || !wr) return fail(FCX_ERR_ARG, "fcx_repair_apply_stream: NULL argument");
-    fcx_repair_file::Reader F;
-    F.rd = rd_rep;
-    F.user = user_rep;
+    fcx_repair_file::Reader F(rd_rep, user_rep);
     if (const int f = F.open()) return fail(f, F.err);
     const uint32_t B = F.block_bytes;
     PeekRead pk{rd, user, {}, 0};
@@ -585,49 +626,22 @@ int fcx_repair_apply_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read
     const int r = stream_groups(dctx, peek_read, &pk, max_in, nullptr, nullptr,
                                 [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before,
                                     hipStream_t st) -> int {
-        if ((lz78 ? '8' : '7') != F.kind) return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        FCX_TRY(codec_check(F, lz78 ? '8' : '7', pk, records));
         if (short_seen)
             return fail(FCX_ERR_FORMAT, "repair: record " + std::to_string(before - 1) +
                                             " gives a block shorter than the block size and is not the last");
         if ((uint64_t)nb * B > out_cap) return fail(FCX_ERR_INTERNAL, "fcx_repair_apply_stream: staging too small");
-        // the group's entries: the sections that hold them are read now, and no further
-        ents.clear();
-        raw.clear();
-        for (;;) {
-            fcx_repair_entry e;
-            const uint8_t *bytes = nullptr;
-            const int g = F.next(before, before + nb, &e, &bytes);
-            if (g < 0) return fail(g, F.err);
-            if (g == 0) break;
-            e.block -= before;
-            e.data_off = 0;
-            if (e.kind == FCX_REPAIR_RAW) {
-                e.data_off = raw.size();
-                raw.insert(raw.end(), bytes, bytes + e.len);
-            }
-            ents.push_back(e);
-        }
+        FCX_TRY(load_entries(dctx, &F, before, nb, &ents, &raw, st));
         RepairScratch &P = dctx->rp;
-        FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * ents.size(), "repair entries"));
-        FCX_TRY(P.data.reserve(raw.size(), "repair data"));
-        if (!ents.empty())
-            FCX_HIP(hipMemcpyAsync(P.entries, ents.data(), sizeof(fcx_repair_entry) * ents.size(), hipMemcpyHostToDevice, st));
-        if (!raw.empty()) FCX_HIP(hipMemcpyAsync(P.data, raw.data(), raw.size(), hipMemcpyHostToDevice, st));
         uint64_t n = 0;
         FCX_TRY(fcx::repair_apply_run(dctx, lz78 ? '8' : '7', x.din, used, nb, fcx::kRepairLastFromRun, B, P.entries,
                                       (uint32_t)ents.size(), P.data, raw.size(), x.dout, out_cap, &n, st, before));
         if (n < (uint64_t)nb * B) short_seen = true;
-        FCX_HIP(hipMemcpyAsync(x.hout, x.dout, n, hipMemcpyDeviceToHost, st));
-        FCX_HIP(hipStreamSynchronize(st));
-        const int w = wr(user_out, x.hout, n);
-        if (w) return fail(w < 0 ? w : FCX_ERR_ARG, "write callback failed");
-        tout += n;
         records += nb;
-        return FCX_OK;
+        return write_group(x, n, wr, user_out, st, &tout);
     });
     if (r) return r;
-    if (records == 0 && pk.seen == sizeof(pk.hdr) && (pk.hdr[3] == '7' ? '7' : '8') != F.kind)
-        return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+    FCX_TRY(codec_check(F, 0, pk, records));
     if (const int f = F.finish(tout, records)) return fail(f, F.err);
     if (total_out) *total_out = tout;
     return FCX_OK;
@@ -642,8 +656,7 @@ int fcx_repair_build_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, co
     const int r = fcx_repair_build_stream(dctx, mem_read, &comp, mem_read, &org, block_bytes, in_len - FCX_HEADER_BYTES, mem_write,
                                           &out, nullptr);
     *repair_len = out.out_pos;
-    if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_repair_build_host: repair capacity too small");
-    return r;
+    return r == FCX_ERR_CAPACITY ? fail(r, "fcx_repair_build_host: repair capacity too small") : r;
 }
 
 int fcx_repair_apply_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
@@ -654,29 +667,20 @@ int fcx_repair_apply_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, co
     const int r = fcx_repair_apply_stream(dctx, mem_read, &comp, mem_read, &rep, mem_write, &dst, in_len - FCX_HEADER_BYTES,
                                           nullptr);
     *out_len = dst.out_pos;
-    if (r == FCX_ERR_CAPACITY) return fail(r, "fcx_repair_apply_host: output capacity too small");
-    return r;
+    return r == FCX_ERR_CAPACITY ? fail(r, "fcx_repair_apply_host: output capacity too small") : r;
 }
 
-}  // extern "C"
-
 // ---- the content digest's check, stream and host forms (include/fcx.h) ---------------
-
-extern "C" {
 
 int fcx_check_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_rep, void *user_rep, fcx_read_fn rd_dig,
                      void *user_dig, uint64_t max_in, fcx_verify_fn on_block, void *user_cb, uint64_t *stats) {
     if (!dctx || !rd || !rd_dig || !stats) return fail(FCX_ERR_ARG, "fcx_check_stream: NULL argument");
-    fcx_digest_file::Reader G;
-    G.rd = rd_dig;
-    G.user = user_dig;
+    fcx_digest_file::Reader G(rd_dig, user_dig);
     if (const int g = G.open()) return fail(g, G.err);
     const uint32_t block_bytes = G.block_bytes;
     const uint64_t B = block_bytes;
-    fcx_repair_file::Reader F;
+    fcx_repair_file::Reader F(rd_rep, user_rep);
     if (rd_rep) {
-        F.rd = rd_rep;
-        F.user = user_rep;
         if (const int f = F.open()) return fail(f, F.err);
         if (F.block_bytes != block_bytes) return fail(FCX_ERR_FORMAT, "repair file: made for another block size than the digest file's");
     }
@@ -688,7 +692,7 @@ int fcx_check_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_
     std::vector<uint8_t> raw;
     const int r = stream_groups(dctx, peek_read, &pk, max_in, nullptr, nullptr,
                                 [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
-        if (rd_rep && (lz78 ? '8' : '7') != F.kind) return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        if (rd_rep) FCX_TRY(codec_check(F, lz78 ? '8' : '7', pk, records));
         // the group's values: the sections that hold them are read now, and no further; whether the
         // group's last block is the file's last, and so shorter, shows once the sections have ended
         want.clear();
@@ -698,31 +702,11 @@ int fcx_check_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_
         if (m < 0) return fail(m, G.err);
         uint64_t n = (uint64_t)got * B;
         if (m == 0 && got) n = (uint64_t)(got - 1) * B + G.block_len(before + (uint64_t)got - 1);
-        ents.clear();
-        raw.clear();
-        while (rd_rep) {
-            fcx_repair_entry e;
-            const uint8_t *bytes = nullptr;
-            const int g = F.next(before, before + nb, &e, &bytes);
-            if (g < 0) return fail(g, F.err);
-            if (g == 0) break;
-            e.block -= before;
-            e.data_off = 0;
-            if (e.kind == FCX_REPAIR_RAW) {
-                e.data_off = raw.size();
-                raw.insert(raw.end(), bytes, bytes + e.len);
-            }
-            ents.push_back(e);
-        }
+        FCX_TRY(load_entries(dctx, rd_rep ? &F : nullptr, before, nb, &ents, &raw, st));
         RepairScratch &P = dctx->rp;
         DigestScratch &D = dctx->dg;
-        FCX_TRY(P.entries.reserve(sizeof(fcx_repair_entry) * ents.size(), "repair entries"));
-        FCX_TRY(P.data.reserve(raw.size(), "repair data"));
         FCX_TRY(D.crc.reserve(4ull * nb, "digest values"));
         FCX_TRY(D.blocks.reserve(8ull * nb, "digest pairs"));
-        if (!ents.empty())
-            FCX_HIP(hipMemcpyAsync(P.entries, ents.data(), sizeof(fcx_repair_entry) * ents.size(), hipMemcpyHostToDevice, st));
-        if (!raw.empty()) FCX_HIP(hipMemcpyAsync(P.data, raw.data(), raw.size(), hipMemcpyHostToDevice, st));
         if (got) FCX_HIP(hipMemcpyAsync(D.crc, want.data(), 4ull * (uint64_t)got, hipMemcpyHostToDevice, st));
         uint64_t gs[FCX_VERIFY_STATS];
         FCX_TRY(fcx::check_run(dctx, lz78 ? '8' : '7', x.din, used, nb, (uint32_t)got, n, block_bytes, P.entries,
@@ -735,28 +719,20 @@ int fcx_check_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, fcx_read_fn rd_
             if (on_block && (k >= (uint64_t)got || pairs[2 * k] != blen || pairs[2 * k + 1] != want[k]))
                 on_block(user_cb, before + k, blen, pairs[2 * k], pairs[2 * k + 1]);
         }
-        if (gs[2] != ~0ull && sum[2] == ~0ull) sum[2] = before + gs[2];
-        for (int i : {0, 1, 3, 4, 5}) sum[i] += gs[i];
+        fold_stats(sum, gs, before);
         records += nb;
         return FCX_OK;
     });
     if (r) return r;
     if (rd_rep) {
-        if (records == 0 && pk.seen == sizeof(pk.hdr) && (pk.hdr[3] == '7' ? '7' : '8') != F.kind)
-            return fail(FCX_ERR_FORMAT, "repair file: made for the other codec");
+        FCX_TRY(codec_check(F, 0, pk, records));
         if (const int f = F.finish(result_bytes, records)) return fail(f, F.err);
     }
     // blocks of the digest file behind the last record
     const int64_t left = G.take(~0ull, nullptr);
     if (left < 0) return fail((int)left, G.err);
     if (const int g = G.finish()) return fail(g, G.err);
-    if (left) {
-        const uint64_t extra = G.n - std::min(G.n, records * B);
-        sum[4] += extra;
-        if (on_block) on_block(user_cb, sum[0], extra, 0, 0);
-    }
-    for (int i = 0; i < FCX_VERIFY_STATS; i++) stats[i] = sum[i];
-    return FCX_OK;
+    return finish_stats(sum, left ? G.n - std::min(G.n, records * B) : 0, on_block, user_cb, stats);
 }
 
 int fcx_check_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
@@ -766,6 +742,52 @@ int fcx_check_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uin
     MemIO comp{in, in_len, 0, nullptr, 0, 0}, rep{repair, repair_len, 0, nullptr, 0, 0}, dig{digest, digest_len, 0, nullptr, 0, 0};
     return fcx_check_stream(dctx, mem_read, &comp, repair ? mem_read : nullptr, &rep, mem_read, &dig, in_len - FCX_HEADER_BYTES,
                             on_block, user_cb, stats);
+}
+
+int fcx_digest_stream(fcx_dctx *c, fcx_read_fn rd, void *user, uint32_t block_bytes, fcx_write_fn wr, void *user_wr,
+                      uint64_t *stats) {
+    if (!c || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_digest_stream: NULL argument");
+    FCX_TRY(block_arg("fcx_digest_stream", c, block_bytes));
+    FCX_HIP(hipSetDevice(c->device));
+    const uint64_t B = block_bytes, shard = kDgShard / B * B;
+    fcx_digest_file::Writer W(wr, user_wr);
+    if (const int w = W.begin(block_bytes)) return fail(w, W.err);
+    DigestScratch &D = c->dg;
+    std::vector<uint8_t> host;
+    std::vector<uint32_t> vals;
+    for (bool end = false; !end;) {
+        host.resize(shard);
+        const int64_t r = read_full(rd, user, host.data(), shard);
+        if (r < 0) return fail(FCX_ERR_ARG, "read callback failed");
+        const uint64_t got = (uint64_t)r;
+        end = got < shard;
+        if (got == 0) break;
+        const uint32_t nb = (uint32_t)((got + B - 1) / B);
+        FCX_TRY(D.stage.reserve(shard, "digest staging"));
+        FCX_TRY(D.crc.reserve(4ull * (shard / B), "digest values"));
+        FCX_HIP(hipMemcpyAsync(D.stage, host.data(), got, hipMemcpyHostToDevice, nullptr));
+        FCX_TRY(fcx::digest_run(c, D.stage, got, block_bytes, D.crc, nullptr, nullptr));
+        vals.resize(nb);
+        FCX_HIP(hipMemcpy(vals.data(), D.crc, 4ull * nb, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < nb; k++)
+            if (const int w = W.add(vals[k], std::min<uint64_t>(B, got - k * B))) return fail(w, W.err);
+    }
+    if (const int w = W.finish()) return fail(w, W.err);
+    if (stats) {
+        stats[0] = W.n;
+        stats[1] = W.blocks;
+        stats[2] = W.whole;
+    }
+    return FCX_OK;
+}
+
+int fcx_digest_host(fcx_dctx *c, const uint8_t *orig, uint64_t n, uint32_t block_bytes, uint8_t *digest, uint64_t cap,
+                    uint64_t *digest_len) {
+    if (!c || (n && !orig) || !digest_len || (cap && !digest)) return fail(FCX_ERR_ARG, "fcx_digest_host: NULL argument");
+    MemIO src{orig, n, 0, nullptr, 0, 0}, dst{nullptr, 0, 0, digest, cap, 0};
+    const int r = fcx_digest_stream(c, mem_read, &src, block_bytes, mem_write, &dst, nullptr);
+    *digest_len = dst.out_pos;
+    return r == FCX_ERR_CAPACITY ? fail(r, "fcx_digest_host: digest capacity too small") : r;
 }
 
 }  // extern "C"

@@ -371,6 +371,40 @@ def test_apply_rejects_what_does_not_fit(dctx, cuda):
 
 
 @pytest.mark.parametrize("kind", ["7", "8"])
+def test_apply_and_check_refuse_the_same_entry(dctx, cuda, kind):
+    """one entry map (k_rmap behind launch_entry_map) under fcx_repair_apply_shard and fcx_check_shard: each
+    invalid entry gets FCX_ERR_FORMAT from both, naming the same entry.  Every record decodes to its 1000 bytes,
+    and the map refuses the entries before a byte is moved."""
+    import torch
+
+    c = Case(kind, text(5, 4000), 1000)
+    assert c.sizes == [1000] * 4
+    r = Run(cuda, c)
+    good = (0, 0, 500, 500, model.FILL, 65)
+    data = bytes(16)
+    table = {   # name: (entries, the index of the first invalid one)
+        "block out of range": ([good, (4, 0, 500, 500, model.FILL, 65)], 1),
+        "blocks not ascending": ([good, (2, 0, 500, 500, model.FILL, 65), (2, 0, 500, 500, model.FILL, 65)], 2),
+        "from beyond the decoded length": ([good, (1, 0, 1001, 0, model.FILL, 0)], 1),
+        "from + len is not the block's length": ([(2, 0, 500, 499, model.FILL, 65)], 0),
+        "RAW range outside the data": ([good, (3, 8, 990, 10, model.RAW, 0)], 1),
+        "unknown kind": ([good, (1, 0, 500, 500, 2, 0)], 1),
+    }
+    d_crc = torch.zeros(4, dtype=torch.int32, device=cuda)
+    vals = (ctypes.c_uint64 * 6)()
+    for name, (ents, bad) in table.items():
+        want = f"repair: entry {bad} of the records from 0 does not fit its record"
+        rc, _, _, d_out = r.apply(dctx, ents, data, 4000)
+        assert rc == FCX_ERR_FORMAT and mc.lib().fcx_last_error().decode() == want, name
+        assert all_are(d_out, S_OUT), name
+        d_e, d_d = framed(cuda, pack(ents), FRONT, S_ENT), framed(cuda, data, 37, S_DATA)
+        rc = mc.lib().fcx_check_shard(dctx._h, kind.encode(), ctypes.c_void_p(r.d_rec.data_ptr()), len(c.recs), 4, 4000, 1000,
+                                      ctypes.c_void_p(d_e.data_ptr() + FRONT), len(ents), ctypes.c_void_p(d_d.data_ptr() + 37),
+                                      len(data), ctypes.c_void_p(d_crc.data_ptr()), None, vals, ctypes.c_void_p(r.stream))
+        assert rc == FCX_ERR_FORMAT and mc.lib().fcx_last_error().decode() == want, name
+
+
+@pytest.mark.parametrize("kind", ["7", "8"])
 def test_host_and_stream_forms(dctx, cuda, kind):
     c = Case(kind, mixed_data(), 4096)
     orig = noisy(c.data, 4096, 6, 4000, 9)
