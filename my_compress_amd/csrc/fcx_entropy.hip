@@ -481,6 +481,13 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(uint32_t nblocks, const Bl
 // staging words: the whole chunk at <= 8 bits per symbol (one pass; random data's chars
 // are exactly 8); longer codes (<= 32 bits) go through several windows of this size
 constexpr uint32_t kEncWords = kChunk / 4 + 2;
+// where the byte-substitution branch keeps staged word x: an XOR of the word's low five bits with
+// its 16-word row number.  For a fixed q the words kSymW t + q of 32 consecutive lanes t then fall
+// on 32 different banks (a dword's bank is its index mod 32), and 32 consecutive x stay at most
+// two to a bank.  A bijection inside each aligned 32 words, so inside kEncWords (the two words
+// past kChunk / 4 map to themselves).
+__device__ inline uint32_t enc_slot(uint32_t x) { return x ^ ((x >> 4) & 31u); }
+static_assert(kSymW == 16 && (kChunk / 4) % 32 == 0 && ((kChunk / 4) >> 4) % 32 == 0, "enc_slot: rows of kSymW words, identity past kChunk / 4");
 
 // k_encode's decoupled look-back: two words per chunk, cleared by k_tree.  [0] status: flag
 // (bit 62: aggregate = this chunk's bit count, bit 63: inclusive prefix = the stream's bits
@@ -567,8 +574,7 @@ __global__ __launch_bounds__(kEncT) __attribute__((amdgpu_waves_per_eu(8))) void
         const uint32_t sh0 = (uint32_t)(g0 & 31);
         const uint32_t nw = (sh0 + T + 31) >> 5;
         uint32_t *o32 = (uint32_t *)out + (g0 >> 5);
-        for (uint32_t x = tid; x < nw; x += kEncT) ws[x] = 0u;
-        uint32_t v[kSymW + 1];
+        uint32_t v[kSymW];
 #pragma unroll
         for (uint32_t q = 0; q < kSymW; q++) {
             const uint32_t w = sym[q];
@@ -576,38 +582,43 @@ __global__ __launch_bounds__(kEncT) __attribute__((amdgpu_waves_per_eu(8))) void
             if (4 * q >= n) v[q] = 0;
             else if (n - 4 * q < 4) v[q] &= (1u << (8 * (n - 4 * q))) - 1u;
         }
-        // this lane's bytes start at staging byte sh0/8 + kSymL tid: shift into kSymW + 1
-        // words, the first and last two shared with the neighbouring lanes
-        const uint32_t bo = (sh0 >> 3) + kSymL * tid, sb = 8 * (bo & 3), w0 = bo >> 2;
-        v[kSymW] = 0;
+        // this lane's bytes start at staging byte sh0/8 + kSymL tid (sh0 is a whole number of
+        // bytes): shifted by sb = sh0 bits they fill words [w0, w0 + kSymW) but for the low sb bits
+        // of word w0, which are the previous lane's top bits (a shuffle; across the two waves
+        // through red[]), and spill sb bits into word w0 + kSymW, the next lane's first.  So every
+        // staged word is one lane's plain store: nothing to zero, no atomics.  The last lane
+        // that holds symbols also stores the word after its kSymW.
+        // Staged word x lives at ws[enc_slot(x)]: a lane stride of kSymW words would put a
+        // 32-lane group's stores on two banks.
+        const uint32_t sb = sh0, w0 = kSymW * tid;
+        const uint32_t top = sb ? v[kSymW - 1] >> (32 - sb) : 0u;
+        if (lane == 63) red[wv] = top;
+        uint32_t prev = __shfl_up(top, 1);
         __syncthreads();
+        if (lane == 0) prev = wv ? red[wv - 1] : 0u;
         if (n) {
-            uint32_t prev = 0;
+            ws[enc_slot(w0)] = (v[0] << sb) | prev;
 #pragma unroll
-            for (uint32_t q = 0; q <= kSymW; q++) {
-                const uint32_t cur = v[q];
-                const uint32_t o = sb ? (cur << sb) | (prev >> (32 - sb)) : cur;
-                prev = cur;
-                if (q == 0 || q >= kSymW - 1) { if (o) atomicOr(&ws[w0 + q], o); }
-                else ws[w0 + q] = o;
-            }
+            for (uint32_t q = 1; q < kSymW; q++)
+                ws[enc_slot(w0 + q)] = sb ? (v[q] << sb) | (v[q - 1] >> (32 - sb)) : v[q];
+            if (i1 == c1) ws[enc_slot(w0 + kSymW)] = top;
         }
         __syncthreads();
         const uint32_t e = sh0 + T;   // end bit in the staging
         const uint32_t nst = lastc ? (uint32_t)(((8 * obyte + 32ull * bi.nwords[s] - 1) >> 5) - (g0 >> 5) + 1) : nw;
         const uint32_t xa = sh0 ? 1u : 0u;                                     // first whole word
         const uint32_t xz = lastc ? nst : ((e & 31) ? nw - 1 : nw);           // end of whole words
-        for (uint32_t x = xa + tid; x < xz; x += kEncT) o32[x] = x < nw ? ws[x] : 0u;
+        for (uint32_t x = xa + tid; x < xz; x += kEncT) o32[x] = x < nw ? ws[enc_slot(x)] : 0u;
         // edge words: bytes [sh0/8, 4) of word 0, bytes [0, (e & 31)/8) of word nw - 1
         uint8_t *o8 = (uint8_t *)o32;
         if (tid < 4) {
             const uint32_t q = tid;
             // word 0 shared with the previous chunk (or the record's header bytes): bytes from sh0/8
             // (a one-word chunk that is not the stream's last: only up to its end)
-            if (sh0 && q >= (sh0 >> 3) && (lastc || nw > 1 || 8 * q < e)) o8[q] = (uint8_t)(ws[0] >> (8 * q));
+            if (sh0 && q >= (sh0 >> 3) && (lastc || nw > 1 || 8 * q < e)) o8[q] = (uint8_t)(ws[enc_slot(0)] >> (8 * q));
             // the last word shared with the next chunk: bytes below the end bit
             if (!lastc && (e & 31) && !(nw == 1 && sh0) && 8 * q < (e & 31))
-                o8[4 * (nw - 1) + q] = (uint8_t)(ws[nw - 1] >> (8 * q));
+                o8[4 * (nw - 1) + q] = (uint8_t)(ws[enc_slot(nw - 1)] >> (8 * q));
         }
         return;
     }

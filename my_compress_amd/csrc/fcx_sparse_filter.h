@@ -34,7 +34,10 @@ constexpr uint32_t kSfRCap = 256;
 
 // 4 x the word index of a 24-bit key (its byte offset in the bitmap): key_mix, a bijection of
 // Z/2^24 (only the multiplier's low 24 bits reach the product's low 24), scaled to [0, kSfWords)
-// by the high half of a second 24 x 24-bit product: two full-rate multiplies and a mask
+// by the high half of a second 24 x 24-bit product: two multiplies and a mask.  (The second is a
+// full-rate v_mul_hi_u32_u24; the first comes out as a 32-bit v_mul_lo_u32, also when written as
+// __umul24: only its low 24 bits are used, so the compiler drops the key's mask and with it the
+// proof that the key fits 24 bits.  DESIGN.md §4d)
 FCX_SF_HD inline uint32_t sf_word_x4(uint32_t key) {
     const uint32_t h = ((key & 0xFFFFFFu) * 0x3779B1u) & 0xFFFFFFu;
     static_assert((kSfWords << 10) < (1u << 24), "a 24-bit scale");
