@@ -125,7 +125,7 @@ struct fcx_loop {
     uint32_t timeout_ms = 60000;
     std::mutex mu;
     std::condition_variable cv;
-    hipStream_t st = nullptr;                      // copies of matched ops, in match order
+    Stream st;                                     // copies of matched ops, in match order
     std::vector<std::deque<LoopOp *>> sendq, recvq;   // per (src * n + dst), FIFO like NCCL
     std::map<uint64_t, std::vector<LoopOp *>> coll;   // k-th collective of every rank
     std::vector<uint64_t> coll_seq;                // per rank: collectives posted
@@ -257,15 +257,15 @@ struct fcx_loop {
                 attached--;
             last = creator_gone && attached == 0;
         }
-        if (!last) return;
+        if (last) delete this;
+    }
+    ~fcx_loop() {   // the stream drained, the event pool destroyed; the stream goes with the members
         if (st) {
             (void)hipSetDevice(device);
             (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
         }
-        for (auto e : free_ev) (void)hipEventDestroy(e);
-        for (auto e : retired_ev) (void)hipEventDestroy(e);
-        delete this;
+        for (auto *pool : {&free_ev, &retired_ev})
+            for (hipEvent_t e : *pool) (void)hipEventDestroy(e);
     }
 };
 
@@ -384,37 +384,56 @@ struct LoopTransport final : Transport {
 
 }  // namespace
 
+namespace {
+
+struct LocalRank {               // what every local rank has
+    int device = -1;
+    std::unique_ptr<Transport> tr;
+    DevBuf<uint64_t> d_sizes;    // 2 x nranks u64 (size + capacity all-gather)
+};
+
+struct HostRank {                // fcx_dist_compress_host's per-device resources, kept across calls
+    std::unique_ptr<fcx_ctx, Calls<fcx_ctx_destroy>> ctx;
+    DevBuf<uint8_t> din, dout;
+    Stream st;
+    uint32_t block = 0;          // the block size they were made for
+};
+
+struct GatherState {             // fcx_dist_compress_gather's resources (process-per-GPU form)
+    Stream cst;                  // the exchange's stream (beside the caller's compress stream)
+    DevBuf<uint64_t> d_words;    // 2 u64 per (sub-batch, rank): piece length, error bits
+    PinnedBuf<uint64_t> h_words; // pinned mirror
+    DevBuf<uint64_t> d_ctl;      // [0, 1] the failure words (never written by a compress stream); [2] verdict
+    PinnedBuf<uint64_t> h_ctl;   // pinned mirror of the verdict
+    Event ev[FCX_DIST_MAX_SUB];  // per sub-batch: compressed and its length copied
+    Event copy_ev[2];            // rank 0: around the final moves of the peers' bytes
+    DevBuf<uint8_t> stage;       // rank 0: the peers' pieces as they arrive
+    DevBuf<uint8_t> drain;       // rank 0: a piece beyond its peer's bound, received and dropped
+};
+
+}  // namespace
+
 struct fcx_dist {
     int nranks = 0;                  // ranks of the job
     int base_rank = 0;               // rank of local index 0
-    std::vector<int> devices;        // per local rank
-    std::vector<std::unique_ptr<Transport>> tr;   // per local rank
-    std::vector<uint64_t *> d_sizes; // per local rank: 2 x nranks u64 (size + capacity all-gather)
-    // fcx_dist_compress_host's per-device resources, kept across calls
-    uint32_t block = 0;
-    std::vector<fcx_ctx *> ctx;
-    std::vector<uint8_t *> din, dout;
-    std::vector<hipStream_t> st;
-    std::vector<uint64_t> dincap, dcap;
-    // fcx_dist_compress_gather's resources (process-per-GPU form), made on first use and kept
-    hipStream_t cst = nullptr;       // the exchange's stream (beside the caller's compress stream)
-    uint64_t *d_words = nullptr;     // 2 u64 per (sub-batch, rank): piece length, error bits
-    uint64_t *h_words = nullptr;     // pinned mirror
-    uint64_t *d_ctl = nullptr;       // [0, 1] the failure words (never written by a compress stream); [2] verdict
-    uint64_t *h_ctl = nullptr;       // pinned mirror of the verdict
-    std::vector<hipEvent_t> ev;      // per sub-batch: compressed and its length copied
-    uint8_t *d_stage = nullptr;      // rank 0: the peers' pieces as they arrive
-    uint64_t stage_cap = 0;
-    uint8_t *d_drain = nullptr;      // rank 0: a piece beyond its peer's bound, received and dropped
-    uint64_t drain_cap = 0;
-    hipEvent_t copy_ev[2] = {nullptr, nullptr};   // rank 0: around the final moves of the peers' bytes
-    float copy_ms = -1.f;            // their duration in the last gather (-1: none timed)
+    std::vector<LocalRank> loc;      // per local rank
+    std::vector<HostRank> host;      // per local rank, made by fcx_dist_compress_host's first call
+    GatherState gs;                  // made by fcx_dist_compress_gather's first call (cst set: complete)
+    float copy_ms = -1.f;            // the final moves' duration in the last gather (-1: none timed)
     int fail_piece = -1;             // testing: a peer treats this piece as failed (fcx_dist_debug_fail)
 };
 
 namespace {
 
 constexpr uint64_t kFailed = ~0ull;   // size-exchange word of a rank whose compress failed
+
+// `body` between group_start and group_end: group_end is always called, the first error returned
+template <typename Body>
+int grouped(Transport &t, Body body) {
+    FCX_TRY(t.group_start());
+    const int rc = body(), rc2 = t.group_end();
+    return rc ? rc : rc2;
+}
 
 // sizes all-gather + segment placement for local rank li (one host thread per local rank).
 // Every rank always enters both phases, whatever happened before: `status` != FCX_OK (this
@@ -425,9 +444,9 @@ constexpr uint64_t kFailed = ~0ull;   // size-exchange word of a rank whose comp
 int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, uint8_t *d_out, uint64_t cap,
                  uint64_t *total, int mode, hipStream_t st, int status = FCX_OK) {
     const int n = d->nranks, rank = d->base_rank + li;
-    Transport &t = *d->tr[li];
-    FCX_HIP(hipSetDevice(d->devices[li]));
-    uint64_t *ds = d->d_sizes[li];
+    Transport &t = *d->loc[li].tr;
+    FCX_HIP(hipSetDevice(d->loc[li].device));
+    uint64_t *ds = d->loc[li].d_sizes;
     const bool receives = mode == FCX_DIST_ALLGATHER || rank == 0;
     const uint64_t mine[2] = {status ? kFailed : seg_len, receives ? cap : kFailed};
     FCX_HIP(hipMemcpyAsync(ds + 2 * rank, mine, sizeof(mine), hipMemcpyHostToDevice, st));
@@ -453,22 +472,21 @@ int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, ui
     const uint64_t own = sizes[rank];
     if (receives && own && d_seg != d_out + offs[rank])
         FCX_HIP(hipMemcpyAsync(d_out + offs[rank], d_seg, own, hipMemcpyDeviceToDevice, st));
-    FCX_TRY(t.group_start());
-    int rc = FCX_OK;
-    if (mode == FCX_DIST_GATHER) {
-        if (rank == 0) {
-            for (int r = 1; r < n && !rc; r++)
-                if (sizes[r]) rc = t.recv(d_out + offs[r], sizes[r], r, st);
-        } else if (own) {
-            rc = t.send(d_seg, own, 0, st);
+    FCX_TRY(grouped(t, [&] {
+        int rc = FCX_OK;
+        if (mode == FCX_DIST_GATHER) {
+            if (rank == 0) {
+                for (int r = 1; r < n && !rc; r++)
+                    if (sizes[r]) rc = t.recv(d_out + offs[r], sizes[r], r, st);
+            } else if (own) {
+                rc = t.send(d_seg, own, 0, st);
+            }
+        } else {
+            for (int r = 0; r < n && !rc; r++)
+                if (sizes[r]) rc = t.broadcast(d_out + offs[r], d_out + offs[r], sizes[r], r, st);
         }
-    } else {
-        for (int r = 0; r < n && !rc; r++)
-            if (sizes[r]) rc = t.broadcast(d_out + offs[r], d_out + offs[r], sizes[r], r, st);
-    }
-    const int rc2 = t.group_end();
-    if (rc) return rc;
-    if (rc2) return rc2;
+        return rc;
+    }));
     FCX_HIP(hipStreamSynchronize(st));
     if (own != seg_len) return fail(FCX_ERR_INTERNAL, "fcx_dist_concat: size exchange mismatch");
     return FCX_OK;
@@ -477,52 +495,22 @@ int concat_local(fcx_dist *d, int li, const uint8_t *d_seg, uint64_t seg_len, ui
 // fcx_dist_compress_gather's stream, length words, control words and events (sized for
 // FCX_DIST_MAX_SUB sub-batches of every rank), and rank 0's staging buffer of >= `stage` bytes
 int ensure_gather(fcx_dist *d, uint64_t stage) {
-    FCX_HIP(hipSetDevice(d->devices[0]));
-    const size_t words = 2ull * FCX_DIST_MAX_SUB * (size_t)d->nranks;
-    if (!d->cst) {
-        FCX_HIP(hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking));
-        FCX_HIP(hipMalloc((void **)&d->d_words, words * sizeof(uint64_t)));
-        FCX_HIP(hipHostMalloc((void **)&d->h_words, words * sizeof(uint64_t), hipHostMallocDefault));
-        FCX_HIP(hipMalloc((void **)&d->d_ctl, 4 * sizeof(uint64_t)));
-        FCX_HIP(hipHostMalloc((void **)&d->h_ctl, 4 * sizeof(uint64_t), hipHostMallocDefault));
+    FCX_HIP(hipSetDevice(d->loc[0].device));
+    if (!d->gs.cst) {   // built aside and moved in when complete: a failure leaves the handle as it was
+        const uint64_t words = 2ull * FCX_DIST_MAX_SUB * (uint64_t)d->nranks * sizeof(uint64_t);
+        GatherState g;
+        FCX_HIP(g.cst.create(hipStreamNonBlocking));
+        FCX_HIP(g.d_words.alloc(words));
+        FCX_HIP(g.h_words.alloc(words));
+        FCX_HIP(g.d_ctl.alloc(4 * sizeof(uint64_t)));
+        FCX_HIP(g.h_ctl.alloc(4 * sizeof(uint64_t)));
         const uint64_t ctl[4] = {kFailed, 1, 0, 0};
-        FCX_HIP(hipMemcpy(d->d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice));
-        d->ev.assign(FCX_DIST_MAX_SUB, nullptr);
-        for (auto &e : d->ev) FCX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : d->copy_ev) FCX_HIP(hipEventCreate(&e));
+        FCX_HIP(hipMemcpy(g.d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+        for (auto &e : g.ev) FCX_HIP(e.create(hipEventDisableTiming));
+        for (auto &e : g.copy_ev) FCX_HIP(e.create());
+        d->gs = std::move(g);
     }
-    if (stage > d->stage_cap) {
-        if (d->d_stage) FCX_HIP(hipFree(d->d_stage));
-        d->d_stage = nullptr;
-        d->stage_cap = 0;
-        if (hipMalloc((void **)&d->d_stage, stage) != hipSuccess)
-            return fail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: staging buffer of " + std::to_string(stage) + " B");
-        d->stage_cap = stage;
-    }
-    return FCX_OK;
-}
-
-void release_gather(fcx_dist *d) {
-    if (d->devices.empty()) return;
-    (void)hipSetDevice(d->devices[0]);
-    if (d->cst) (void)hipStreamSynchronize(d->cst);
-    for (auto e : d->ev)
-        if (e) (void)hipEventDestroy(e);
-    d->ev.clear();
-    for (auto &e : d->copy_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (d->cst) (void)hipStreamDestroy(d->cst);
-    if (d->d_words) (void)hipFree(d->d_words);
-    if (d->h_words) (void)hipHostFree(d->h_words);
-    if (d->d_ctl) (void)hipFree(d->d_ctl);
-    if (d->h_ctl) (void)hipHostFree(d->h_ctl);
-    if (d->d_stage) (void)hipFree(d->d_stage);
-    if (d->d_drain) (void)hipFree(d->d_drain);
-    d->cst = nullptr; d->d_words = nullptr; d->h_words = nullptr; d->d_ctl = nullptr; d->h_ctl = nullptr;
-    d->d_stage = nullptr; d->stage_cap = 0;
-    d->d_drain = nullptr; d->drain_cap = 0;
+    return stage ? d->gs.stage.reserve(stage, "fcx_dist_compress_gather: staging buffer") : FCX_OK;
 }
 
 inline uint64_t round16(uint64_t x) { return (x + 15) & ~15ull; }
@@ -547,53 +535,54 @@ uint64_t pieces_bound(uint64_t n, uint32_t block, uint32_t nsub) {
     return t;
 }
 
-void release_local(fcx_dist *d) {
-    for (size_t i = 0; i < d->ctx.size(); i++) {
-        (void)hipSetDevice(d->devices[i]);
-        if (d->st[i]) (void)hipStreamDestroy(d->st[i]);
-        if (d->din[i]) (void)hipFree(d->din[i]);
-        if (d->dout[i]) (void)hipFree(d->dout[i]);
-        fcx_ctx_destroy(d->ctx[i]);
-    }
-    d->ctx.clear(); d->din.clear(); d->dout.clear(); d->st.clear(); d->dincap.clear(); d->dcap.clear();
-    d->block = 0;
-}
-
 // (re)allocates fcx_dist_compress_host's resources when the block size changes or a call
 // needs more than the cached ones hold: `per` input bytes per device, and output for the
 // whole round (`round` input bytes) on device 0, one device's range elsewhere
 int ensure_local(fcx_dist *d, uint32_t block, uint64_t per, uint64_t round) {
-    const size_t nd = d->devices.size();
-    bool ok = d->block == block && d->ctx.size() == nd;
-    for (size_t i = 0; ok && i < nd; i++)
-        ok = d->dincap[i] >= per && d->dcap[i] >= fcx_shard_bound(i == 0 ? round : per, block);
+    const size_t nd = d->loc.size();
+    bool ok = d->host.size() == nd;
+    for (size_t i = 0; ok && i < nd; i++) {
+        const HostRank &h = d->host[i];
+        ok = h.block == block && h.din.bytes >= per && h.dout.bytes >= fcx_shard_bound(i == 0 ? round : per, block);
+    }
     if (ok) return FCX_OK;
-    release_local(d);
-    d->ctx.assign(nd, nullptr); d->din.assign(nd, nullptr); d->dout.assign(nd, nullptr);
-    d->st.assign(nd, nullptr); d->dincap.assign(nd, 0); d->dcap.assign(nd, 0);
-    d->block = block;
-    for (size_t i = 0; i < nd; i++) {   // one device at a time
+    d->host = std::vector<HostRank>(nd);   // (the old ones go before the new ones are sized)
+    for (size_t i = 0; i < nd; i++) {      // one device at a time
+        HostRank &h = d->host[i];
+        const int dev = d->loc[i].device;
+        fcx_ctx *c = nullptr;
         int r = FCX_OK;
-        if (hipSetDevice(d->devices[i]) != hipSuccess || hipStreamCreate(&d->st[i]) != hipSuccess)
+        if (hipSetDevice(dev) != hipSuccess || h.st.create() != hipSuccess)
             r = fail(FCX_ERR_HIP, "fcx_dist_compress_host: stream");
-        if (!r) r = fcx_ctx_create(&d->ctx[i], d->devices[i], block, per);
-        d->dincap[i] = per;
-        d->dcap[i] = fcx_shard_bound(i == 0 ? round : per, block);
-        if (!r && (hipMalloc((void **)&d->din[i], per) != hipSuccess ||
-                   hipMalloc((void **)&d->dout[i], d->dcap[i]) != hipSuccess))
-            r = fail(FCX_ERR_NOMEM, "fcx_dist_compress_host: device buffers");
-        if (r) { release_local(d); return r; }
+        if (!r) r = fcx_ctx_create(&c, dev, block, per);
+        h.ctx.reset(c);
+        h.block = block;
+        if (!r) r = h.din.reserve(per, "fcx_dist_compress_host: input");
+        if (!r) r = h.dout.reserve(fcx_shard_bound(i == 0 ? round : per, block), "fcx_dist_compress_host: output");
+        if (r) {
+            d->host.clear();
+            return r;
+        }
     }
     return FCX_OK;
 }
 
-int make_dist(fcx_dist **out, fcx_dist *d) {
-    d->d_sizes.resize(d->devices.size(), nullptr);
-    for (size_t i = 0; i < d->devices.size(); i++) {
-        FCX_HIP(hipSetDevice(d->devices[i]));
-        FCX_HIP(hipMalloc((void **)&d->d_sizes[i], 2 * sizeof(uint64_t) * (size_t)d->nranks));
+// the one constructor of a handle: local rank i is job rank base_rank + i on devices[i] over tr[i]
+int make_dist(fcx_dist **out, int nranks, int base_rank, const std::vector<int> &devices,
+              std::vector<std::unique_ptr<Transport>> tr) {
+    std::unique_ptr<fcx_dist, Calls<fcx_dist_destroy>> d(new fcx_dist());
+    d->nranks = nranks;
+    d->base_rank = base_rank;
+    d->loc.resize(tr.size());
+    for (size_t i = 0; i < tr.size(); i++) {
+        d->loc[i].device = devices[i];
+        d->loc[i].tr = std::move(tr[i]);
     }
-    *out = d;
+    for (LocalRank &l : d->loc) {
+        FCX_HIP(hipSetDevice(l.device));
+        FCX_HIP(l.d_sizes.alloc(2 * sizeof(uint64_t) * (size_t)nranks));
+    }
+    *out = d.release();
     return FCX_OK;
 }
 
@@ -609,7 +598,7 @@ int need_device(int device) {
 int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const uint64_t *rank_bytes,
                 uint32_t nsub, uint32_t B, uint8_t *d_out, uint64_t cap, uint64_t *total, hipStream_t st) {
     const int N = d->nranks;
-    Transport &t = *d->tr[0];
+    Transport &t = *d->loc[0].tr;
     std::vector<uint64_t> soff(N, 0), bound(N, 0);   // each peer's staging region
     uint64_t stage = 0;
     for (int r = 1; r < N; r++) {
@@ -618,7 +607,9 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
         stage += bound[r];
     }
     FCX_TRY(ensure_gather(d, stage));
-    uint64_t *dw = d->d_words, *hw = d->h_words;
+    GatherState &g = d->gs;
+    const hipStream_t cst = g.cst;
+    uint64_t *dw = g.d_words, *hw = g.h_words;
     // own range straight into d_out at offset 0 (a failure is reported after the peers' pieces
     // are drained, so no peer is left in a send), the peers' pieces into the staging regions on
     // the exchange stream meanwhile: per round s, every peer's length words, then its bytes
@@ -628,14 +619,13 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
     std::string peer_err;
     for (uint32_t s = 0; s < nsub && N > 1; s++) {
         uint64_t *ws = dw + 2ull * s * N, *hs = hw + 2ull * s * N;
-        FCX_TRY(t.group_start());
-        int rc = FCX_OK;
-        for (int r = 1; r < N && !rc; r++) rc = t.recv(ws + 2 * r, 2 * sizeof(uint64_t), r, d->cst);
-        const int rc2 = t.group_end();
-        FCX_TRY(rc);
-        FCX_TRY(rc2);
-        FCX_HIP(hipMemcpyAsync(hs, ws, 2ull * N * sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
-        FCX_HIP(hipStreamSynchronize(d->cst));
+        FCX_TRY(grouped(t, [&] {
+            int rc = FCX_OK;
+            for (int r = 1; r < N && !rc; r++) rc = t.recv(ws + 2 * r, 2 * sizeof(uint64_t), r, cst);
+            return rc;
+        }));
+        FCX_HIP(hipMemcpyAsync(hs, ws, 2ull * N * sizeof(uint64_t), hipMemcpyDeviceToHost, cst));
+        FCX_HIP(hipStreamSynchronize(cst));
         // a piece beyond its peer's staging bound (the ranks disagree on rank_bytes; a peer checks
         // its pieces against the same bound otherwise) is still received -- into the drain buffer,
         // so the peer's send completes and the protocol runs on to the failing verdict
@@ -644,35 +634,28 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
             const uint64_t len = hs[2 * r], err = hs[2 * r + 1];
             if (!err && len != kFailed && len && fill[r] + len > bound[r]) drain = std::max(drain, len);
         }
-        if (drain > d->drain_cap) {
-            if (d->d_drain) FCX_HIP(hipFree(d->d_drain));
-            d->d_drain = nullptr;
-            d->drain_cap = 0;
-            if (hipMalloc((void **)&d->d_drain, drain) != hipSuccess)
-                return fail(FCX_ERR_NOMEM, "fcx_dist_compress_gather: drain buffer of " + std::to_string(drain) + " B");
-            d->drain_cap = drain;
-        }
-        FCX_TRY(t.group_start());
-        for (int r = 1; r < N && !rc; r++) {
-            const uint64_t len = hs[2 * r], err = hs[2 * r + 1];
-            if (err || len == kFailed) {
-                if (peer_err.empty()) peer_err = "rank " + std::to_string(r) + " failed in sub-batch " + std::to_string(s);
-                continue;
+        if (drain) FCX_TRY(g.drain.reserve(drain, "fcx_dist_compress_gather: drain buffer"));
+        FCX_TRY(grouped(t, [&] {
+            int rc = FCX_OK;
+            for (int r = 1; r < N && !rc; r++) {
+                const uint64_t len = hs[2 * r], err = hs[2 * r + 1];
+                if (err || len == kFailed) {
+                    if (peer_err.empty()) peer_err = "rank " + std::to_string(r) + " failed in sub-batch " + std::to_string(s);
+                    continue;
+                }
+                if (len == 0) continue;
+                if (fill[r] + len > bound[r]) {
+                    if (peer_err.empty()) peer_err = "rank " + std::to_string(r) + " sent a piece beyond its bound";
+                    rc = t.recv(g.drain, len, r, cst);   // (concurrent drains of one round share it: dropped)
+                    continue;
+                }
+                rc = t.recv(g.stage + soff[r] + fill[r], len, r, cst);
+                fill[r] += len;
             }
-            if (len == 0) continue;
-            if (fill[r] + len > bound[r]) {
-                if (peer_err.empty()) peer_err = "rank " + std::to_string(r) + " sent a piece beyond its bound";
-                rc = t.recv(d->d_drain, len, r, d->cst);   // (concurrent drains of one round share it: dropped)
-                continue;
-            }
-            rc = t.recv(d->d_stage + soff[r] + fill[r], len, r, d->cst);
-            fill[r] += len;
-        }
-        const int rc3 = t.group_end();
-        FCX_TRY(rc);
-        FCX_TRY(rc3);
+            return rc;
+        }));
     }
-    FCX_HIP(hipStreamSynchronize(d->cst));
+    FCX_HIP(hipStreamSynchronize(cst));
     uint64_t own = 0;
     if (!own_rc) {
         own_rc = fcx_ctx_read_out_len(c, &own);
@@ -691,30 +674,29 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
         msg = "fcx_dist_compress_gather: output capacity too small (" + std::to_string(off) + " B)";
     }
     if (N > 1) {   // the job's verdict to every peer, so every rank returns the same outcome
-        d->h_ctl[2] = (uint64_t)(int64_t)verdict;
-        FCX_HIP(hipMemcpyAsync(d->d_ctl + 2, d->h_ctl + 2, sizeof(uint64_t), hipMemcpyHostToDevice, d->cst));
-        FCX_TRY(t.group_start());
-        int rc = FCX_OK;
-        for (int r = 1; r < N && !rc; r++) rc = t.send(d->d_ctl + 2, sizeof(uint64_t), r, d->cst);
-        const int rc2 = t.group_end();
-        FCX_TRY(rc);
-        FCX_TRY(rc2);
+        g.h_ctl[2] = (uint64_t)(int64_t)verdict;
+        FCX_HIP(hipMemcpyAsync(g.d_ctl + 2, g.h_ctl + 2, sizeof(uint64_t), hipMemcpyHostToDevice, cst));
+        FCX_TRY(grouped(t, [&] {
+            int rc = FCX_OK;
+            for (int r = 1; r < N && !rc; r++) rc = t.send(g.d_ctl + 2, sizeof(uint64_t), r, cst);
+            return rc;
+        }));
     }
     if (verdict) {
-        FCX_HIP(hipStreamSynchronize(d->cst));
+        FCX_HIP(hipStreamSynchronize(cst));
         FCX_HIP(hipStreamSynchronize(st));
         return fail(verdict, msg);
     }
     off = own;
-    FCX_HIP(hipEventRecord(d->copy_ev[0], st));
+    FCX_HIP(hipEventRecord(g.copy_ev[0], st));
     for (int r = 1; r < N; r++) {   // the peers' bytes behind the own segment, in rank order
-        if (fill[r]) FCX_HIP(hipMemcpyAsync(d_out + off, d->d_stage + soff[r], fill[r], hipMemcpyDeviceToDevice, st));
+        if (fill[r]) FCX_HIP(hipMemcpyAsync(d_out + off, g.stage + soff[r], fill[r], hipMemcpyDeviceToDevice, st));
         off += fill[r];
     }
-    FCX_HIP(hipEventRecord(d->copy_ev[1], st));
-    FCX_HIP(hipStreamSynchronize(d->cst));
+    FCX_HIP(hipEventRecord(g.copy_ev[1], st));
+    FCX_HIP(hipStreamSynchronize(cst));
     FCX_HIP(hipStreamSynchronize(st));
-    if (hipEventElapsedTime(&d->copy_ms, d->copy_ev[0], d->copy_ev[1]) != hipSuccess) d->copy_ms = -1.f;
+    if (hipEventElapsedTime(&d->copy_ms, g.copy_ev[0], g.copy_ev[1]) != hipSuccess) d->copy_ms = -1.f;
     *total = off;
     return FCX_OK;
 }
@@ -726,12 +708,18 @@ int gather_root(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, const 
 // compress-stream copy ever writes, so a pending copy cannot turn the announcement into a length.
 int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t nsub, uint32_t B,
                 uint8_t *d_out, uint64_t cap, uint64_t *total, hipStream_t st) {
-    Transport &t = *d->tr[0];
+    Transport &t = *d->loc[0].tr;
     FCX_TRY(ensure_gather(d, 0));
-    uint64_t *dw = d->d_words, *hw = d->h_words;
+    GatherState &g = d->gs;
+    const hipStream_t cst = g.cst;
+    uint64_t *dw = g.d_words, *hw = g.h_words;
     std::vector<uint64_t> ro(nsub, 0), pb(nsub, 0), lens(nsub, 0);
     int status = FCX_OK;
-    std::string msg;
+    std::string msg;   // this rank's own failure, kept past the calls that follow it
+    auto failed_with = [&](int code, const std::string &text) {
+        status = fail(code, text);
+        msg = text;
+    };
     uint32_t enq = 0;   // pieces enqueued before a host-side failure
     uint64_t o = 0;
     for (uint32_t s = 0; s < nsub; s++) {
@@ -739,10 +727,8 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
         piece_range(n, B, s, nsub, &lo, &hi);
         ro[s] = o;
         pb[s] = round16(fcx_shard_bound(hi - lo, B));
-        if (status == FCX_OK && o + pb[s] > cap) {
-            status = fail(FCX_ERR_CAPACITY, "fcx_dist_compress_gather: peer output capacity too small (see fcx_dist_gather_bound)");
-            msg = fcx_last_error();
-        }
+        if (status == FCX_OK && o + pb[s] > cap)
+            failed_with(FCX_ERR_CAPACITY, "fcx_dist_compress_gather: peer output capacity too small (see fcx_dist_gather_bound)");
         if (status == FCX_OK) {
             status = fcx_compress_shard(c, d_in + lo, hi - lo, d_out + o, pb[s], nullptr, st);
             if (status) msg = fcx_last_error();
@@ -750,7 +736,7 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
         if (status == FCX_OK) {
             FCX_HIP(hipMemcpyAsync(dw + 2 * s, fcx_ctx_device_out_len(c), kCwHeadBytes, hipMemcpyDeviceToDevice, st));   // [kCwTotal, kCwErr]
             FCX_HIP(hipMemcpyAsync(hw + 2 * s, dw + 2 * s, kCwHeadBytes, hipMemcpyDeviceToHost, st));
-            FCX_HIP(hipEventRecord(d->ev[s], st));
+            FCX_HIP(hipEventRecord(g.ev[s], st));
             enq = s + 1;
         }
         o += pb[s];
@@ -761,41 +747,38 @@ int gather_peer(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32
         if (!failed) {
             if (s >= enq) {
                 failed = true;
-            } else if (hipEventSynchronize(d->ev[s]) != hipSuccess) {
+            } else if (hipEventSynchronize(g.ev[s]) != hipSuccess) {
                 failed = true;
-                if (status == FCX_OK) { status = fail(FCX_ERR_HIP, "fcx_dist_compress_gather: compress failed"); msg = fcx_last_error(); }
+                if (status == FCX_OK) failed_with(FCX_ERR_HIP, "fcx_dist_compress_gather: compress failed");
             } else if (hw[2 * s + kCwErr]) {
                 failed = true;
-                status = fail(hw[2 * s + kCwErr] & kErrCapacity ? FCX_ERR_CAPACITY : FCX_ERR_INTERNAL,
-                               "fcx_dist_compress_gather: device error bits " + std::to_string(hw[2 * s + kCwErr]));
-                msg = fcx_last_error();
+                failed_with(hw[2 * s + kCwErr] & kErrCapacity ? FCX_ERR_CAPACITY : FCX_ERR_INTERNAL,
+                            "fcx_dist_compress_gather: device error bits " + std::to_string(hw[2 * s + kCwErr]));
             } else if (hw[2 * s + kCwTotal] > pb[s]) {
                 failed = true;
-                status = fail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: piece longer than its bound");
-                msg = fcx_last_error();
+                failed_with(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: piece longer than its bound");
             } else if ((int)s == d->fail_piece) {
                 failed = true;
-                status = fail(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: injected failure (fcx_dist_debug_fail)");
-                msg = fcx_last_error();
+                failed_with(FCX_ERR_INTERNAL, "fcx_dist_compress_gather: injected failure (fcx_dist_debug_fail)");
             }
         }
         if (failed) {   // this and every later round: the constant failure words
-            FCX_TRY(t.send(d->d_ctl, 2 * sizeof(uint64_t), 0, d->cst));
+            FCX_TRY(t.send(g.d_ctl, 2 * sizeof(uint64_t), 0, cst));
             continue;
         }
         lens[s] = hw[2 * s];
-        FCX_HIP(hipStreamWaitEvent(d->cst, d->ev[s], 0));
-        FCX_TRY(t.send(dw + 2 * s, 2 * sizeof(uint64_t), 0, d->cst));
-        if (lens[s]) FCX_TRY(t.send(d_out + ro[s], lens[s], 0, d->cst));
+        FCX_HIP(hipStreamWaitEvent(cst, g.ev[s], 0));
+        FCX_TRY(t.send(dw + 2 * s, 2 * sizeof(uint64_t), 0, cst));
+        if (lens[s]) FCX_TRY(t.send(d_out + ro[s], lens[s], 0, cst));
         sent += lens[s];
     }
     // the job's verdict from rank 0
-    FCX_TRY(t.recv(d->d_ctl + 2, sizeof(uint64_t), 0, d->cst));
-    FCX_HIP(hipMemcpyAsync(d->h_ctl + 2, d->d_ctl + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, d->cst));
-    FCX_HIP(hipStreamSynchronize(d->cst));
+    FCX_TRY(t.recv(g.d_ctl + 2, sizeof(uint64_t), 0, cst));
+    FCX_HIP(hipMemcpyAsync(g.h_ctl + 2, g.d_ctl + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, cst));
+    FCX_HIP(hipStreamSynchronize(cst));
     FCX_HIP(hipStreamSynchronize(st));
     if (status) return fail(status, msg);
-    const int64_t verdict = (int64_t)d->h_ctl[2];
+    const int64_t verdict = (int64_t)g.h_ctl[2];
     if (verdict)
         return fail(verdict < 0 && verdict >= FCX_ERR_RCCL ? (int)verdict : FCX_ERR_RCCL,
                      "fcx_dist_compress_gather: rank 0 reports the job failed (code " + std::to_string(verdict) + ")");
@@ -844,14 +827,14 @@ int fcx_dist_compress_gather(fcx_dist *d, fcx_ctx *c, const uint8_t *d_in, uint6
                              uint32_t nsub, uint8_t *d_out, uint64_t cap, uint64_t *total, void *stream) {
     if (!d || !c || !rank_bytes || !total || !d_out || (n && !d_in) || nsub < 1 || nsub > FCX_DIST_MAX_SUB)
         return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: bad argument");
-    if (d->tr.size() != 1)
+    if (d->loc.size() != 1)
         return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: one rank per handle (fcx_dist_init_rank / fcx_dist_init_loop)");
     const int rank = d->base_rank;
     if (rank_bytes[rank] != n) return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: rank_bytes[rank] != n");
     int dev = 0;
     uint32_t B = 0;
     FCX_TRY(fcx_ctx_info(c, &dev, &B, nullptr));
-    if (dev != d->devices[0]) return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: context on another device");
+    if (dev != d->loc[0].device) return fail(FCX_ERR_ARG, "fcx_dist_compress_gather: context on another device");
     *total = 0;
     FCX_HIP(hipSetDevice(dev));
     if (rank == 0) return gather_root(d, c, d_in, n, rank_bytes, nsub, B, d_out, cap, total, (hipStream_t)stream);
@@ -874,14 +857,9 @@ int fcx_dist_init_rank(fcx_dist **out, int nranks, int rank, const uint8_t *id, 
     memcpy(u.internal, id, FCX_DIST_ID_BYTES);
     ncclComm_t comm;
     DNCCL(ncclCommInitRank(&comm, nranks, u, rank));
-    fcx_dist *d = new fcx_dist();
-    d->nranks = nranks;
-    d->base_rank = rank;
-    d->devices = {device};
-    d->tr.emplace_back(new RcclTransport(comm));
-    const int r = make_dist(out, d);
-    if (r) fcx_dist_destroy(d);
-    return r;
+    std::vector<std::unique_ptr<Transport>> tr;
+    tr.emplace_back(new RcclTransport(comm));
+    return make_dist(out, nranks, rank, {device}, std::move(tr));
 }
 
 int fcx_dist_init_local(fcx_dist **out, int ndev, const int *devices) {
@@ -890,14 +868,9 @@ int fcx_dist_init_local(fcx_dist **out, int ndev, const int *devices) {
     for (int i = 0; i < ndev; i++) FCX_TRY(need_device(devices[i]));
     std::vector<ncclComm_t> comms(ndev);
     DNCCL(ncclCommInitAll(comms.data(), ndev, devices));
-    fcx_dist *d = new fcx_dist();
-    d->nranks = ndev;
-    d->base_rank = 0;
-    d->devices.assign(devices, devices + ndev);
-    for (auto cm : comms) d->tr.emplace_back(new RcclTransport(cm));
-    const int r = make_dist(out, d);
-    if (r) fcx_dist_destroy(d);
-    return r;
+    std::vector<std::unique_ptr<Transport>> tr;
+    for (auto cm : comms) tr.emplace_back(new RcclTransport(cm));
+    return make_dist(out, ndev, 0, std::vector<int>(devices, devices + ndev), std::move(tr));
 }
 
 int fcx_loop_create(fcx_loop **out, int nranks, int device, uint32_t timeout_ms) {
@@ -905,18 +878,15 @@ int fcx_loop_create(fcx_loop **out, int nranks, int device, uint32_t timeout_ms)
     *out = nullptr;
     FCX_TRY(need_device(device));
     FCX_HIP(hipSetDevice(device));
-    fcx_loop *h = new fcx_loop();
+    std::unique_ptr<fcx_loop> h(new fcx_loop());
     h->nranks = nranks;
     h->device = device;
     h->timeout_ms = timeout_ms ? timeout_ms : 60000;
     h->sendq.resize((size_t)nranks * nranks);
     h->recvq.resize((size_t)nranks * nranks);
     h->coll_seq.assign(nranks, 0);
-    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return fail(FCX_ERR_HIP, "fcx_loop_create: stream");
-    }
-    *out = h;
+    if (h->st.create(hipStreamNonBlocking) != hipSuccess) return fail(FCX_ERR_HIP, "fcx_loop_create: stream");
+    *out = h.release();
     return FCX_OK;
 }
 
@@ -931,14 +901,9 @@ int fcx_dist_init_loop(fcx_dist **out, fcx_loop *h, int rank) {
         std::lock_guard<std::mutex> lk(h->mu);
         h->attached++;
     }
-    fcx_dist *d = new fcx_dist();
-    d->nranks = h->nranks;
-    d->base_rank = rank;
-    d->devices = {h->device};
-    d->tr.emplace_back(new LoopTransport(h, rank));
-    const int r = make_dist(out, d);
-    if (r) fcx_dist_destroy(d);
-    return r;
+    std::vector<std::unique_ptr<Transport>> tr;
+    tr.emplace_back(new LoopTransport(h, rank));
+    return make_dist(out, h->nranks, rank, {h->device}, std::move(tr));
 }
 
 int fcx_dist_init_loop_local(fcx_dist **out, int nranks, int device, uint32_t timeout_ms) {
@@ -946,22 +911,17 @@ int fcx_dist_init_loop_local(fcx_dist **out, int nranks, int device, uint32_t ti
     *out = nullptr;
     fcx_loop *h = nullptr;
     FCX_TRY(fcx_loop_create(&h, nranks, device, timeout_ms));
-    fcx_dist *d = new fcx_dist();
-    d->nranks = nranks;
-    d->base_rank = 0;
-    d->devices.assign(nranks, device);
     {
         std::lock_guard<std::mutex> lk(h->mu);
         h->attached += nranks;
     }
-    for (int r = 0; r < nranks; r++) d->tr.emplace_back(new LoopTransport(h, r));
+    std::vector<std::unique_ptr<Transport>> tr;
+    for (int r = 0; r < nranks; r++) tr.emplace_back(new LoopTransport(h, r));
     fcx_loop_destroy(h);   // (the transports keep the hub)
-    const int r = make_dist(out, d);
-    if (r) fcx_dist_destroy(d);
-    return r;
+    return make_dist(out, nranks, 0, std::vector<int>(nranks, device), std::move(tr));
 }
 
-const char *fcx_dist_transport(fcx_dist *d) { return d && !d->tr.empty() ? d->tr[0]->name() : ""; }
+const char *fcx_dist_transport(fcx_dist *d) { return d && !d->loc.empty() ? d->loc[0].tr->name() : ""; }
 
 int fcx_dist_gather_copy_ms(fcx_dist *d, float *ms) {
     if (!d || !ms) return fail(FCX_ERR_ARG, "fcx_dist_gather_copy_ms: NULL argument");
@@ -977,32 +937,29 @@ int fcx_dist_debug_fail(fcx_dist *d, int piece) {
 
 void fcx_dist_destroy(fcx_dist *d) {
     if (!d) return;
-    release_local(d);
-    release_gather(d);
-    for (size_t i = 0; i < d->devices.size(); i++) {
-        (void)hipSetDevice(d->devices[i]);
-        if (i < d->d_sizes.size() && d->d_sizes[i]) {
-            (void)hipDeviceSynchronize();
-            (void)hipFree(d->d_sizes[i]);
-        }
+    for (size_t i = 0; i < d->loc.size(); i++) {   // per device: its work done, then what lives on it
+        (void)hipSetDevice(d->loc[i].device);
+        (void)hipDeviceSynchronize();
+        if (i < d->host.size()) d->host[i] = HostRank();
+        if (i == 0) d->gs = GatherState();
+        d->loc[i].d_sizes.release();
     }
-    d->tr.clear();
-    delete d;
+    delete d;   // (the transports last)
 }
 
 int fcx_dist_size(fcx_dist *d, int *nranks, int *nlocal) {
     if (!d) return fail(FCX_ERR_ARG, "NULL dist");
     if (nranks) *nranks = d->nranks;
-    if (nlocal) *nlocal = (int)d->tr.size();
+    if (nlocal) *nlocal = (int)d->loc.size();
     return FCX_OK;
 }
 
 int fcx_dist_concat(fcx_dist *d, int local, const uint8_t *d_seg, uint64_t seg_len, uint8_t *d_out, uint64_t cap,
                     uint64_t *total, int mode, void *stream) {
-    if (!d || !total || local < 0 || local >= (int)d->tr.size() || (seg_len && !d_seg) ||
+    if (!d || !total || local < 0 || local >= (int)d->loc.size() || (seg_len && !d_seg) ||
         (mode != FCX_DIST_GATHER && mode != FCX_DIST_ALLGATHER))
         return fail(FCX_ERR_ARG, "fcx_dist_concat: bad argument");
-    if (d->tr.size() > 1) return fail(FCX_ERR_ARG, "fcx_dist_concat: a multi-device process uses fcx_dist_compress_host");
+    if (d->loc.size() > 1) return fail(FCX_ERR_ARG, "fcx_dist_concat: a multi-device process uses fcx_dist_compress_host");
     return concat_local(d, local, d_seg, seg_len, d_out, cap, total, mode, (hipStream_t)stream);
 }
 
@@ -1010,7 +967,7 @@ int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t 
                            uint8_t *out, uint64_t cap, uint64_t *out_len) {
     if (!d || (n && !in) || !out || !out_len || block_bytes == 0 || block_bytes > FCX_MAX_BLOCK_BYTES)
         return fail(FCX_ERR_ARG, "fcx_dist_compress_host: bad argument");
-    if (d->base_rank != 0 || (int)d->tr.size() != d->nranks)
+    if (d->base_rank != 0 || (int)d->loc.size() != d->nranks)
         return fail(FCX_ERR_ARG, "fcx_dist_compress_host: needs every rank in this process (fcx_dist_init_local)");
     *out_len = 0;
     if (n == 0) return FCX_OK;
@@ -1020,32 +977,26 @@ int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t 
     const uint64_t rn0 = n < round_max ? n : round_max;
     // per device: context, input and output buffers (device 0's output receives the round),
     // kept in the fcx_dist between calls (the CLI's -g N calls once per round of input)
-    int r0 = ensure_local(d, block_bytes, per < rn0 ? per : rn0, rn0);
-    if (r0) return r0;
-    std::vector<fcx_ctx *> &ctx = d->ctx;
-    std::vector<uint8_t *> &din = d->din, &dout = d->dout;
-    std::vector<hipStream_t> &st = d->st;
-    std::vector<uint64_t> &dcap = d->dcap;
+    FCX_TRY(ensure_local(d, block_bytes, per < rn0 ? per : rn0, rn0));
+    HostRank &h0 = d->host[0];
     std::vector<int> rc(nd, FCX_OK);
     std::vector<std::string> err(nd);
     uint64_t done_in = 0, done_out = 0;
     while (done_in < n) {
         const uint64_t rn = n - done_in < round_max ? n - done_in : round_max;
-        const uint64_t nb = (rn + block_bytes - 1) / block_bytes;
         uint64_t total = 0;
         auto work = [&](int i) {
-            uint64_t b0, b1;
-            fcx_dist_block_range(nb, i, nd, &b0, &b1);
-            const uint64_t lo = b0 * block_bytes < rn ? b0 * block_bytes : rn;
-            const uint64_t hi = b1 * block_bytes < rn ? b1 * block_bytes : rn;
+            HostRank &h = d->host[i];
+            uint64_t lo, hi;
+            piece_range(rn, block_bytes, (uint32_t)i, (uint32_t)nd, &lo, &hi);
             int r = FCX_OK;
             uint64_t seg = 0, tot = 0;
-            if (hipSetDevice(d->devices[i]) != hipSuccess) r = fail(FCX_ERR_HIP, "hipSetDevice");
-            if (!r && hi > lo && hipMemcpyAsync(din[i], in + done_in + lo, hi - lo, hipMemcpyHostToDevice, st[i]) != hipSuccess)
+            if (hipSetDevice(d->loc[i].device) != hipSuccess) r = fail(FCX_ERR_HIP, "hipSetDevice");
+            if (!r && hi > lo && hipMemcpyAsync(h.din, in + done_in + lo, hi - lo, hipMemcpyHostToDevice, h.st) != hipSuccess)
                 r = fail(FCX_ERR_HIP, "fcx_dist_compress_host: H2D");
-            if (!r && hi > lo) r = fcx_compress_shard(ctx[i], din[i], hi - lo, dout[i], dcap[i], &seg, st[i]);
+            if (!r && hi > lo) r = fcx_compress_shard(h.ctx.get(), h.din, hi - lo, h.dout, h.dout.bytes, &seg, h.st);
             // every rank enters the exchange, failed or not (a failure is published there)
-            r = concat_local(d, i, dout[i], seg, dout[0], dcap[0], &tot, FCX_DIST_GATHER, st[i], r);
+            r = concat_local(d, i, h.dout, seg, h0.dout, h0.dout.bytes, &tot, FCX_DIST_GATHER, h.st, r);
             if (i == 0) total = tot;
             rc[i] = r;
             if (r) err[i] = fcx_last_error();
@@ -1055,12 +1006,10 @@ int fcx_dist_compress_host(fcx_dist *d, const uint8_t *in, uint64_t n, uint32_t 
         work(0);
         for (auto &t : th) t.join();
         for (int i = 0; i < nd; i++)
-            if (rc[i]) {
-                return fail(rc[i], "device " + std::to_string(d->devices[i]) + ": " + err[i]);
-            }
+            if (rc[i]) return fail(rc[i], "device " + std::to_string(d->loc[i].device) + ": " + err[i]);
         if (done_out + total > cap) return fail(FCX_ERR_CAPACITY, "fcx_dist_compress_host: output capacity too small");
-        (void)hipSetDevice(d->devices[0]);
-        if (hipMemcpy(out + done_out, dout[0], total, hipMemcpyDeviceToHost) != hipSuccess)
+        (void)hipSetDevice(d->loc[0].device);
+        if (hipMemcpy(out + done_out, h0.dout, total, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(FCX_ERR_HIP, "fcx_dist_compress_host: D2H");
         done_out += total;
         done_in += rn;

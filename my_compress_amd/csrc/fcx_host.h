@@ -1,5 +1,5 @@
 // fcx_host.h — the host layer the C ABI files share (no device code): the last-error helpers,
-// owned device / pinned memory, the stage-time recorder of the profiled paths and the deleter of
+// owned device / pinned memory, streams and events, the stage-time recorder of the profiled paths and the deleter of
 // per-thread and lazily made objects.  DESIGN.md, "host layer".
 #ifndef FCX_HOST_H
 #define FCX_HOST_H
@@ -75,6 +75,37 @@ struct Buf {
 };
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinnedBuf = Buf<T, true>;
+
+// ---- owned stream / event ----------------------------------------------------------------------
+// One handle each: move-only, converts to it, destroys it when it goes.  create(flags) drops what
+// it holds and returns the hipError_t, so a caller keeps its own error code and text.
+template <typename H, hipError_t (*Make)(H *, unsigned), hipError_t (*Drop)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Handle &operator=(Handle &&o) noexcept {
+        if (this != &o) {
+            release();
+            h = std::exchange(o.h, nullptr);
+        }
+        return *this;
+    }
+    ~Handle() { release(); }
+    void release() {
+        if (h) (void)Drop(h);
+        h = nullptr;
+    }
+    hipError_t create(unsigned flags = 0) {
+        release();
+        const hipError_t e = Make(&h, flags);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 
 // unique_ptr deleter that calls Fn: contexts a host thread keeps for itself
 // (thread_local std::unique_ptr<fcx_dctx, Calls<fcx_dctx_destroy>>, gone at thread exit) and parts

@@ -30,37 +30,30 @@ struct Slot {
     DevBuf<uint8_t> din, dout;
     PinnedBuf<uint64_t> hlen;   // pinned copy of the device length / error words ([kCwTotal, kCwErr])
     uint64_t n = 0;             // input bytes in this slot
-    hipEvent_t h2d = nullptr, comp = nullptr, d2h = nullptr;
+    Event h2d, comp, d2h;
 };
 
 struct Pipeline {
     Slot s[2];
-    hipStream_t sin = nullptr, scomp = nullptr, sout = nullptr;
+    Stream sin, scomp, sout;
     int device = -1;
     uint64_t in_bytes = 0, out_bytes = 0;
-    ~Pipeline() {
-        for (auto &x : s)
-            for (hipEvent_t e : {x.h2d, x.comp, x.d2h})
-                if (e) (void)hipEventDestroy(e);
-        for (hipStream_t q : {sin, scomp, sout})
-            if (q) (void)hipStreamDestroy(q);
-    }
     int init(int dev, uint64_t in_b, uint64_t out_b) {
         device = dev;
         in_bytes = in_b;
         out_bytes = out_b;
-        FCX_HIP(hipStreamCreateWithFlags(&sin, hipStreamNonBlocking));
-        FCX_HIP(hipStreamCreateWithFlags(&scomp, hipStreamNonBlocking));
-        FCX_HIP(hipStreamCreateWithFlags(&sout, hipStreamNonBlocking));
+        FCX_HIP(sin.create(hipStreamNonBlocking));
+        FCX_HIP(scomp.create(hipStreamNonBlocking));
+        FCX_HIP(sout.create(hipStreamNonBlocking));
         for (auto &x : s) {
             FCX_HIP(x.hin.alloc(in_bytes));
             FCX_HIP(x.hout.alloc(out_bytes));
             FCX_HIP(x.hlen.alloc(kCwHeadBytes));
             FCX_HIP(x.din.alloc(in_bytes));
             FCX_HIP(x.dout.alloc(out_bytes));
-            FCX_HIP(hipEventCreateWithFlags(&x.h2d, hipEventDisableTiming));
-            FCX_HIP(hipEventCreateWithFlags(&x.comp, hipEventDisableTiming));
-            FCX_HIP(hipEventCreateWithFlags(&x.d2h, hipEventDisableTiming));
+            FCX_HIP(x.h2d.create(hipEventDisableTiming));
+            FCX_HIP(x.comp.create(hipEventDisableTiming));
+            FCX_HIP(x.d2h.create(hipEventDisableTiming));
             FCX_HIP(hipEventRecord(x.comp, scomp));   // slots start free
             FCX_HIP(hipEventRecord(x.d2h, sout));
             FCX_HIP(hipEventRecord(x.h2d, sin));

@@ -57,9 +57,10 @@ class Job:
         for d in self.dists:
             d.close()
 
-    def gather(self, data: bytes, block: int, share0: int, nsub: int, caps=None, fail=None):
+    def gather(self, data: bytes, block: int, share0: int, nsub: int, caps=None, fail=None, rank_bytes=None):
         """one fcx_dist_compress_gather step over `data`; returns (results, errors, rank 0's
-        output tensor).  caps: per-rank capacity overrides; fail: {rank: piece} injected failures"""
+        output tensor).  caps: per-rank capacity overrides; fail: {rank: piece} injected failures;
+        rank_bytes: {rank: the rank_bytes list that rank passes instead of the true one}"""
         import torch
 
         n, cuda = self.n, self.cuda
@@ -78,8 +79,8 @@ class Job:
         torch.cuda.synchronize(cuda)
         try:
             res, errs = run_ranks(n, lambda r: self.dists[r].compress_gather(
-                ctxs[r], d_in.data_ptr() + ranges[r][0], rb[r], rb, nsub, outs[r].data_ptr(), cap[r],
-                self.streams[r].cuda_stream))
+                ctxs[r], d_in.data_ptr() + ranges[r][0], rb[r], (rank_bytes or {}).get(r, rb), nsub,
+                outs[r].data_ptr(), cap[r], self.streams[r].cuda_stream))
         finally:
             for c in ctxs:
                 c.close()
@@ -254,5 +255,145 @@ def test_loop_unmatched_operation_times_out(cuda):
         res, errs = run_ranks(2, lambda r: job.dists[r].concat(seg.data_ptr(), 1000, out.data_ptr(), 4096,
                                                              mc.DIST_GATHER, job.streams[r].cuda_stream), timeout=30)
         assert all(isinstance(e, mc.FcxError) for e in errs)
+    finally:
+        job.close()
+
+
+# ---- handle lifecycles, and the host path's and the gather's state across calls ----------------
+def _file(data: bytes, block: int, records: bytes) -> bytes:
+    return mc.write_header(len(data), (len(data) + block - 1) // block) + records
+
+
+def _concat_once(dists, streams, cuda):
+    """one fcx_dist_concat gather over len(dists) ranks, checked at rank 0"""
+    import torch
+
+    n = len(dists)
+    segs = [torch.full((1000 + 7 * r,), 17 + r, dtype=torch.uint8, device=cuda) for r in range(n)]
+    tot = sum(s.numel() for s in segs)
+    outs = [torch.zeros(tot + 16, dtype=torch.uint8, device=cuda) for _ in range(n)]
+    torch.cuda.synchronize(cuda)
+    res, errs = run_ranks(n, lambda r: dists[r].concat(segs[r].data_ptr(), segs[r].numel(), outs[r].data_ptr(),
+                                                     outs[r].numel(), mc.DIST_GATHER, streams[r].cuda_stream))
+    assert errs == [None] * n, errs
+    assert res == [tot] * n and torch.equal(outs[0][:tot], torch.cat(segs))
+
+
+def test_handles_destroyed_unused(cuda):
+    """every kind of handle made and destroyed with no call in between: the parts a call makes on
+    first use (the host path's, the gather's) were never made"""
+    hub = mc.Loop(2, cuda.index)
+    a, b = mc.Dist.loop(hub, 0), mc.Dist.loop(hub, 1)
+    loc = mc.Dist.loop_local(3, cuda.index)
+    one = mc.Dist.rank(1, 0, mc.dist_unique_id(), cuda.index)
+    for h in (a, b, loc, one, hub):
+        h.close()
+
+
+@pytest.mark.parametrize("hub_first", [True, False])
+@pytest.mark.parametrize("rank0_first", [True, False])
+def test_loop_close_orders(hub_first, rank0_first, cuda):
+    """the hub closed before its handles or after them, rank 0's handle before the peers' or after:
+    the last one to go frees the hub"""
+    import torch
+
+    n = 3
+    hub = mc.Loop(n, cuda.index)
+    dists = [mc.Dist.loop(hub, r) for r in range(n)]
+    if hub_first:
+        hub.close()
+    _concat_once(dists, [torch.cuda.Stream(cuda) for _ in range(n)], cuda)
+    for d in (dists if rank0_first else dists[::-1]):
+        d.close()
+    hub.close()
+
+
+@pytest.mark.parametrize("gone", [0, 1])
+def test_loop_handle_destroyed_while_sibling_times_out(gone, cuda):
+    """a handle that only ran concat, then a gather, is destroyed with its gather state; its sibling's
+    next concat finds no partner and fails after the hub's timeout, and is destroyed too"""
+    block = 4096
+    data = inputs.mosaic(51, 6 * block + 3)
+    job = Job(2, cuda, timeout_ms=1500)
+    try:
+        _concat_once(job.dists, job.streams, cuda)
+        res, errs, out0 = job.gather(data, block, 500000, 2)
+        assert errs == [None, None], errs
+        assert _file(data, block, out0[:res[0]].cpu().numpy().tobytes()) == oracle.compress_file(data, block)
+        job.dists[gone].close()
+        left = job.dists[1 - gone]
+        res, errs = run_ranks(1, lambda r: left.concat(out0.data_ptr(), 1000, out0.data_ptr(), out0.numel(),
+                                                     mc.DIST_GATHER, job.streams[0].cuda_stream), timeout=30)
+        assert isinstance(errs[0], mc.FcxError) and "waited" in str(errs[0]), errs
+    finally:
+        job.close()
+
+
+def test_loop_concat_only_handle_destroyed(cuda):
+    """handles that only ever ran concat: no gather state, no host path"""
+    job = Job(2, cuda)
+    try:
+        _concat_once(job.dists, job.streams, cuda)
+    finally:
+        job.close()
+
+
+@pytest.mark.parametrize("nsub", [1, 4])
+def test_loop_gather_state_grows_and_is_reused(nsub, cuda):
+    """one pair of handles through 3, 40 and 3 blocks: rank 0's staging buffer is made, grown, and
+    the larger one reused; each step equals the reference's file"""
+    block = 4096
+    job = Job(2, cuda)
+    try:
+        for nblocks in (3, 40, 3):
+            data = inputs.mosaic(60 + nblocks, nblocks * block - 11)
+            res, errs, out0 = job.gather(data, block, 250000, nsub)
+            assert errs == [None, None], (nblocks, errs)
+            assert _file(data, block, out0[:res[0]].cpu().numpy().tobytes()) == oracle.compress_file(data, block), nblocks
+    finally:
+        job.close()
+
+
+def test_loop_local_host_path_rebuilds(cuda):
+    """fcx_dist_compress_host on one handle: first build, another block size, back again, and a
+    larger call at the same block size (the cached buffers are short); each equals the reference's file"""
+    small = inputs.mosaic(71, 5 * 4096 + 7)
+    d = mc.Dist.loop_local(2, cuda.index)
+    try:
+        for data, block, round_bytes in [
+            (small, 4096, 2 * 4096),
+            (inputs.mosaic(72, 3 * 65536 + 1), 65536, 0),
+            (small, 4096, 2 * 4096),
+            (inputs.mosaic(73, 64 * 4096), 4096, 0),
+        ]:
+            got = d.compress_host(data, block, round_bytes=round_bytes)
+            assert _file(data, block, got) == oracle.compress_file(data, block), (len(data), block, round_bytes)
+    finally:
+        d.close()
+
+
+def test_loop_gather_drains_a_piece_beyond_its_bound(cuda):
+    """rank 0 is told that rank 1 holds one block while rank 1 sends eight: rank 1's pieces lie
+    beyond the staging bound rank 0 computed for it, are received into the drain buffer and dropped,
+    and every rank fails with no hang; again (the drain buffer is reused), then a correct step"""
+    n, block, nsub = 3, 4096, 2
+    data = inputs.generate("rand", 9, 24 * block)
+    ranges = [fdist.byte_range(len(data), block, r, n, 0) for r in range(n)]
+    rb = [b - a for a, b in ranges]
+    assert rb == [8 * block] * 3
+    told = [rb[0], block, rb[2]]   # rank 0's view; its own entry is true, so the argument check passes
+    bound = sum((mc.shard_bound(hi - lo, block) + 15) & ~15 for lo, hi in fdist.piece_ranges(told[1], block, nsub))
+    lo, hi = fdist.piece_ranges(rb[1], block, nsub)[0]
+    first = data[ranges[1][0] + lo:ranges[1][0] + hi]
+    assert len(first) == 4 * block and len(oracle.compress_file(first, block)) - 10 > bound   # it reaches the drain
+    job = Job(n, cuda)
+    try:
+        for _ in range(2):
+            res, errs, _ = job.gather(data, block, 0, nsub, rank_bytes={0: told})
+            assert all(isinstance(e, mc.FcxError) for e in errs), errs
+            assert "beyond its bound" in str(errs[0]), errs[0]
+        res, errs, out0 = job.gather(data, block, 0, nsub)
+        assert errs == [None] * n, errs
+        assert _file(data, block, out0[:res[0]].cpu().numpy().tobytes()) == oracle.compress_file(data, block)
     finally:
         job.close()
