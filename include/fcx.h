@@ -570,6 +570,50 @@ int fcx_digest_host(fcx_dctx *ctx, const uint8_t *orig, uint64_t n, uint32_t blo
 int fcx_check_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *repair, uint64_t repair_len,
                    const uint8_t *digest, uint64_t digest_len, fcx_verify_fn on_block, void *user_cb, uint64_t *stats);
 
+/* ---- search: where does a byte string occur in the decoded run? (FCX7 and FCX8) ----------------
+ * The decoded run is what fcx_decompress_shard / fcx_lz78_decompress_shard write for the records, quirks
+ * included: the bytes and the coordinates of the index and the range calls above.  A hit is an offset p
+ * with decoded[p, p + plen) == pattern; overlapping occurrences all count; record and block boundaries do
+ * not exist for the search, so a match may lie across any number of records.  Hits come in ascending
+ * order.  The decoded bytes stay on the device: only the pattern goes to it and the hit offsets come
+ * back.  A repair sidecar is not applied: the search is over the bytes the records decode to. */
+#define FCX_FIND_MAX_PATTERN 256u
+#define FCX_FIND_STATS 6
+/* Searches the nblocks records (no file header) of rec_len device bytes at d_rec for the plen bytes at
+ * pattern (host, 1 <= plen <= FCX_FIND_MAX_PATTERN).  *nhits is always the number of hits in the run;
+ * d_hits[0, min(cap, *nhits)) (device) receives the first of them, ascending, and nothing else is
+ * written; d_hits == NULL with cap == 0 is the count alone.  FCX_OK whether or not cap was reached.
+ * nblocks == 0 gives *nhits = 0 and touches no device memory.  The run is indexed, then decoded in
+ * fcx_verify_shard's groups into the context's bounded buffer (fcx_dctx_set_verify_group applies; the
+ * result does not depend on it) and each group is scanned together with the last plen - 1 bytes before
+ * it.  Synchronises `stream`.  FCX_ERR_ARG, before the device is touched, for a NULL ctx, pattern or
+ * nhits, a NULL d_rec with nblocks > 0, a NULL d_hits with cap > 0, a kind other than '7' or '8', plen
+ * outside [1, FCX_FIND_MAX_PATTERN]; FCX_ERR_FORMAT exactly where the index and the full decoders give
+ * it.  Stage table with profiling: index, decode, scan, summary. */
+int fcx_find_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                   const uint8_t *pattern /* host */, uint32_t plen,
+                   uint64_t *d_hits, uint64_t cap, uint64_t *nhits, void *stream);
+typedef void (*fcx_hit_fn)(void *user, uint64_t offset);
+/* fcx_decompress_stream's twin: reads the header, then the records in that function's groups, and
+ * searches them as one run: a match that lies across two groups is found like any other.  on_hit (may
+ * be NULL) is called for every hit of the file, in order, with file-wide offsets.  stats (4 values, may
+ * be NULL): hits, decoded bytes, records, positions judged, summed over the file. */
+int fcx_find_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in,
+                    const uint8_t *pattern, uint32_t plen, fcx_hit_fn on_hit, void *user_cb, uint64_t *stats);
+/* a whole file (header + records) in host memory, through fcx_find_stream: *nhits the hits of the file,
+ * hits[0, min(cap, *nhits)) (host, NULL with cap == 0: the count alone) the first of them */
+int fcx_find_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint8_t *pattern, uint32_t plen,
+                  uint64_t *hits, uint64_t cap, uint64_t *nhits);
+/* Counters of the last fcx_find_shard call on the context (the stream and host forms: of their last
+ * group), min(n, FCX_FIND_STATS) values: start positions judged, positions that passed the prefix filter
+ * (the first min(plen, 4) bytes), hits, groups decoded, carry bytes kept across group ends, write
+ * windows run.  After a whole run positions judged = max(decoded bytes - plen + 1, 0): no position is
+ * judged twice or skipped. */
+int fcx_dctx_find_stats(fcx_dctx *ctx, uint64_t *out, int n);
+/* Testing: hits per window of the stream form's hit buffer in later calls (0 = the default, 1 Mi); a
+ * group with more hits is delivered in several windows.  The results do not depend on it. */
+int fcx_dctx_set_find_window(fcx_dctx *ctx, uint32_t hits);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

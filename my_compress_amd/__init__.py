@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -173,6 +173,14 @@ def lib():
         L.fcx_digest_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint32, c_u8p, ctypes.c_uint64, P64]
         L.fcx_check_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64,
                                      VERIFY_FN, ctypes.c_void_p, P64]
+    if hasattr(L, "fcx_find_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        L.fcx_find_shard.argtypes = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                     c_u8p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, P64, ctypes.c_void_p]
+        L.fcx_find_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, c_u8p, ctypes.c_uint32,
+                                      HIT_FN, ctypes.c_void_p, P64]
+        L.fcx_find_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint32, P64, ctypes.c_uint64, P64]
+        L.fcx_dctx_find_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+        L.fcx_dctx_set_find_window.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -214,6 +222,9 @@ WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes
 # fcx_verify_fn: block, its length in the original, its decoded bytes, the first difference
 VERIFY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32)
 VERIFY_SAME = 0xFFFFFFFF   # FCX_VERIFY_SAME
+# fcx_hit_fn: the decoded offset of a hit
+HIT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64)
+FIND_MAX_PATTERN = 256     # FCX_FIND_MAX_PATTERN
 
 
 # the repair sidecar (include/fcx.h): one 32-byte entry layout on the device, in the FCXR file and here
@@ -743,6 +754,43 @@ class DContext:
                                     len(digest), cb, None, vals), "fcx_check_host")
         return self._verify_stats(vals), bad
 
+    # ---- search (fcx_find_*): where a byte string occurs in the decoded run ----
+    FIND_STATS = ("judged", "candidates", "hits", "groups", "carry_bytes", "windows")
+
+    def find_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, pattern: bytes, d_hits: int = 0, cap: int = 0,
+                   stream: int = 0) -> int:
+        """searches device records (no header) for `pattern` (1 to 256 bytes); returns the number of hits in
+        the run; the first min(cap, hits) offsets go to d_hits (u64 on the device), ascending"""
+        n = ctypes.c_uint64(0)
+        _check(lib().fcx_find_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, pattern, len(pattern),
+                                    ctypes.c_void_p(d_hits or None), cap, ctypes.byref(n), ctypes.c_void_p(stream)),
+               "fcx_find_shard")
+        return int(n.value)
+
+    def find(self, blob: bytes, pattern: bytes, max_hits: int = None):
+        """a whole FCX7 or FCX8 file in memory -> (count, [offsets]): every offset of the decoded file at which
+        `pattern` occurs, ascending, the first max_hits of them when that is given (0: the count alone)"""
+        n = ctypes.c_uint64(0)
+        if not max_hits:   # the count: all there is to do, or what sizes the room for all
+            _check(lib().fcx_find_host(self._h, blob, len(blob), pattern, len(pattern), None, 0, ctypes.byref(n)), "fcx_find_host")
+            if max_hits == 0 or n.value == 0:
+                return int(n.value), []
+            max_hits = int(n.value)
+        out = (ctypes.c_uint64 * max_hits)()
+        _check(lib().fcx_find_host(self._h, blob, len(blob), pattern, len(pattern), out, max_hits, ctypes.byref(n)), "fcx_find_host")
+        return int(n.value), [int(v) for v in out[:min(max_hits, int(n.value))]]
+
+    def find_stats(self) -> dict:
+        """counters of the last find call (fcx_dctx_find_stats)"""
+        n = len(self.FIND_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_find_stats(self._h, vals, n), "fcx_dctx_find_stats")
+        return dict(zip(self.FIND_STATS, [int(v) for v in vals]))
+
+    def set_find_window(self, hits: int):
+        """testing: hits per window of the stream form's hit buffer in later calls (0: the default)"""
+        _check(lib().fcx_dctx_set_find_window(self._h, hits), "fcx_dctx_set_find_window")
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -849,6 +897,16 @@ def check(blob: bytes, digest: bytes, repair: bytes = None, device: int = 0):
     ctx = DContext(device)
     try:
         return ctx.check_host(blob, digest, repair)
+    finally:
+        ctx.close()
+
+
+def find(blob: bytes, pattern: bytes, max_hits: int = None, device: int = 0):
+    """where `pattern` (1 to 256 bytes) occurs in what the FCX7 or FCX8 file `blob` decodes to: (count,
+    [offsets]) as DContext.find; the file is decoded and searched on the GPU, only the offsets come back"""
+    ctx = DContext(device)
+    try:
+        return ctx.find(blob, pattern, max_hits)
     finally:
         ctx.close()
 

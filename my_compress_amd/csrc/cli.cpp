@@ -43,6 +43,13 @@
 //                   Not with -c, --compare, --range or --list; --digest not with --range or --list.
 // One line per failing block, then the verdict; exit status 0 for OK, 1 for FAIL.  Without a HIP device the
 // FCX7 directions run on the host decoder and the host CRC-32, with the same file bytes and lines; FCX8 fails.
+// Search, decompress mode only (fcx_find_stream: the decoded bytes stay on the device, the hit offsets come back):
+//   --find STRING     the argument's bytes (1 to 256), anywhere in the decoded file, across record boundaries too
+//   --find-hex HEX    the same for any bytes: an even number of hex digits
+//   --count           with either: only the totals
+// One line "find: offset N" per hit, then "find: H hits, decoded bytes = D"; no -o file; exit status 0 when the
+// search ran.  Not with -c, --range, --list, --compare, --verify, --repair, --digest, --test, or both together.
+// Without a HIP device an FCX7 file is searched on the host decoder, with the same lines; FCX8 fails.
 #include <getopt.h>
 
 #include <chrono>
@@ -64,7 +71,8 @@ static int usage() {
             "[-g (or --gpus) <count>] [--verify (with -c)] [--range <offset>:<length> | --list | --compare <original> "
             "(decompress only)] [--repair <sidecar file> (written with -c or --compare, read by a decompress)] "
             "[--digest <digest file> (written with -c or --compare, checked by a decompress)] "
-            "[--test (decompress with --digest: check only, no output file)]\n");
+            "[--test (decompress with --digest: check only, no output file)] "
+            "[--find <string> | --find-hex <hex digits> [--count] (decompress only: search the decoded bytes)]\n");
     return -1;
 }
 
@@ -471,6 +479,44 @@ static int do_check(FILE *fcomp, FILE *frep, const char *digest_path, int device
     return r;
 }
 
+// --find / --find-hex: the pattern's offsets in the decoded file, by fcx_find_stream on the device, or for
+// an FCX7 file without one by the host decoder
+static int do_find(FILE *fin, int device, const std::vector<uint8_t> &pat, bool count_only) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_find(fin, nblocks, pat.data(), (uint32_t)pat.size(), count_only, nullptr);
+    }
+    uint64_t max_in = 0, stats[4] = {};
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    const fcx_hit_fn line = [](void *, uint64_t off) { fcx_cli::find_line(off); };
+    const int r = fcx_find_stream(d, file_read, fin, max_in, pat.data(), (uint32_t)pat.size(), count_only ? nullptr : line, nullptr,
+                                  stats);
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::find_totals(stats[0], stats[1]);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -551,6 +597,9 @@ int main(int argc, char **argv) {
                                            {"repair", required_argument, nullptr, 'P'},
                                            {"digest", required_argument, nullptr, 'D'},
                                            {"test", no_argument, nullptr, 'T'},
+                                           {"find", required_argument, nullptr, 'F'},
+                                           {"find-hex", required_argument, nullptr, 'X'},
+                                           {"count", no_argument, nullptr, 'N'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -559,6 +608,9 @@ int main(int argc, char **argv) {
     bool dist = false;   // -g given: the RCCL multi-GPU path (also at -g 1)
     bool verify = false, compare = false, test = false;
     std::string original, repair, digest;
+    std::vector<uint8_t> pattern;
+    int finds = 0;   // --find and --find-hex options seen
+    bool count_only = false;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -582,6 +634,16 @@ int main(int argc, char **argv) {
         case 'P': repair = optarg; break;
         case 'D': digest = optarg; break;
         case 'T': test = true; break;
+        case 'F':
+            pattern.assign(optarg, optarg + strlen(optarg));
+            if (pattern.empty() || pattern.size() > FCX_FIND_MAX_PATTERN) return usage();
+            finds++;
+            break;
+        case 'X':
+            if (!fcx_cli::parse_hex(optarg, &pattern)) return usage();
+            finds++;
+            break;
+        case 'N': count_only = true; break;
         default: return usage();
         }
     }
@@ -591,19 +653,26 @@ int main(int argc, char **argv) {
     if (!repair.empty() && (want.range || want.list)) return usage();
     if (!digest.empty() && (want.range || want.list)) return usage();
     if (test && (digest.empty() || compress || compare || want.range || want.list)) return usage();
+    if (finds > 1 || (count_only && !finds)) return usage();
+    if (finds && (compress || want.range || want.list || compare || verify || test || !repair.empty() || !digest.empty())) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    const bool no_out = want.list || compare || test;   // (--list, --compare and --test write no file)
+    const bool no_out = want.list || compare || test || finds;   // (--list, --compare, --test and --find write no file)
     FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
     if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
     if (compress && !lz77 && hipSetDevice(device) != hipSuccess) {
         fprintf(stderr, "fcx: no HIP device %d\n", device);
         return -1;
+    }
+    if (finds) {
+        const int r = do_find(fin, device, pattern, count_only);
+        fclose(fin);
+        return r;
     }
     if (compare) {
         int r = do_compare(fin, original.c_str(), device, block);

@@ -1,7 +1,8 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
-// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair and --digest.  Host code
+// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest and --find.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
-// (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp).
+// (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
+// tools/find_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -384,6 +385,56 @@ inline int host_check(FILE *fin, FILE *frep, FILE *fdig, uint16_t nblocks, uint6
     }
     if (stats) memcpy(stats, s, sizeof(s));
     return check_totals(s[1], s[0], s[4]);
+}
+
+// ---- --find / --find-hex: the printout, the same on the GPU and on the host ----
+inline void find_line(uint64_t off) { printf("find: offset %llu\n", (unsigned long long)off); }
+inline int find_totals(uint64_t hits, uint64_t decoded) {
+    printf("find: %llu hits, decoded bytes = %llu\n", (unsigned long long)hits, (unsigned long long)decoded);
+    return 0;
+}
+// an even number of hex digits, 1 to FCX_FIND_MAX_PATTERN bytes of them; false for anything else
+inline bool parse_hex(const char *s, std::vector<uint8_t> *out) {
+    out->clear();
+    auto nib = [](char ch) { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1; };
+    for (; s[0]; s += 2) {
+        const int hi = nib(s[0]), lo = s[1] ? nib(s[1]) : -1;
+        if (hi < 0 || lo < 0) return false;
+        out->push_back((uint8_t)(16 * hi + lo));
+    }
+    return !out->empty() && out->size() <= FCX_FIND_MAX_PATTERN;
+}
+
+// --find without a device: every FCX7 record through the host decoder, searched behind a rolling tail of
+// the last m - 1 decoded bytes, so a match may lie across any number of records; one line per hit unless
+// count_only, then the totals.  stats (2 values, may be null): hits, decoded bytes.
+inline int host_find(FILE *fin, uint16_t nblocks, const uint8_t *pat, uint32_t m, bool count_only, uint64_t *stats) {
+    std::vector<uint8_t> win;   // [tail | record]
+    uint64_t pos = 0, hits = 0, tail = 0;   // decoded bytes before the record, hits, bytes of win kept from before
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        win.resize(tail);
+        win.insert(win.end(), plain, plain + n);
+        const uint64_t len = win.size(), first = pos - tail;   // win[0] is decoded byte `first`
+        for (uint64_t p = 0; p + m <= len; p++) {
+            const uint8_t *at = (const uint8_t *)memchr(win.data() + p, pat[0], (size_t)(len - m + 1 - p));
+            if (!at) break;
+            p = (uint64_t)(at - win.data());
+            if (memcmp(at, pat, m) == 0) {
+                if (!count_only) find_line(first + p);
+                hits++;
+            }
+        }
+        pos += n;
+        tail = len < m - 1 ? len : m - 1;
+        win.erase(win.begin(), win.end() - (ptrdiff_t)tail);
+        return true;
+    });
+    if (r) return r;
+    if (stats) {
+        stats[0] = hits;
+        stats[1] = pos;
+    }
+    return find_totals(hits, pos);
 }
 
 }  // namespace fcx_cli

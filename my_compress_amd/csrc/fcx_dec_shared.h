@@ -445,13 +445,14 @@ int run_index(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, ui
 // the end of the record group that starts at g0: the bound of fcx_dctx_set_verify_group over doff
 uint32_t verify_group_end(const VerifyScratch &V, const uint64_t *doff, uint32_t nblocks, uint32_t g0);
 // the run's groups in order, vf.groups set and vf.buf reserved for the largest of them that `staged`
-// (records [g0, g1); none given: every group) says goes through the buffer
+// (records [g0, g1); none given: every group) says goes through the buffer, with `headroom` bytes
+// more for a caller that decodes behind the buffer's start (find_run's carry)
 struct RunGroup {
     uint32_t g0, g1;
     uint64_t gbytes;   // decoded bytes of its records
 };
 int run_groups(fcx_dctx *c, const RunIndex &ix, uint32_t nblocks, std::vector<RunGroup> *groups,
-               const std::function<bool(uint32_t, uint32_t)> &staged = nullptr);
+               const std::function<bool(uint32_t, uint32_t)> &staged = nullptr, uint64_t headroom = 0);
 // records [g0, g0 + nrec) of the run through their codec's decoder to dst, which must give `want` bytes;
 // `who` names the entry point in the message, FCX8 messages number the records from rec_base
 int decode_group(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, const std::vector<uint64_t> &roff, uint32_t g0,
@@ -525,6 +526,45 @@ struct DigestScratch {
     uint64_t stats[FCX_DIGEST_STATS] = {};
 };
 
+// ---- status words of a search (fcx_dctx's fd.words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kFwJudged = 0;      // start positions judged (k_fscan)
+constexpr uint32_t kFwCand = 1;        // of those, the ones that passed the prefix filter (k_fscan)
+constexpr uint32_t kFwHits = 2;        // hits of the call so far: advanced by k_fbase, group by group
+constexpr uint32_t kFwGroupBase = 3;   // hits of the call before the group scanned last (k_fbase)
+constexpr uint32_t kFwWords = 8;
+constexpr uint32_t kFCarry = FCX_FIND_MAX_PATTERN;   // bytes in front of a decoded group: room for the carry
+
+// where a search leaves its hits: the first `cap` of the call at d_hits (device, the shard form), and / or
+// every hit through on_hit in order (the stream form, by windows of fd.window hits through fd.hits)
+struct FindSink {
+    uint64_t *d_hits = nullptr;
+    uint64_t cap = 0;
+    fcx_hit_fn on_hit = nullptr;
+    void *user = nullptr;
+};
+// fcx_find_shard behind its argument checks (fcx_find.hip), for the stream path's groups of a longer file:
+// `base` is the decoded offset of the run's first byte in the file, and the search continues from the
+// carry the context holds (fd.carry_len bytes: 0 starts a new search); messages number the records from
+// rec_base.  *nhits: the run's hits, *decoded: its decoded bytes.
+int find_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint8_t *pattern,
+             uint32_t plen, uint64_t base, const FindSink &sink, uint64_t *nhits, uint64_t *decoded, hipStream_t st,
+             uint64_t rec_base);
+
+// scratch of the search (fcx_find.hip)
+struct FindScratch {
+    DevBuf<uint32_t> pat;            // the pattern, zero-padded to kFCarry bytes
+    DevBuf<uint8_t> carry;           // kFCarry bytes: the last carry_len decoded bytes seen, right-aligned
+    DevBuf<uint16_t> bitmap;         // per tile of 4096 start positions 512 B of hit bits
+    DevBuf<uint32_t> tile_count;     // per tile its hits, and ...
+    DevBuf<uint32_t> tile_base;      // ... the hits of the group's tiles before it
+    DevBuf<uint64_t> hits;           // the stream form's window
+    DevBuf<uint64_t> words;          // kFw*
+    PinnedBuf<uint64_t> host_words;
+    uint32_t carry_len = 0;
+    uint32_t window = 0;             // fcx_dctx_set_find_window (0: 1 Mi hits)
+    uint64_t stats[FCX_FIND_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -556,6 +596,7 @@ struct fcx_dctx {
     fcx::VerifyScratch vf;
     fcx::RepairScratch rp;
     fcx::DigestScratch dg;
+    fcx::FindScratch fd;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

@@ -1,7 +1,7 @@
 // fcx_run.hip — the run core: the host half of every call over a device-resident run of
 // FCX7 / FCX8 records that is indexed, decoded group by group into the verification's bounded buffer and
 // judged block by block: verify_run (fcx_verify.hip), repair_apply_run (fcx_repair.hip) and check_run
-// (fcx_digest.hip).  Host code only; the stage times of such a call: RunTimes (fcx_dec_shared.h).
+// (fcx_digest.hip); or searched across the blocks: find_run (fcx_find.hip).  Host code only; the stage times of such a call: RunTimes (fcx_dec_shared.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,7 +56,7 @@ int run_index(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, ui
 }
 
 int run_groups(fcx_dctx *c, const RunIndex &ix, uint32_t nblocks, std::vector<RunGroup> *groups,
-               const std::function<bool(uint32_t, uint32_t)> &staged) {
+               const std::function<bool(uint32_t, uint32_t)> &staged, uint64_t headroom) {
     VerifyScratch &V = c->vf;
     const uint64_t *doff = ix.doff.data();
     uint64_t need = 0;
@@ -68,7 +68,7 @@ int run_groups(fcx_dctx *c, const RunIndex &ix, uint32_t nblocks, std::vector<Ru
         g0 = g1;
     }
     V.groups = (uint32_t)groups->size();
-    return V.buf.reserve(need + 64, "verify buffer");
+    return V.buf.reserve(need + headroom + 64, "verify buffer");
 }
 
 int decode_group(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, const std::vector<uint64_t> &roff, uint32_t g0,

@@ -737,6 +737,54 @@ int fcx_check_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uin
                             on_block, user_cb, stats);
 }
 
+// ---- the search's stream and host forms (include/fcx.h) ------------------------------
+
+int fcx_find_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, const uint8_t *pattern, uint32_t plen,
+                    fcx_hit_fn on_hit, void *user_cb, uint64_t *stats) {
+    if (!dctx || !rd || !pattern) return fail(FCX_ERR_ARG, "fcx_find_stream: NULL argument");
+    if (plen < 1 || plen > FCX_FIND_MAX_PATTERN)
+        return fail(FCX_ERR_ARG, "fcx_find_stream: pattern length outside [1, FCX_FIND_MAX_PATTERN]");
+    uint64_t sum[4] = {0, 0, 0, 0};
+    FindSink sink;
+    sink.on_hit = on_hit;
+    sink.user = user_cb;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        if (before == 0) dctx->fd.carry_len = 0;   // a new search; later groups go on from the carry
+        uint64_t hits = 0, dec = 0;
+        FCX_TRY(fcx::find_run(dctx, lz78 ? '8' : '7', x.din, used, nb, pattern, plen, sum[1], sink, &hits, &dec, st, before));
+        sum[0] += hits;
+        sum[1] += dec;
+        sum[2] += nb;
+        sum[3] += dctx->fd.stats[0];
+        return FCX_OK;
+    });
+    if (r) return r;
+    for (int i = 0; i < 4 && stats; i++) stats[i] = sum[i];
+    return FCX_OK;
+}
+
+int fcx_find_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint8_t *pattern, uint32_t plen, uint64_t *hits,
+                  uint64_t cap, uint64_t *nhits) {
+    if (!dctx || !in || !pattern || !nhits || (cap && !hits)) return fail(FCX_ERR_ARG, "fcx_find_host: NULL argument");
+    if (plen < 1 || plen > FCX_FIND_MAX_PATTERN)
+        return fail(FCX_ERR_ARG, "fcx_find_host: pattern length outside [1, FCX_FIND_MAX_PATTERN]");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    struct Take {
+        uint64_t *hits, cap, n;
+    } take{hits, cap, 0};
+    MemIO comp{in, in_len, 0, nullptr, 0, 0};
+    uint64_t stats[4] = {};
+    const fcx_hit_fn keep = [](void *u, uint64_t off) {
+        Take *k = (Take *)u;
+        if (k->n < k->cap) k->hits[k->n] = off;
+        k->n++;
+    };
+    FCX_TRY(fcx_find_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, pattern, plen, cap ? keep : nullptr, &take, stats));
+    *nhits = stats[0];
+    return FCX_OK;
+}
+
 int fcx_digest_stream(fcx_dctx *c, fcx_read_fn rd, void *user, uint32_t block_bytes, fcx_write_fn wr, void *user_wr,
                       uint64_t *stats) {
     if (!c || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_digest_stream: NULL argument");
