@@ -614,6 +614,85 @@ int fcx_dctx_find_stats(fcx_dctx *ctx, uint64_t *out, int n);
  * group with more hits is delivered in several windows.  The results do not depend on it. */
 int fcx_dctx_set_find_window(fcx_dctx *ctx, uint32_t hits);
 
+/* ---- lines: count, locate, decode and number the lines of the decoded run (FCX7 and FCX8) --------
+ * D is the decoded run: what fcx_decompress_shard / fcx_lz78_decompress_shard write for the records,
+ * quirks included; the bytes and coordinates of the index, the range and the search calls.  It has T
+ * bytes.  A repair sidecar is not applied.  The delimiter d is one byte value chosen by the caller, any
+ * of the 256 (the tools default to 0x0A).
+ *   nl(x), 0 <= x <= T: the number of i < x with D[i] == d.
+ *   Line j (0-based here and in Python) starts at s_j: s_0 = 0, s_j = 1 + the position of the j-th
+ *   delimiter for 1 <= j <= nl(T).
+ *   The number of lines is L = nl(T) + (T > 0 && D[T-1] != d): an unterminated tail is a line, T == 0 has none.
+ *   Line j < L is D[s_j, e_j) with e_j = s_{j+1} when j < nl(T), else T: the delimiter belongs to the line it ends.
+ *   The line of an offset x <= T is nl(x).
+ * Record and block boundaries do not exist for lines.  The decoded bytes stay on the device.
+ * Argument checks come before the device is touched and give FCX_ERR_ARG: a NULL ctx, a NULL output or
+ * count pointer, a NULL d_rec with nblocks > 0, a kind other than '7' or '8', a partial set of index
+ * pointers.  FCX_ERR_FORMAT exactly where the index and the full decoders give it.  The shard calls run
+ * in fcx_verify_shard's groups through the context's bounded buffer (fcx_dctx_set_verify_group applies;
+ * the results do not depend on it) and synchronise `stream`.  Stage table with profiling: index, decode,
+ * count, summary. */
+#define FCX_LINES_STATS 4
+#define FCX_LINES_CALL_STATS 5
+/* The line column of the index: d_line_off[k] = nl(dec_off[k]), the delimiters in the decoded bytes before
+ * record k, d_line_off[nblocks] = nl(T); nblocks + 1 u64 on the device beside fcx_index_shard's rec_off /
+ * dec_off, or NULL for the counts alone.  stats (host, FCX_LINES_STATS values): nl(T), L, T, the bytes
+ * behind the last delimiter.  nblocks == 0 gives zeros and touches no device memory.  Nothing but
+ * d_line_off is written. */
+int fcx_lines_index_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                          uint64_t *d_line_off, uint64_t *stats, void *stream);
+/* The byte range of lines [first, first + count): *off = s_first, *len reaches to e of the last line
+ * taken.  first + count saturates, so count = UINT64_MAX means "to the end"; first >= L gives *off = T,
+ * *len = 0, not an error.  Pass all three index arrays (fcx_index_shard's and fcx_lines_index_shard's
+ * for the same delimiter) or none of them.  With none the call indexes the run, counts group by group and
+ * decodes no group behind the one that holds the second boundary.  With an index its arrays are copied
+ * to the host (24 bytes per record), the records that hold the two boundary delimiters are found by
+ * bisection on line_off, and only those, two at most, are decoded and scanned.  A given index is trusted
+ * for where things are, not for safety (the rule of fcx_decompress_range_shard): FCX_ERR_FORMAT when it
+ * does not ascend, when a touched record does not decode to dec_off[k+1] - dec_off[k] bytes or does not
+ * hold the delimiters line_off promises, or when the arrays do not start at 0; never an access outside d_rec[0, rec_len), the arrays or the
+ * context's buffer.  A damaged record the call does not touch does not fail it.  The call with an index
+ * publishes no stage table (it has no index or group stage): fcx_dctx_stage_count is 0 after it. */
+int fcx_lines_locate_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                           const uint64_t *d_rec_off, const uint64_t *d_dec_off, const uint64_t *d_line_off,
+                           uint64_t first, uint64_t count, uint64_t *off, uint64_t *len, void *stream);
+/* The bytes of lines [first, first + count) to d_out: the locate above, then fcx_decompress_range_shard with
+ * the same index, or the one the call built.  cap < their length: FCX_ERR_CAPACITY with *out_len set to it.
+ * Nothing past d_out[*out_len) is written. */
+int fcx_decompress_lines_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                               uint8_t delim, const uint64_t *d_rec_off, const uint64_t *d_dec_off,
+                               const uint64_t *d_line_off, uint64_t first, uint64_t count, uint8_t *d_out, uint64_t cap,
+                               uint64_t *out_len, void *stream);
+/* d_lines[i] = nl(d_offsets[i]) for noff non-decreasing decoded offsets <= T on the device, such as
+ * fcx_find_shard's d_hits.  An offset above T or a descending pair is found on the device: FCX_ERR_ARG
+ * naming the first bad index.  Only d_lines[0, noff) is written.  noff == 0 is FCX_OK and touches nothing. */
+int fcx_lines_of_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                       const uint64_t *d_offsets, uint64_t noff, uint64_t *d_lines, void *stream);
+/* fcx_find_stream's twins: the file is read in that function's groups and treated as one run; a line that
+ * spans two groups is handled like any other, the delimiters so far are carried from group to group.
+ * fcx_lines_stream: the FCX_LINES_STATS values over the file (wc -l).
+ * fcx_lines_locate_stream: one pass, file-wide *off / *len; reading stops once both boundaries are known
+ * (a range that reaches the last line reads to the end, for T).
+ * fcx_lines_of_stream: noff host offsets, ascending, to host line numbers; per group only the offsets
+ * inside the group's decoded range go to the device; FCX_ERR_ARG naming the first bad index. */
+int fcx_lines_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim, uint64_t *stats);
+int fcx_lines_locate_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim,
+                            uint64_t first, uint64_t count, uint64_t *off, uint64_t *len);
+int fcx_lines_of_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim,
+                        const uint64_t *offsets, uint64_t noff, uint64_t *lines);
+/* a whole file (header + records) in host memory, through the stream forms; fcx_decompress_lines_host is
+ * fcx_lines_locate_stream over the memory, then fcx_decompress_range_host (cap < the length:
+ * FCX_ERR_CAPACITY with *out_len set to it) */
+int fcx_lines_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, uint64_t *stats);
+int fcx_decompress_lines_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, uint64_t first,
+                              uint64_t count, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int fcx_lines_of_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, const uint64_t *offsets,
+                      uint64_t noff, uint64_t *lines);
+/* Counters of the last line call on the context (the stream and host forms: of their last group),
+ * min(n, FCX_LINES_CALL_STATS) values: bytes counted, records decoded, groups decoded, offsets ranked,
+ * selects run.  After a whole-run index bytes counted == T: no byte is counted twice or skipped. */
+int fcx_dctx_lines_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

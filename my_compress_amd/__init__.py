@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -181,6 +181,24 @@ def lib():
         L.fcx_find_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint32, P64, ctypes.c_uint64, P64]
         L.fcx_dctx_find_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
         L.fcx_dctx_set_find_window.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    if hasattr(L, "fcx_lines_index_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint8]
+        index = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fcx_lines_index_shard.argtypes = run + [ctypes.c_void_p, P64, ctypes.c_void_p]
+        L.fcx_lines_locate_shard.argtypes = run + index + [ctypes.c_uint64, ctypes.c_uint64, P64, P64, ctypes.c_void_p]
+        L.fcx_decompress_lines_shard.argtypes = run + index + [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, P64,
+                                                               ctypes.c_void_p]
+        L.fcx_lines_of_shard.argtypes = run + [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.fcx_lines_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, P64]
+        L.fcx_lines_locate_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8,
+                                              ctypes.c_uint64, ctypes.c_uint64, P64, P64]
+        L.fcx_lines_of_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, P64,
+                                          ctypes.c_uint64, P64]
+        L.fcx_lines_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, P64]
+        L.fcx_decompress_lines_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_uint64,
+                                                ctypes.c_uint64, c_u8p, ctypes.c_uint64, P64]
+        L.fcx_lines_of_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, P64, ctypes.c_uint64, P64]
+        L.fcx_dctx_lines_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -791,6 +809,101 @@ class DContext:
         """testing: hits per window of the stream form's hit buffer in later calls (0: the default)"""
         _check(lib().fcx_dctx_set_find_window(self._h, hits), "fcx_dctx_set_find_window")
 
+    # ---- lines (fcx_lines_*): count, locate, decode and number the lines of the decoded run; lines are 0-based,
+    # delim is one byte, count None means "to the end" ----
+    LINES_STATS = ("delimiters", "lines", "decoded", "tail_bytes")
+    LINES_CALL_STATS = ("bytes_counted", "records", "groups", "offsets_ranked", "selects")
+
+    @staticmethod
+    def _delim(delim) -> int:
+        if isinstance(delim, int):
+            if not 0 <= delim <= 255:
+                raise ValueError("the delimiter is one byte")
+            return delim
+        if len(delim) != 1:
+            raise ValueError("the delimiter is one byte")
+        return delim[0]
+
+    def lines_index_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, delim=b"\n", d_line_off: int = 0,
+                          stream: int = 0) -> dict:
+        """the line column of the index: d_line_off[k] = delimiters in front of record k (nblocks + 1 u64 on the
+        device, or 0 for the counts alone); returns {delimiters, lines, decoded, tail_bytes}"""
+        vals = (ctypes.c_uint64 * len(self.LINES_STATS))()
+        _check(lib().fcx_lines_index_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                           self._delim(delim), ctypes.c_void_p(d_line_off or None), vals, ctypes.c_void_p(stream)),
+               "fcx_lines_index_shard")
+        return dict(zip(self.LINES_STATS, [int(v) for v in vals]))
+
+    def lines_locate_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, first: int, count: int = None, delim=b"\n",
+                           index=None, stream: int = 0):
+        """(offset, length) of lines [first, first + count) in the decoded run; index: the three device arrays
+        (rec_off, dec_off, line_off) of index_shard and lines_index_shard, or None (the call counts itself)"""
+        off, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        ro, do, lo = index if index is not None else (0, 0, 0)
+        _check(lib().fcx_lines_locate_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                            self._delim(delim), ctypes.c_void_p(ro or None), ctypes.c_void_p(do or None),
+                                            ctypes.c_void_p(lo or None), first, 2**64 - 1 if count is None else count,
+                                            ctypes.byref(off), ctypes.byref(n), ctypes.c_void_p(stream)), "fcx_lines_locate_shard")
+        return int(off.value), int(n.value)
+
+    def decompress_lines_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, first: int, count: int, d_out: int,
+                               cap: int, delim=b"\n", index=None, stream: int = 0) -> int:
+        """the bytes of lines [first, first + count) to d_out[0 ..); returns their count"""
+        got = ctypes.c_uint64(0)
+        ro, do, lo = index if index is not None else (0, 0, 0)
+        _check(lib().fcx_decompress_lines_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                                self._delim(delim), ctypes.c_void_p(ro or None), ctypes.c_void_p(do or None),
+                                                ctypes.c_void_p(lo or None), first, 2**64 - 1 if count is None else count,
+                                                ctypes.c_void_p(d_out or None), cap, ctypes.byref(got), ctypes.c_void_p(stream)),
+               "fcx_decompress_lines_shard")
+        return int(got.value)
+
+    def lines_of_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, d_offsets: int, noff: int, d_lines: int,
+                       delim=b"\n", stream: int = 0):
+        """d_lines[i] = the line of d_offsets[i] for noff ascending decoded offsets on the device (find_shard's d_hits)"""
+        _check(lib().fcx_lines_of_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, self._delim(delim),
+                                        ctypes.c_void_p(d_offsets or None), noff, ctypes.c_void_p(d_lines or None),
+                                        ctypes.c_void_p(stream)), "fcx_lines_of_shard")
+
+    def count_lines(self, blob: bytes, delim=b"\n") -> dict:
+        """a whole FCX7 or FCX8 file in memory -> {delimiters, lines, decoded, tail_bytes} (wc -l)"""
+        vals = (ctypes.c_uint64 * len(self.LINES_STATS))()
+        _check(lib().fcx_lines_host(self._h, blob, len(blob), self._delim(delim), vals), "fcx_lines_host")
+        return dict(zip(self.LINES_STATS, [int(v) for v in vals]))
+
+    def lines_locate(self, blob: bytes, first: int, count: int = None, delim=b"\n"):
+        """(offset, length) of lines [first, first + count) in what a whole FCX7 or FCX8 file decodes to: one pass
+        (fcx_lines_locate_stream), which ends once both boundaries are known"""
+        import io
+
+        rd, _ = _stream_fns(io.BytesIO(blob), None)
+        off, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().fcx_lines_locate_stream(self._h, rd, None, max(0, len(blob) - HEADER_BYTES), self._delim(delim), first,
+                                             2**64 - 1 if count is None else count, ctypes.byref(off), ctypes.byref(n)),
+               "fcx_lines_locate_stream")
+        return int(off.value), int(n.value)
+
+    def decompress_lines(self, blob: bytes, first: int, count: int = None, delim=b"\n") -> bytes:
+        """the bytes of lines [first, first + count) of a whole FCX7 or FCX8 file (sed -n): the locate once, then the
+        range decode of what it found"""
+        off, n = self.lines_locate(blob, first, count, delim)
+        return self.decompress_range_host(blob, off, n) if n else b""
+
+    def line_numbers(self, blob: bytes, offsets, delim=b"\n"):
+        """the line (0-based) of each of the ascending decoded offsets of a whole FCX7 or FCX8 file"""
+        n = len(offsets)
+        offs = (ctypes.c_uint64 * max(n, 1))(*offsets)
+        out = (ctypes.c_uint64 * max(n, 1))()
+        _check(lib().fcx_lines_of_host(self._h, blob, len(blob), self._delim(delim), offs, n, out), "fcx_lines_of_host")
+        return [int(v) for v in out[:n]]
+
+    def lines_stats(self) -> dict:
+        """counters of the last line call (fcx_dctx_lines_stats)"""
+        n = len(self.LINES_CALL_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_lines_stats(self._h, vals, n), "fcx_dctx_lines_stats")
+        return dict(zip(self.LINES_CALL_STATS, [int(v) for v in vals]))
+
     def set_profiling(self, on: bool = True):
         _check(lib().fcx_dctx_set_profiling(self._h, 1 if on else 0), "fcx_dctx_set_profiling")
 
@@ -909,6 +1022,40 @@ def find(blob: bytes, pattern: bytes, max_hits: int = None, device: int = 0):
         return ctx.find(blob, pattern, max_hits)
     finally:
         ctx.close()
+
+
+def _with_dctx(device, fn):
+    ctx = DContext(device)
+    try:
+        return fn(ctx)
+    finally:
+        ctx.close()
+
+
+def count_lines(blob: bytes, delim=b"\n", device: int = 0) -> dict:
+    """the lines of what the FCX7 or FCX8 file `blob` decodes to, counted on the GPU: {delimiters, lines, decoded,
+    tail_bytes}; an unterminated tail is a line"""
+    return _with_dctx(device, lambda c: c.count_lines(blob, delim))
+
+
+def decompress_lines(blob: bytes, first: int, count: int = None, delim=b"\n", device: int = 0) -> bytes:
+    """lines [first, first + count) (0-based; count None: to the end) of what `blob` decodes to, each with its
+    delimiter: only the records that hold them are expanded"""
+    return _with_dctx(device, lambda c: c.decompress_lines(blob, first, count, delim))
+
+
+def line_numbers(blob: bytes, offsets, delim=b"\n", device: int = 0):
+    """the line (0-based) on which each of the ascending decoded offsets lies"""
+    return _with_dctx(device, lambda c: c.line_numbers(blob, offsets, delim))
+
+
+def find_lines(blob: bytes, pattern: bytes, delim=b"\n", device: int = 0):
+    """[(offset, line)] of every occurrence of `pattern` in what `blob` decodes to: find(), then the line of each
+    hit in a second pass (lines 0-based)"""
+    def both(c):
+        _, hits = c.find(blob, pattern)
+        return list(zip(hits, c.line_numbers(blob, hits, delim)))
+    return _with_dctx(device, both)
 
 
 def my_compress_file_lz77(block: bytes) -> bytes:

@@ -50,6 +50,17 @@
 // One line "find: offset N" per hit, then "find: H hits, decoded bytes = D"; no -o file; exit status 0 when the
 // search ran.  Not with -c, --range, --list, --compare, --verify, --repair, --digest, --test, or both together.
 // Without a HIP device an FCX7 file is searched on the host decoder, with the same lines; FCX8 fails.
+// Lines, decompress mode only (fcx_lines_*: the decoded bytes stay on the device; a line ends with its delimiter,
+// an unterminated tail is a line, lines lie across record boundaries like any other bytes):
+//   --count-lines     prints "lines: L lines, N delimiters, decoded bytes = T" (wc -l); no -o file
+//   --lines A:N       writes lines A .. A+N-1 to -o, A counted from 1 as sed -n 'A,Bp' counts; "A:" means to the
+//                     end (fcx_lines_locate_stream, then the range decode of what it found); --range's twin
+//   --line-numbers    with --find / --find-hex: "find: offset P line K" per hit, K counted from 1; a second pass
+//                     over the file (fcx_lines_of_stream over the hits of fcx_find_stream)
+//   --delim HH        the delimiter byte of the three, two hex digits (default 0a)
+// Usage errors: --count-lines or --lines with -c, --range, --list, --compare, --verify, --repair, --digest, --test,
+// --find or each other; --line-numbers without --find / --find-hex or with --count; --delim without one of the three.
+// Without a HIP device an FCX7 file is served by the host decoder, with the same lines and bytes; FCX8 fails.
 #include <getopt.h>
 
 #include <chrono>
@@ -72,7 +83,9 @@ static int usage() {
             "(decompress only)] [--repair <sidecar file> (written with -c or --compare, read by a decompress)] "
             "[--digest <digest file> (written with -c or --compare, checked by a decompress)] "
             "[--test (decompress with --digest: check only, no output file)] "
-            "[--find <string> | --find-hex <hex digits> [--count] (decompress only: search the decoded bytes)]\n");
+            "[--find <string> | --find-hex <hex digits> [--count | --line-numbers] (decompress only: search the decoded bytes)] "
+            "[--count-lines | --lines <first line>:[<count>] (decompress only: the lines of the decoded bytes)] "
+            "[--delim <two hex digits> (the line delimiter, default 0a)]\n");
     return -1;
 }
 
@@ -517,6 +530,96 @@ static int do_find(FILE *fin, int device, const std::vector<uint8_t> &pat, bool 
     return fcx_cli::find_totals(stats[0], stats[1]);
 }
 
+// --find --line-numbers: the hits as do_find collects them, then a second pass over the file for the line each
+// lies on (fcx_lines_of_stream), or for an FCX7 file without a device the host decoder in one pass
+static int do_find_numbered(FILE *fin, int device, const std::vector<uint8_t> &pat, uint8_t delim) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_find_numbered(fin, nblocks, pat.data(), (uint32_t)pat.size(), delim, nullptr);
+    }
+    uint64_t max_in = 0, stats[4] = {};
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    std::vector<uint64_t> hits;
+    const fcx_hit_fn keep = [](void *u, uint64_t off) { ((std::vector<uint64_t> *)u)->push_back(off); };
+    int r = fcx_find_stream(d, file_read, fin, max_in, pat.data(), (uint32_t)pat.size(), keep, &hits, stats);
+    std::vector<uint64_t> lines(hits.size());
+    if (r == FCX_OK && !hits.empty()) {
+        rewind(fin);
+        r = fcx_lines_of_stream(d, file_read, fin, max_in, delim, hits.data(), hits.size(), lines.data());
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    for (size_t i = 0; i < hits.size(); i++) fcx_cli::find_line_numbered(hits[i], lines[i]);
+    return fcx_cli::find_totals(stats[0], stats[1]);
+}
+
+// --count-lines (fout null) and --lines: fcx_lines_stream, or fcx_lines_locate_stream and then the range decode
+// of what it found in a second pass; for an FCX7 file without a device the host decoder
+static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t first, uint64_t count) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_lines(fin, nblocks, delim, fout, first, count, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_LINES_STATS] = {}, off = 0, len = 0, got = 0;
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    int r;
+    if (!fout) {
+        r = fcx_lines_stream(d, file_read, fin, max_in, delim, stats);
+    } else {
+        r = fcx_lines_locate_stream(d, file_read, fin, max_in, delim, first, count, &off, &len);
+        if (r == FCX_OK && len) {
+            rewind(fin);
+            Files io{fin, fout};
+            r = fcx_decompress_range_stream(d, files_read, files_write, &io, max_in, off, len, &got);
+        }
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fout ? fcx_cli::lines_done(got, off) : fcx_cli::lines_totals(stats[1], stats[0], stats[2]);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -600,6 +703,10 @@ int main(int argc, char **argv) {
                                            {"find", required_argument, nullptr, 'F'},
                                            {"find-hex", required_argument, nullptr, 'X'},
                                            {"count", no_argument, nullptr, 'N'},
+                                           {"count-lines", no_argument, nullptr, 'W'},
+                                           {"lines", required_argument, nullptr, 'S'},
+                                           {"line-numbers", no_argument, nullptr, 'K'},
+                                           {"delim", required_argument, nullptr, 'M'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -611,6 +718,9 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> pattern;
     int finds = 0;   // --find and --find-hex options seen
     bool count_only = false;
+    bool count_lines = false, lines = false, line_numbers = false, delim_given = false;
+    uint64_t line_first = 0, line_count = 0;
+    uint8_t delim = 0x0A;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -644,6 +754,16 @@ int main(int argc, char **argv) {
             finds++;
             break;
         case 'N': count_only = true; break;
+        case 'W': count_lines = true; break;
+        case 'S':
+            if (!fcx_cli::parse_lines(optarg, &line_first, &line_count)) return usage();
+            lines = true;
+            break;
+        case 'K': line_numbers = true; break;
+        case 'M':
+            if (!fcx_cli::parse_delim(optarg, &delim)) return usage();
+            delim_given = true;
+            break;
         default: return usage();
         }
     }
@@ -655,13 +775,18 @@ int main(int argc, char **argv) {
     if (test && (digest.empty() || compress || compare || want.range || want.list)) return usage();
     if (finds > 1 || (count_only && !finds)) return usage();
     if (finds && (compress || want.range || want.list || compare || verify || test || !repair.empty() || !digest.empty())) return usage();
+    if ((count_lines || lines) && (compress || want.range || want.list || compare || verify || test || finds || !repair.empty() ||
+                                   !digest.empty() || (count_lines && lines)))
+        return usage();
+    if (line_numbers && (!finds || count_only)) return usage();
+    if (delim_given && !(count_lines || lines || line_numbers)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    const bool no_out = want.list || compare || test || finds;   // (--list, --compare, --test and --find write no file)
+    const bool no_out = want.list || compare || test || finds || count_lines;   // (--list, --compare, --test, --find and --count-lines write no file)
     FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
     if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
@@ -670,8 +795,14 @@ int main(int argc, char **argv) {
         return -1;
     }
     if (finds) {
-        const int r = do_find(fin, device, pattern, count_only);
+        const int r = line_numbers ? do_find_numbered(fin, device, pattern, delim) : do_find(fin, device, pattern, count_only);
         fclose(fin);
+        return r;
+    }
+    if (count_lines || lines) {
+        const int r = do_lines(fin, fout, device, delim, line_first, line_count);
+        fclose(fin);
+        if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;
     }
     if (compare) {

@@ -1,8 +1,9 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
-// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest and --find.  Host code
+// (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest, --find,
+// --count-lines and --lines.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
-// tools/find_host_check.cpp).
+// tools/find_host_check.cpp, tools/lines_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -426,6 +427,130 @@ inline int host_find(FILE *fin, uint16_t nblocks, const uint8_t *pat, uint32_t m
         }
         pos += n;
         tail = len < m - 1 ? len : m - 1;
+        win.erase(win.begin(), win.end() - (ptrdiff_t)tail);
+        return true;
+    });
+    if (r) return r;
+    if (stats) {
+        stats[0] = hits;
+        stats[1] = pos;
+    }
+    return find_totals(hits, pos);
+}
+
+// ---- --count-lines / --lines / --find --line-numbers: the parsers and the printout, the same on the GPU and on the host ----
+// "A:N" or "A:" (to the end), A >= 1 the first line as sed counts them: *first 0-based, *count UINT64_MAX for
+// "to the end"; false for anything else
+inline bool parse_lines(const char *s, uint64_t *first, uint64_t *count) {
+    uint64_t v[2] = {0, UINT64_MAX};
+    for (int i = 0; i < 2; i++) {
+        if (i == 1 && *s == '\0') break;   // "A:"
+        if (*s < '0' || *s > '9') return false;
+        uint64_t x = 0;
+        for (; *s >= '0' && *s <= '9'; s++) {
+            if (x > (UINT64_MAX - (uint64_t)(*s - '0')) / 10) return false;
+            x = 10 * x + (uint64_t)(*s - '0');
+        }
+        v[i] = x;
+        if (*s != (i == 0 ? ':' : '\0')) return false;
+        if (i == 0) s++;
+    }
+    if (v[0] == 0) return false;
+    *first = v[0] - 1;
+    *count = v[1];
+    return true;
+}
+// exactly two hex digits
+inline bool parse_delim(const char *s, uint8_t *delim) {
+    std::vector<uint8_t> one;
+    if (strlen(s) != 2 || !parse_hex(s, &one)) return false;
+    *delim = one[0];
+    return true;
+}
+inline int lines_totals(uint64_t lines, uint64_t delims, uint64_t decoded) {
+    printf("lines: %llu lines, %llu delimiters, decoded bytes = %llu\n", (unsigned long long)lines, (unsigned long long)delims,
+           (unsigned long long)decoded);
+    return 0;
+}
+inline int lines_done(uint64_t n, uint64_t off) {
+    printf("lines decompress bytes = %llu (offset %llu)\n", (unsigned long long)n, (unsigned long long)off);
+    return 0;
+}
+inline void find_line_numbered(uint64_t off, uint64_t line0) {   // line0: 0-based, printed as sed counts
+    printf("find: offset %llu line %llu\n", (unsigned long long)off, (unsigned long long)(line0 + 1));
+}
+
+// --count-lines (fout null) and --lines without a device: every FCX7 record through the host decoder, the
+// delimiters counted across the records; with fout the bytes of lines [first, first + count) are written and
+// the records behind them are not read.  stats (may be null): delimiters, lines, decoded bytes, bytes behind
+// the last delimiter (--count-lines); bytes written, their offset (--lines).
+inline int host_lines(FILE *fin, uint16_t nblocks, uint8_t delim, FILE *fout, uint64_t first, uint64_t count, uint64_t *stats) {
+    const uint64_t end = count < UINT64_MAX - first ? first + count : UINT64_MAX;
+    uint64_t pos = 0, nl = 0, last = 0, out = 0, out_off = first == 0 ? 0 : UINT64_MAX;   // out_off: where line `first` starts, once known
+    bool io_ok = true;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        for (uint64_t p = 0; p < n;) {   // [p, q): the rest of line nl inside this record
+            const uint8_t *at = (const uint8_t *)memchr(plain + p, delim, (size_t)(n - p));
+            const uint64_t q = at ? (uint64_t)(at - plain) + 1 : n;
+            if (fout && nl >= first && nl < end) {
+                io_ok = io_ok && fwrite(plain + p, 1, (size_t)(q - p), fout) == q - p;
+                out += q - p;
+            }
+            if (at) {
+                nl++;
+                last = pos + q;
+                if (nl == first) out_off = last;
+            }
+            p = q;
+        }
+        pos += n;
+        return io_ok && !(fout && nl >= end);
+    });
+    if (r) return r;
+    if (!io_ok) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (fout) {
+        if (out_off == UINT64_MAX) out_off = pos;   // the file has no line `first`: an empty range at its end
+        if (stats) {
+            stats[0] = out;
+            stats[1] = out_off;
+        }
+        return lines_done(out, out_off);
+    }
+    const uint64_t s[4] = {nl, nl + (pos > 0 && last != pos), pos, pos - last};
+    if (stats) memcpy(stats, s, sizeof(s));
+    return lines_totals(s[1], s[0], s[2]);
+}
+
+// --find --line-numbers without a device: host_find's walk with the delimiters counted alongside, so every hit
+// is printed with the line it lies on.  stats (2 values, may be null): hits, decoded bytes.
+inline int host_find_numbered(FILE *fin, uint16_t nblocks, const uint8_t *pat, uint32_t m, uint8_t delim, uint64_t *stats) {
+    std::vector<uint8_t> win;   // [tail | record]
+    uint64_t pos = 0, hits = 0, tail = 0, nl_first = 0;   // nl_first: delimiters in front of win[0]
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        win.resize(tail);
+        win.insert(win.end(), plain, plain + n);
+        const uint64_t len = win.size(), first = pos - tail;   // win[0] is decoded byte `first`
+        uint64_t seen = 0, nl = nl_first;                      // nl: delimiters in front of win[seen]
+        auto advance = [&](uint64_t to) {
+            for (; seen < to; seen++) nl += win[seen] == delim;
+        };
+        for (uint64_t p = 0; p + m <= len; p++) {
+            const uint8_t *at = (const uint8_t *)memchr(win.data() + p, pat[0], (size_t)(len - m + 1 - p));
+            if (!at) break;
+            p = (uint64_t)(at - win.data());
+            if (memcmp(at, pat, m) == 0) {
+                advance(p);
+                find_line_numbered(first + p, nl);
+                hits++;
+            }
+        }
+        pos += n;
+        tail = len < m - 1 ? len : m - 1;
+        advance(len - tail);
+        nl_first = nl;
         win.erase(win.begin(), win.end() - (ptrdiff_t)tail);
         return true;
     });

@@ -565,6 +565,56 @@ struct FindScratch {
     uint64_t stats[FCX_FIND_STATS] = {};
 };
 
+// ---- status words of a line call (fcx_dctx's ln.words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kLwTotal = 0;       // delimiters of the call so far: advanced by k_lbase, group by group
+constexpr uint32_t kLwGroupBase = 1;   // delimiters of the call before the group counted last (k_lbase)
+constexpr uint32_t kLwBytes = 2;       // bytes counted (k_lcount)
+constexpr uint32_t kLwBadIndex = 3;    // the first offset of a caller's list that is out of order or bound (k_lrank; preset ~0)
+constexpr uint32_t kLwSel = 4;         // two words: 1 + the position of each selected delimiter (k_lselect; preset ~0)
+constexpr uint32_t kLwLast = 6;        // 1 + the position of the last delimiter seen (k_lcount; 0: none yet)
+constexpr uint32_t kLwWords = 8;
+
+// What a line call asks of a run (fcx_lines.hip), and where the run lies in a longer file: the stream forms
+// carry the decoded base, the delimiters so far and the last delimiter from group to group.  Offsets,
+// ranks and positions are file-wide.
+struct LinesReq {
+    uint8_t delim = 0x0A;
+    uint64_t base = 0;          // decoded offset of the run's first byte in the file
+    uint64_t nl_before = 0;     // delimiters before the run
+    uint64_t last_before = 0;   // 1 + the position of the last delimiter before the run (0: none)
+    bool last_run = true;       // the file ends with this run: an offset equal to its end is ranked
+    uint64_t *d_line_off = nullptr;         // the line index: nblocks + 1 values (device), or none
+    const uint64_t *d_offsets = nullptr;    // offsets to rank (device, ascending), noff of them, their ...
+    uint64_t noff = 0;
+    uint64_t *d_lines = nullptr;            // ... line numbers
+    bool check_offsets = false;             // order and bound of d_offsets are the caller's: check them
+    uint64_t sel[2] = {~0ull, ~0ull};       // the sel[q]-th delimiter of the file (1-based) is to be found; ~0: none
+    bool stop_early = false;                // decode no group behind the one that answers both
+    // called once the run's decoded bytes are known, before any group: a stream form stages its offsets here
+    std::function<int(uint64_t decoded, LinesReq *)> staged;
+};
+struct LinesRes {
+    uint64_t nl = 0;        // delimiters up to the end of what was counted (nl_before included)
+    uint64_t last = 0;      // 1 + the position of the last delimiter seen (last_before included)
+    uint64_t decoded = 0;   // the run's decoded bytes (the index's)
+    uint64_t bad = ~0ull;   // the first bad offset's index
+    uint64_t sel[2] = {~0ull, ~0ull};   // 1 + the position of each selected delimiter; ~0: not in what was counted
+};
+// the line calls behind their argument checks, for the stream path's groups of a longer file: messages
+// number the records from rec_base
+int lines_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, LinesReq &req, LinesRes *res,
+              hipStream_t st, uint64_t rec_base);
+
+// scratch of the line calls (fcx_lines.hip)
+struct LinesScratch {
+    DevBuf<uint32_t> chunk_count;    // per chunk of kLChunk decoded bytes its delimiters, and ...
+    DevBuf<uint32_t> chunk_base;     // ... the delimiters of the group's chunks before it
+    DevBuf<uint64_t> words;          // kLw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint64_t> offs, lines;    // the stream forms: a group's slice of the offsets and its line numbers
+    uint64_t stats[FCX_LINES_CALL_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -597,6 +647,7 @@ struct fcx_dctx {
     fcx::RepairScratch rp;
     fcx::DigestScratch dg;
     fcx::FindScratch fd;
+    fcx::LinesScratch ln;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

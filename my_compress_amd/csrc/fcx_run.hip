@@ -1,7 +1,7 @@
 // fcx_run.hip — the run core: the host half of every call over a device-resident run of
 // FCX7 / FCX8 records that is indexed, decoded group by group into the verification's bounded buffer and
 // judged block by block: verify_run (fcx_verify.hip), repair_apply_run (fcx_repair.hip) and check_run
-// (fcx_digest.hip); or searched across the blocks: find_run (fcx_find.hip).  Host code only; the stage times of such a call: RunTimes (fcx_dec_shared.h).
+// (fcx_digest.hip); or searched or counted across the blocks: find_run (fcx_find.hip), lines_run (fcx_lines.hip).  Host code only; the stage times of such a call: RunTimes (fcx_dec_shared.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -785,6 +785,149 @@ int fcx_find_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const uint
     return FCX_OK;
 }
 
+}  // extern "C"
+
+// ---- the line calls' stream and host forms (include/fcx.h) ---------------------------
+
+namespace {
+
+// The groups of a file as one run of lines: `each` prepares the group's request (the decoded base, the
+// delimiters so far and the last delimiter are already in it), `after` sees its result and may end the reading.
+// sum: delimiters, 1 + the position of the last one, decoded bytes.
+template <typename Each, typename After>
+int lines_groups(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, uint64_t *sum, Each each,
+                        After after) {
+    sum[0] = sum[1] = sum[2] = 0;
+    return stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                         [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        LinesReq q;
+        q.delim = delim;
+        q.base = sum[2];
+        q.nl_before = sum[0];
+        q.last_before = sum[1];
+        q.last_run = false;   // (whether a group is the file's last shows only at the end of the reading)
+        each(&q, st);
+        LinesRes res;
+        FCX_TRY(fcx::lines_run(dctx, lz78 ? '8' : '7', x.din, used, nb, q, &res, st, before));
+        sum[0] = res.nl;
+        sum[1] = res.last;
+        sum[2] += res.decoded;
+        return after(q, res, st);
+    });
+}
+
+void lines_file_stats(const uint64_t *sum, uint64_t *stats) {
+    stats[0] = sum[0];
+    stats[1] = sum[0] + (sum[2] > 0 && sum[1] != sum[2]);
+    stats[2] = sum[2];
+    stats[3] = sum[2] - std::min(sum[1], sum[2]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fcx_lines_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, uint64_t *stats) {
+    if (!dctx || !rd || !stats) return fail(FCX_ERR_ARG, "fcx_lines_stream: NULL argument");
+    uint64_t sum[3];
+    FCX_TRY(lines_groups(dctx, rd, user, max_in, delim, sum, [](LinesReq *, hipStream_t) {}, [](const LinesReq &, const LinesRes &, hipStream_t) { return FCX_OK; }));
+    lines_file_stats(sum, stats);
+    return FCX_OK;
+}
+
+int fcx_lines_locate_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, uint64_t first,
+                            uint64_t count, uint64_t *off, uint64_t *len) {
+    if (!dctx || !rd || !off || !len) return fail(FCX_ERR_ARG, "fcx_lines_locate_stream: NULL argument");
+    const uint64_t r[2] = {first, count < ~0ull - first ? first + count : ~0ull};
+    uint64_t found[2] = {r[0] ? ~0ull : 0, r[1] ? ~0ull : 0};   // 1 + the position of each boundary delimiter; ~0: not seen yet
+    uint64_t sum[3];
+    FCX_TRY(lines_groups(dctx, rd, user, max_in, delim, sum,
+                         [&](LinesReq *q, hipStream_t) {
+                             for (int i = 0; i < 2; i++) q->sel[i] = found[i] == ~0ull ? r[i] : ~0ull;
+                             q->stop_early = true;
+                         },
+                         [&](const LinesReq &q, const LinesRes &res, hipStream_t) {
+                             for (int i = 0; i < 2; i++)
+                                 if (q.sel[i] != ~0ull) found[i] = res.sel[i];
+                             return found[0] != ~0ull && found[1] != ~0ull ? kStopReading : FCX_OK;
+                         }));
+    // a boundary the file does not hold is its end: the reading went to it, so sum[2] is T
+    *off = found[0] == ~0ull ? sum[2] : found[0];
+    *len = (found[1] == ~0ull ? sum[2] : found[1]) - *off;
+    return FCX_OK;
+}
+
+int fcx_lines_of_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, const uint64_t *offsets,
+                        uint64_t noff, uint64_t *lines) {
+    if (!dctx || !rd || (noff && (!offsets || !lines))) return fail(FCX_ERR_ARG, "fcx_lines_of_stream: NULL argument");
+    for (uint64_t i = 1; i < noff; i++)
+        if (offsets[i - 1] > offsets[i]) return fail(FCX_ERR_ARG, "fcx_lines_of_stream: offset " + std::to_string(i) + " descends");
+    uint64_t done = 0, take = 0;   // offsets answered, the group's slice
+    uint64_t sum[3];
+    FCX_TRY(lines_groups(dctx, rd, user, max_in, delim, sum,
+                         [&](LinesReq *q, hipStream_t st) {
+                             // the offsets in [base, base + decoded) go to the device once the group's size is known
+                             q->staged = [&, st](uint64_t decoded, LinesReq *r) -> int {
+                                 const uint64_t *lo = offsets + done, *hi = std::lower_bound(lo, offsets + noff, r->base + decoded);
+                                 take = (uint64_t)(hi - lo);
+                                 if (!take) return FCX_OK;
+                                 LinesScratch &S = dctx->ln;
+                                 FCX_TRY(S.offs.reserve(8 * take, "line offsets"));
+                                 FCX_TRY(S.lines.reserve(8 * take, "line numbers"));
+                                 FCX_HIP(hipMemcpyAsync(S.offs, lo, 8 * take, hipMemcpyHostToDevice, st));
+                                 FCX_HIP(hipStreamSynchronize(st));
+                                 r->d_offsets = S.offs;
+                                 r->noff = take;
+                                 r->d_lines = S.lines;
+                                 return FCX_OK;
+                             };
+                         },
+                         [&](const LinesReq &, const LinesRes &, hipStream_t st) -> int {
+                             if (take) {
+                                 FCX_HIP(hipMemcpyAsync(lines + done, dctx->ln.lines, 8 * take, hipMemcpyDeviceToHost, st));
+                                 FCX_HIP(hipStreamSynchronize(st));
+                             }
+                             done += take;
+                             take = 0;
+                             return FCX_OK;   // (groups behind the last offset are still read: an offset may be the file's end)
+                         }));
+    for (; done < noff; done++) {   // what is left lies at the file's end, or behind it
+        if (offsets[done] > sum[2])
+            return fail(FCX_ERR_ARG, "fcx_lines_of_stream: offset " + std::to_string(done) + " lies behind the file's end");
+        lines[done] = sum[0];
+    }
+    return FCX_OK;
+}
+
+int fcx_lines_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t delim, uint64_t *stats) {
+    if (!dctx || !in || !stats) return fail(FCX_ERR_ARG, "fcx_lines_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0};
+    return fcx_lines_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, delim, stats);
+}
+
+int fcx_decompress_lines_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t delim, uint64_t first, uint64_t count,
+                              uint8_t *out, uint64_t cap, uint64_t *out_len) {
+    if (!dctx || !in || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_decompress_lines_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0};
+    uint64_t off = 0, len = 0;
+    *out_len = 0;
+    FCX_TRY(fcx_lines_locate_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, delim, first, count, &off, &len));
+    *out_len = len;
+    if (len > cap) return fail(FCX_ERR_CAPACITY, "fcx_decompress_lines_host: output capacity too small");
+    if (len == 0) return FCX_OK;
+    return fcx_decompress_range_host(dctx, in, in_len, off, len, out, len, out_len);
+}
+
+int fcx_lines_of_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_t delim, const uint64_t *offsets, uint64_t noff,
+                      uint64_t *lines) {
+    if (!dctx || !in || (noff && (!offsets || !lines))) return fail(FCX_ERR_ARG, "fcx_lines_of_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    MemIO comp{in, in_len, 0, nullptr, 0, 0};
+    return fcx_lines_of_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, delim, offsets, noff, lines);
+}
+
 int fcx_digest_stream(fcx_dctx *c, fcx_read_fn rd, void *user, uint32_t block_bytes, fcx_write_fn wr, void *user_wr,
                       uint64_t *stats) {
     if (!c || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_digest_stream: NULL argument");
