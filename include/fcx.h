@@ -693,6 +693,89 @@ int fcx_lines_of_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t
  * selects run.  After a whole-run index bytes counted == T: no byte is counted twice or skipped. */
 int fcx_dctx_lines_stats(fcx_dctx *ctx, uint64_t *out, int n);
 
+/* ---- grep: which lines of the decoded run hold a byte string, and a decode of many ranges (FCX7 and FCX8) ----
+ * D, T, the delimiter d and the lines s_j / e_j are those of the line calls above, a hit is the search's: an
+ * offset p with D[p, p + plen) == pattern.  A pattern that holds d is FCX_ERR_ARG (grep -F cannot express it
+ * either), so every hit lies wholly inside one line.  Line j is selected iff some hit p has s_j <= p < e_j.
+ * The result is the selected lines in ascending order, each exactly once however many hits it holds, as
+ * (start = s_j, end = e_j): the delimiter belongs to the line it ends, an unterminated tail line ends at T, a
+ * run without a delimiter is one line [0, T).  Record, block, tile and group boundaries do not exist for
+ * this: a line may be longer than a record or a decode group, hold hits on both sides of any boundary and
+ * span records that decode to no bytes.  A repair sidecar is not applied. */
+#define FCX_GREP_STATS 5   /* lines, bytes (sum of end - start), hits, judged, decoded */
+/* The selected lines of the nblocks records at d_rec: stats[0] (host, FCX_GREP_STATS values) is always their
+ * number in the run, d_start / d_end[0, min(cap, stats[0])) (device, two separate arrays: d_start feeds
+ * fcx_lines_of_shard, both feed fcx_decompress_ranges_shard) receive the first of them and nothing behind
+ * is written; both NULL with cap == 0 is the count alone; FCX_OK whether or not cap was reached.  stats[3],
+ * the start positions judged, is max(T - plen + 1, 0) after every call, stats[4] is T.  nblocks == 0 gives
+ * zeros and touches no device.  The run is indexed, then decoded in fcx_verify_shard's groups into the
+ * context's bounded buffer (fcx_dctx_set_verify_group applies; the result does not depend on it); each group
+ * is scanned once together with the last plen - 1 bytes before it, and what goes from group to group is a
+ * few words (the last delimiter, the last hit, the lines so far, whether the open line is selected), never
+ * bytes of the open line.  Device scratch beyond the decoded group is two bitmaps of group bytes / 8 each
+ * and 48 bytes per 4096 decoded bytes, whatever the number of hits or lines.  Synchronises `stream`.
+ * FCX_ERR_ARG before the device is touched: a NULL ctx, pattern or stats, a NULL d_rec with nblocks > 0, a
+ * NULL d_start or d_end with cap > 0, a kind other than '7' or '8', plen outside [1, FCX_FIND_MAX_PATTERN],
+ * a pattern that holds delim; a decode group of 4 GiB or more is FCX_ERR_ARG as in fcx_find_shard.
+ * Stage table with profiling: index, decode, scan, select, summary. */
+int fcx_grep_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                   const uint8_t *pattern /* host */, uint32_t plen, uint64_t *d_start, uint64_t *d_end, uint64_t cap,
+                   uint64_t *stats, void *stream);
+/* Device bytes the last fcx_grep_shard call on the context reserved beside the decoded group (the bitmaps and the
+ * tile words of its largest group; 0 after a call without records). */
+int fcx_dctx_grep_scratch(fcx_dctx *ctx, uint64_t *bytes);
+/* Decodes nranges byte ranges [d_start[i], d_end[i]) of D (device arrays) in one call: d_out[0, sum) is the
+ * concatenation of D[start_i, end_i) in order, *out_len is always the sum.  Rules: start_i <= end_i <= T and
+ * end_i <= start_{i+1} (ascending and disjoint; empty and touching ranges are allowed).  They are checked on
+ * the device before anything is stored: FCX_ERR_ARG naming the first range that breaks one.  sum > cap:
+ * FCX_ERR_CAPACITY with nothing stored, so d_out == NULL with cap == 0 is the size query.  nranges == 0
+ * stores nothing, decodes nothing and touches no device.  The ranges never visit the host: a device pass
+ * scans their lengths into output offsets and leaves one flag per record that holds a byte of a range, and
+ * only those nblocks flags come back.  Of each of fcx_verify_shard's groups only the touched records are
+ * decoded, stretch by stretch, to their places in the context's bounded buffer (a group without one is
+ * skipped), and the pieces of the ranges inside are copied to their output offsets.  Pass fcx_index_shard's arrays or NULL
+ * for both (the call then indexes the run itself); a given index is trusted for where things are, not for
+ * safety, as in fcx_decompress_range_shard: FCX_ERR_FORMAT when it does not start at 0, does not ascend or
+ * leaves the run, or a decoded record has another size than it says.  With an index a damaged record that no
+ * range touches does not fail the call.  FCX_ERR_ARG before the device is touched: a NULL ctx or out_len, a
+ * NULL d_rec with nblocks > 0, NULL ranges with nranges > 0, a NULL d_out with cap > 0, half an index, a
+ * kind other than '7' or '8'.  Synchronises `stream`.  Stage table with profiling: index, map, decode, gather. */
+int fcx_decompress_ranges_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                                const uint64_t *d_rec_off, const uint64_t *d_dec_off,
+                                const uint64_t *d_start, const uint64_t *d_end, uint64_t nranges,
+                                uint8_t *d_out, uint64_t cap, uint64_t *out_len, void *stream);
+/* Counters of the last fcx_decompress_ranges_shard call on the context, min(n, FCX_RANGES_STATS) values:
+ * ranges, bytes stored, records touched, records decoded, groups decoded. */
+#define FCX_RANGES_STATS 5
+int fcx_dctx_ranges_stats(fcx_dctx *ctx, uint64_t *out, int n);
+/* A whole file (header + records) in host memory.  fcx_grep_host: the bytes of the selected lines to out (grep
+ * -F): the records go to the device once, fcx_grep_shard's arrays feed fcx_decompress_ranges_shard there, and
+ * only the lines' bytes come back; *out_len is always their number, cap < *out_len is FCX_ERR_CAPACITY, out ==
+ * NULL with cap == 0 the size query; stats (FCX_GREP_STATS values, may be NULL).  fcx_decompress_ranges_host:
+ * nranges host ranges under fcx_decompress_ranges_shard's rules. */
+int fcx_grep_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, const uint8_t *pattern, uint32_t plen,
+                  uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats);
+typedef void (*fcx_range_fn)(void *user, uint64_t start, uint64_t end);
+/* fcx_find_stream's twin: reads the header, then the records in that function's groups of 256, and treats the
+ * file as one run: the words above and the decoded base go from group to group, so a line across two stream
+ * groups with a hit on either side is one line.  on_line (may be NULL: the totals alone) is called for every
+ * selected line of the file once, in order, with its file-wide start and its true end: a selected line still
+ * open at a stream group's end is held back (two words) until a later group closes it or the file ends.  The
+ * lines come to the host by windows of fcx_dctx_set_find_window lines.  stats (FCX_GREP_STATS values, may be
+ * NULL) over the file.  Argument checks as fcx_grep_shard, before anything is read. */
+int fcx_grep_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim,
+                    const uint8_t *pattern, uint32_t plen, fcx_range_fn on_line, void *user_line, uint64_t *stats);
+/* fcx_decompress_range_stream's twin for many ranges: n host ranges under fcx_decompress_ranges_shard's rules,
+ * checked on the host before anything is read (FCX_ERR_ARG naming the first that descends, overlaps or has end <
+ * start).  Each stream group is indexed, gets the slice of the ranges that meets its decoded bytes, clipped to
+ * them, gathers it on the device and writes it; a range across groups is written in pieces.  Reading stops
+ * behind the group that holds the last range's end.  A range that ends behind the file's end is FCX_ERR_ARG once
+ * the end is reached; what lay inside the file has been written by then.  *out_len (may be NULL): bytes written. */
+int fcx_decompress_ranges_stream(fcx_dctx *ctx, fcx_read_fn read_comp, fcx_write_fn write_out, void *user, uint64_t max_in,
+                                 const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *out_len);
+int fcx_decompress_ranges_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *starts, const uint64_t *ends,
+                               uint64_t nranges, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

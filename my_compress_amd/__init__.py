@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -199,6 +199,22 @@ def lib():
                                                 ctypes.c_uint64, c_u8p, ctypes.c_uint64, P64]
         L.fcx_lines_of_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, P64, ctypes.c_uint64, P64]
         L.fcx_dctx_lines_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+    if hasattr(L, "fcx_grep_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]
+        L.fcx_grep_shard.argtypes = run + [ctypes.c_uint8, c_u8p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, P64,
+                                           ctypes.c_void_p]
+        L.fcx_decompress_ranges_shard.argtypes = run + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                        ctypes.c_void_p, ctypes.c_uint64, P64, ctypes.c_void_p]
+        L.fcx_dctx_ranges_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+        L.fcx_dctx_grep_scratch.argtypes = [ctypes.c_void_p, P64]
+        L.fcx_grep_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint64,
+                                    P64, P64]
+        L.fcx_decompress_ranges_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, P64, P64, ctypes.c_uint64, c_u8p, ctypes.c_uint64,
+                                                 P64]
+        L.fcx_grep_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, c_u8p, ctypes.c_uint32,
+                                      RANGE_FN, ctypes.c_void_p, P64]
+        L.fcx_decompress_ranges_stream.argtypes = [ctypes.c_void_p, READ_FN, WRITE_FN, ctypes.c_void_p, ctypes.c_uint64, P64, P64,
+                                                   ctypes.c_uint64, P64]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -243,6 +259,8 @@ VERIFY_SAME = 0xFFFFFFFF   # FCX_VERIFY_SAME
 # fcx_hit_fn: the decoded offset of a hit
 HIT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64)
 FIND_MAX_PATTERN = 256     # FCX_FIND_MAX_PATTERN
+# fcx_range_fn: start and end of a selected line
+RANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
 
 
 # the repair sidecar (include/fcx.h): one 32-byte entry layout on the device, in the FCXR file and here
@@ -809,6 +827,95 @@ class DContext:
         """testing: hits per window of the stream form's hit buffer in later calls (0: the default)"""
         _check(lib().fcx_dctx_set_find_window(self._h, hits), "fcx_dctx_set_find_window")
 
+    # ---- grep (fcx_grep_*, fcx_decompress_ranges_*): the lines that hold a byte string, and many ranges in one call ----
+    GREP_STATS = ("lines", "bytes", "hits", "judged", "decoded")
+    RANGES_STATS = ("ranges", "bytes", "records_touched", "records_decoded", "groups")
+
+    def grep_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, pattern: bytes, delim=b"\n", d_start: int = 0,
+                   d_end: int = 0, cap: int = 0, stream: int = 0) -> dict:
+        """the lines of device records (no header) that hold `pattern` (1 to 256 bytes without the delimiter): returns
+        {lines, bytes, hits, judged, decoded}; start and end of the first min(cap, lines) go to d_start / d_end (u64
+        on the device, two arrays), ascending"""
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        _check(lib().fcx_grep_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, self._delim(delim),
+                                    pattern, len(pattern), ctypes.c_void_p(d_start or None), ctypes.c_void_p(d_end or None), cap, vals,
+                                    ctypes.c_void_p(stream)), "fcx_grep_shard")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals]))
+
+    def decompress_ranges_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, d_start: int, d_end: int, nranges: int,
+                                d_out: int, cap: int, index=None, stream: int = 0) -> int:
+        """the decoded bytes of nranges ascending, disjoint ranges [d_start[i], d_end[i]) (u64 on the device) back to
+        back to d_out[0 ..); returns their count; index: the device arrays (rec_off, dec_off) of index_shard, or None"""
+        got = ctypes.c_uint64(0)
+        ro, do = index if index is not None else (0, 0)
+        _check(lib().fcx_decompress_ranges_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks,
+                                                 ctypes.c_void_p(ro or None), ctypes.c_void_p(do or None), ctypes.c_void_p(d_start or None),
+                                                 ctypes.c_void_p(d_end or None), nranges, ctypes.c_void_p(d_out or None), cap,
+                                                 ctypes.byref(got), ctypes.c_void_p(stream)), "fcx_decompress_ranges_shard")
+        return int(got.value)
+
+    def ranges_stats(self) -> dict:
+        """counters of the last decompress_ranges_shard call (fcx_dctx_ranges_stats)"""
+        n = len(self.RANGES_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_ranges_stats(self._h, vals, n), "fcx_dctx_ranges_stats")
+        return dict(zip(self.RANGES_STATS, [int(v) for v in vals]))
+
+    def grep_scratch(self) -> int:
+        """device bytes the last grep_shard call reserved beside the decoded group: bitmaps and tile words"""
+        v = ctypes.c_uint64(0)
+        _check(lib().fcx_dctx_grep_scratch(self._h, ctypes.byref(v)), "fcx_dctx_grep_scratch")
+        return int(v.value)
+
+    def grep_host(self, blob: bytes, pattern: bytes, delim=b"\n"):
+        """a whole FCX7 or FCX8 file in memory -> (stats, the bytes of the lines that hold `pattern`): grep -F; the
+        lines are found and gathered on the GPU, only their bytes come back"""
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        need = ctypes.c_uint64(0)
+        args = (self._h, blob, len(blob), self._delim(delim), pattern, len(pattern))
+        rc = lib().fcx_grep_host(*args, None, 0, ctypes.byref(need), vals)   # the size
+        if rc != -2:
+            _check(rc, "fcx_grep_host")
+            return dict(zip(self.GREP_STATS, [int(v) for v in vals])), b""
+        out = ctypes.create_string_buffer(need.value)
+        _check(lib().fcx_grep_host(*args, out, need.value, ctypes.byref(need), vals), "fcx_grep_host")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals])), out.raw[:need.value]
+
+    def decompress_ranges_host(self, blob: bytes, ranges) -> bytes:
+        """the decoded bytes of the ascending, disjoint (start, end) pairs of a whole FCX7 or FCX8 file, back to back"""
+        n = len(ranges)
+        starts = (ctypes.c_uint64 * max(n, 1))(*[r[0] for r in ranges])
+        ends = (ctypes.c_uint64 * max(n, 1))(*[r[1] for r in ranges])
+        cap = sum(max(e - s, 0) for s, e in ranges)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        got = ctypes.c_uint64(0)
+        _check(lib().fcx_decompress_ranges_host(self._h, blob, len(blob), starts, ends, n, out, cap, ctypes.byref(got)),
+               "fcx_decompress_ranges_host")
+        return out.raw[:got.value]
+
+    def grep_stream(self, src, pattern: bytes, delim=b"\n", max_in: int = 0, want_lines: bool = True):
+        """an FCX7 or FCX8 file from src (binary reader) -> (stats, [(start, end)] of every line that holds `pattern`,
+        ascending, each once and with its true end); want_lines False: the totals alone"""
+        rd, _ = _stream_fns(src, None)
+        got = []
+        cb = RANGE_FN(lambda _u, s, e: got.append((int(s), int(e)))) if want_lines else ctypes.cast(None, RANGE_FN)
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        _check(lib().fcx_grep_stream(self._h, rd, None, max_in, self._delim(delim), pattern, len(pattern), cb, None, vals),
+               "fcx_grep_stream")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals])), got
+
+    def decompress_ranges_stream(self, src, sink, ranges, max_in: int = 0) -> int:
+        """the decoded bytes of the ascending, disjoint (start, end) pairs of an FCX7 or FCX8 file from src (binary
+        reader) to sink, back to back; reads no further than the last range needs; returns the bytes written"""
+        rd, wr = _stream_fns(src, sink)
+        n = len(ranges)
+        starts = (ctypes.c_uint64 * max(n, 1))(*[r[0] for r in ranges])
+        ends = (ctypes.c_uint64 * max(n, 1))(*[r[1] for r in ranges])
+        got = ctypes.c_uint64(0)
+        _check(lib().fcx_decompress_ranges_stream(self._h, rd, wr, None, max_in, starts, ends, n, ctypes.byref(got)),
+               "fcx_decompress_ranges_stream")
+        return int(got.value)
+
     # ---- lines (fcx_lines_*): count, locate, decode and number the lines of the decoded run; lines are 0-based,
     # delim is one byte, count None means "to the end" ----
     LINES_STATS = ("delimiters", "lines", "decoded", "tail_bytes")
@@ -1056,6 +1163,20 @@ def find_lines(blob: bytes, pattern: bytes, delim=b"\n", device: int = 0):
         _, hits = c.find(blob, pattern)
         return list(zip(hits, c.line_numbers(blob, hits, delim)))
     return _with_dctx(device, both)
+
+
+def grep(blob: bytes, pattern: bytes, delim=b"\n", device: int = 0) -> bytes:
+    """the lines of what the FCX7 or FCX8 file `blob` decodes to that hold `pattern` (1 to 256 bytes without the
+    delimiter), each once and with its delimiter, in order: grep -F on the GPU, only the lines' bytes come back"""
+    return _with_dctx(device, lambda c: c.grep_host(blob, pattern, delim)[1])
+
+
+def grep_ranges(blob: bytes, pattern: bytes, delim=b"\n", device: int = 0):
+    """(stats, [(start, end)]) of the lines of what `blob` decodes to that hold `pattern`: the byte ranges grep()
+    prints, for decompress_ranges or a viewer; stats: {lines, bytes, hits, judged, decoded}"""
+    import io
+
+    return _with_dctx(device, lambda c: c.grep_stream(io.BytesIO(blob), pattern, delim, max(0, len(blob) - HEADER_BYTES)))
 
 
 def my_compress_file_lz77(block: bytes) -> bytes:

@@ -61,6 +61,17 @@
 // Usage errors: --count-lines or --lines with -c, --range, --list, --compare, --verify, --repair, --digest, --test,
 // --find or each other; --line-numbers without --find / --find-hex or with --count; --delim without one of the three.
 // Without a HIP device an FCX7 file is served by the host decoder, with the same lines and bytes; FCX8 fails.
+// Matching lines, decompress mode only (grep -F; fcx_grep_stream, then fcx_decompress_ranges_stream):
+//   --grep STRING     writes every line that holds the argument's bytes (1 to 256, without the delimiter) to -o, each
+//                     once and with its delimiter, in order; pass 1 collects the lines' byte ranges (16 bytes a line),
+//                     pass 2 decodes the records they touch and writes them
+//   --grep-hex HEX    the same for any bytes
+//   --count           with either: only the totals, no -o file
+//   --delim HH        the delimiter byte (default 0a)
+// The last line printed is "grep: L lines, B bytes, H hits, decoded bytes = T".  Usage errors: --grep or --grep-hex with
+// -c, --range, --list, --compare, --verify, --repair, --digest, --test, --find, --find-hex, --count-lines, --lines,
+// --line-numbers or each other; a pattern that holds the delimiter; an empty or over-long pattern.
+// Without a HIP device an FCX7 file is cut into lines on the host decoder, with the same bytes and last line; FCX8 fails.
 #include <getopt.h>
 
 #include <chrono>
@@ -85,6 +96,7 @@ static int usage() {
             "[--test (decompress with --digest: check only, no output file)] "
             "[--find <string> | --find-hex <hex digits> [--count | --line-numbers] (decompress only: search the decoded bytes)] "
             "[--count-lines | --lines <first line>:[<count>] (decompress only: the lines of the decoded bytes)] "
+            "[--grep <string> | --grep-hex <hex digits> [--count] (decompress only: the lines that hold the bytes, to -o)] "
             "[--delim <two hex digits> (the line delimiter, default 0a)]\n");
     return -1;
 }
@@ -620,6 +632,61 @@ static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t f
     return fout ? fcx_cli::lines_done(got, off) : fcx_cli::lines_totals(stats[1], stats[0], stats[2]);
 }
 
+// --grep / --grep-hex: pass 1 collects the matching lines' byte ranges (fcx_grep_stream), pass 2 decodes them to
+// fout (fcx_decompress_ranges_stream; fout null: --count, the totals alone); for an FCX7 file without a device the
+// host decoder in one pass
+static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t> &pat, uint8_t delim) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_grep(fin, nblocks, delim, pat.data(), (uint32_t)pat.size(), fout, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_GREP_STATS] = {}, got = 0;
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    struct Lines {
+        std::vector<uint64_t> starts, ends;
+    } lines;
+    const fcx_range_fn keep = [](void *u, uint64_t s, uint64_t e) {
+        ((Lines *)u)->starts.push_back(s);
+        ((Lines *)u)->ends.push_back(e);
+    };
+    int r = fcx_grep_stream(d, file_read, fin, max_in, delim, pat.data(), (uint32_t)pat.size(), fout ? keep : nullptr, &lines, stats);
+    if (r == FCX_OK && fout && !lines.starts.empty()) {
+        rewind(fin);
+        Files io{fin, fout};
+        r = fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
+                                         lines.starts.size(), &got);
+        if (r == FCX_OK && got != stats[1]) {
+            fprintf(stderr, "fcx: the lines' bytes disagree with the grep's sum\n");
+            fcx_dctx_destroy(d);
+            return -1;
+        }
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::grep_totals(stats[0], stats[1], stats[2], stats[4]);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -707,6 +774,8 @@ int main(int argc, char **argv) {
                                            {"lines", required_argument, nullptr, 'S'},
                                            {"line-numbers", no_argument, nullptr, 'K'},
                                            {"delim", required_argument, nullptr, 'M'},
+                                           {"grep", required_argument, nullptr, 'G'},
+                                           {"grep-hex", required_argument, nullptr, 'H'},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -717,6 +786,8 @@ int main(int argc, char **argv) {
     std::string original, repair, digest;
     std::vector<uint8_t> pattern;
     int finds = 0;   // --find and --find-hex options seen
+    std::vector<uint8_t> grep_pattern;
+    int greps = 0;   // --grep and --grep-hex options seen
     bool count_only = false;
     bool count_lines = false, lines = false, line_numbers = false, delim_given = false;
     uint64_t line_first = 0, line_count = 0;
@@ -753,6 +824,15 @@ int main(int argc, char **argv) {
             if (!fcx_cli::parse_hex(optarg, &pattern)) return usage();
             finds++;
             break;
+        case 'G':
+            grep_pattern.assign(optarg, optarg + strlen(optarg));
+            if (grep_pattern.empty() || grep_pattern.size() > FCX_FIND_MAX_PATTERN) return usage();
+            greps++;
+            break;
+        case 'H':
+            if (!fcx_cli::parse_hex(optarg, &grep_pattern)) return usage();
+            greps++;
+            break;
         case 'N': count_only = true; break;
         case 'W': count_lines = true; break;
         case 'S':
@@ -773,20 +853,24 @@ int main(int argc, char **argv) {
     if (!repair.empty() && (want.range || want.list)) return usage();
     if (!digest.empty() && (want.range || want.list)) return usage();
     if (test && (digest.empty() || compress || compare || want.range || want.list)) return usage();
-    if (finds > 1 || (count_only && !finds)) return usage();
+    if (finds > 1 || greps > 1 || (count_only && !finds && !greps)) return usage();
+    if (greps && (compress || want.range || want.list || compare || verify || test || finds || count_lines || lines || line_numbers ||
+                  !repair.empty() || !digest.empty() || fcx_cli::pattern_holds(grep_pattern, delim)))
+        return usage();
     if (finds && (compress || want.range || want.list || compare || verify || test || !repair.empty() || !digest.empty())) return usage();
     if ((count_lines || lines) && (compress || want.range || want.list || compare || verify || test || finds || !repair.empty() ||
                                    !digest.empty() || (count_lines && lines)))
         return usage();
     if (line_numbers && (!finds || count_only)) return usage();
-    if (delim_given && !(count_lines || lines || line_numbers)) return usage();
+    if (delim_given && !(count_lines || lines || line_numbers || greps)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
     }
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
-    const bool no_out = want.list || compare || test || finds || count_lines;   // (--list, --compare, --test, --find and --count-lines write no file)
+    // (--list, --compare, --test, --find, --count-lines and --grep --count write no file)
+    const bool no_out = want.list || compare || test || finds || count_lines || (greps && count_only);
     FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
     if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
@@ -797,6 +881,12 @@ int main(int argc, char **argv) {
     if (finds) {
         const int r = line_numbers ? do_find_numbered(fin, device, pattern, delim) : do_find(fin, device, pattern, count_only);
         fclose(fin);
+        return r;
+    }
+    if (greps) {
+        const int r = do_grep(fin, fout, device, grep_pattern, delim);
+        fclose(fin);
+        if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;
     }
     if (count_lines || lines) {

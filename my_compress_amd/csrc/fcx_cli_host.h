@@ -1,9 +1,9 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
 // (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest, --find,
-// --count-lines and --lines.  Host code
+// --count-lines, --lines and --grep.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
-// tools/find_host_check.cpp, tools/lines_host_check.cpp).
+// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -560,6 +560,66 @@ inline int host_find_numbered(FILE *fin, uint16_t nblocks, const uint8_t *pat, u
         stats[1] = pos;
     }
     return find_totals(hits, pos);
+}
+
+// ---- --grep / --grep-hex: the printout, the same on the GPU and on the host ----
+inline int grep_totals(uint64_t lines, uint64_t bytes, uint64_t hits, uint64_t decoded) {
+    printf("grep: %llu lines, %llu bytes, %llu hits, decoded bytes = %llu\n", (unsigned long long)lines, (unsigned long long)bytes,
+           (unsigned long long)hits, (unsigned long long)decoded);
+    return 0;
+}
+// does the pattern hold the delimiter?  (then no line can hold the pattern: a usage error)
+inline bool pattern_holds(const std::vector<uint8_t> &pat, uint8_t delim) { return memchr(pat.data(), delim, pat.size()) != nullptr; }
+
+// --grep without a device: every FCX7 record through the host decoder, cut into lines across the records; the
+// open line is buffered (a hit lies wholly inside a line, so a line is searched once, when it closes or the
+// file ends) and written to fout (null: --count) when it holds the pattern.  stats (4 values, may be null):
+// lines, bytes, hits, decoded bytes.
+inline int host_grep(FILE *fin, uint16_t nblocks, uint8_t delim, const uint8_t *pat, uint32_t m, FILE *fout, uint64_t *stats) {
+    std::vector<uint8_t> line;   // the open line so far
+    uint64_t pos = 0, lines = 0, bytes = 0, hits = 0;
+    bool failed = false;
+    auto close_line = [&]() {
+        uint64_t h = 0;
+        const uint64_t len = line.size();
+        for (uint64_t p = 0; p + m <= len; p++) {
+            const uint8_t *at = (const uint8_t *)memchr(line.data() + p, pat[0], (size_t)(len - m + 1 - p));
+            if (!at) break;
+            p = (uint64_t)(at - line.data());
+            h += memcmp(at, pat, m) == 0;
+        }
+        if (h) {
+            hits += h;
+            lines++;
+            bytes += len;
+            if (fout && fwrite(line.data(), 1, (size_t)len, fout) != len) failed = true;
+        }
+        line.clear();
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        for (uint64_t p = 0; p < n;) {
+            const uint8_t *at = (const uint8_t *)memchr(plain + p, delim, (size_t)(n - p));
+            const uint64_t q = at ? (uint64_t)(at - plain) + 1 : n;   // the line's bytes in this record end here
+            line.insert(line.end(), plain + p, plain + q);
+            if (at) close_line();
+            p = q;
+        }
+        pos += n;
+        return !failed;
+    });
+    if (r) return r;
+    if (!line.empty()) close_line();   // the unterminated tail is a line
+    if (failed) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (stats) {
+        stats[0] = lines;
+        stats[1] = bytes;
+        stats[2] = hits;
+        stats[3] = pos;
+    }
+    return grep_totals(lines, bytes, hits, pos);
 }
 
 }  // namespace fcx_cli

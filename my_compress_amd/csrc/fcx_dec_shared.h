@@ -615,6 +615,84 @@ struct LinesScratch {
     uint64_t stats[FCX_LINES_CALL_STATS] = {};
 };
 
+// ---- status words of a grep (fcx_dctx's gp.words, u64 each; host_words mirrors them).  What travels from group
+// to group is in them, never bytes of the open line: positions are run-wide and stored as 1 + position ----
+constexpr uint32_t kGwJudged = 0;      // start positions judged (k_gscan)
+constexpr uint32_t kGwHits = 1;        // hits (k_gscan)
+constexpr uint32_t kGwLines = 2;       // selected lines so far: advanced by k_gbase, group by group
+constexpr uint32_t kGwGroupBase = 3;   // selected lines before the group scanned last (k_gbase)
+constexpr uint32_t kGwBytes = 4;       // sum of end - start over the selected lines whose end is known
+constexpr uint32_t kGwLast = 5;        // 1 + the position of the last delimiter seen (0: none): the open line's start
+constexpr uint32_t kGwLastHit = 6;     // 1 + the position of the last hit seen (0: none)
+constexpr uint32_t kGwOpen = 7;        // 1: the line open at the group's end is selected: the end of line kGwLines - 1 is to come
+constexpr uint32_t kGwClosed = 8;      // the end of the open line the group scanned last closed (0: it closed none)
+constexpr uint32_t kGwWords = 16;
+
+// where a grep leaves its lines: the first `cap` of the call at d_start / d_end (device, the shard form), or every
+// line through on_line in order (the stream form, by windows of fd.window lines)
+struct GrepSink {
+    uint64_t *d_start = nullptr, *d_end = nullptr;
+    uint64_t cap = 0;
+    fcx_range_fn on_line = nullptr;
+    void *user = nullptr;
+};
+// what the stream form keeps between its runs beside the context's words and carry: the decoded offset of the
+// next run's first byte, and the start of a selected line that is still open (reported once it closes)
+struct GrepCarry {
+    uint64_t base = 0;
+    bool held = false;
+    uint64_t held_start = 0;
+};
+// fcx_grep_shard behind its argument checks (fcx_grep.hip).  carry == nullptr: a whole run; the line open at its
+// end closes at its last byte.  With a carry the run continues the file of the runs before it (carry->base == 0
+// starts one), positions are file-wide, and the open line is left to the next run or to the caller.  stats: the
+// FCX_GREP_STATS values of the file so far; messages number the records from rec_base.
+int grep_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim, const uint8_t *pattern,
+             uint32_t plen, const GrepSink &sink, GrepCarry *carry, uint64_t *stats, hipStream_t st, uint64_t rec_base);
+
+// scratch of the grep (fcx_grep.hip); pattern and carry as the search's
+struct GrepScratch {
+    DevBuf<uint32_t> pat;
+    DevBuf<uint8_t> carry;
+    DevBuf<uint16_t> hit_bits;       // per tile of 4096 positions 512 B of hit bits (k_gmark: of first hits of a line) ...
+    DevBuf<uint16_t> delim_bits;     // ... and 512 B of delimiter bits
+    DevBuf<uint32_t> tile_sum;       // per tile 4 words: hits, 1 + first and 1 + last delimiter, 1 + last hit (in the range; 0: none)
+    DevBuf<uint64_t> tile_ctx;       // per tile 3 words: 1 + last delimiter and 1 + last hit before it, 1 + first delimiter behind it
+    DevBuf<uint32_t> tile_count;     // per tile its first hits, and ...
+    DevBuf<uint32_t> tile_base;      // ... those of the group's tiles before it
+    DevBuf<uint64_t> words;          // kGw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint64_t> win_start, win_end;   // the stream form's window
+    uint32_t carry_len = 0;
+    uint64_t scratch_bytes = 0;      // device bytes the last call reserved beside the decoded group (bitmaps and tile words)
+};
+
+// ---- status words of a multi-range decode (fcx_dctx's rq.words, u64 each; host_words mirrors them) ----
+constexpr uint32_t kQwSum = 0;        // bytes of all ranges (k_qchunks)
+constexpr uint32_t kQwBadIndex = 1;   // the first range that breaks a rule (k_qlen; preset ~0)
+constexpr uint32_t kQwTouched = 2;    // records touched (k_qtouch)
+constexpr uint32_t kQwSlice = 4;      // 4 words of the group in work (k_qslice): its ranges [ia, ib), its output span [o_lo, o_hi)
+constexpr uint32_t kQwWords = 8;
+
+// fcx_decompress_ranges_shard behind its argument checks (fcx_ranges.hip)
+int ranges_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint64_t *d_rec_off,
+               const uint64_t *d_dec_off, const uint64_t *d_start, const uint64_t *d_end, uint64_t nranges, uint8_t *d_out,
+               uint64_t cap, uint64_t *out_len, hipStream_t st);
+
+// scratch of the multi-range decode (fcx_ranges.hip); the host forms' device copies of a file and its ranges
+struct RangesScratch {
+    DevBuf<uint64_t> out_off;        // nranges + 1: the exclusive scan of the range lengths
+    DevBuf<uint64_t> chunk_sum;      // per chunk of 1024 ranges its bytes, then the bytes of the chunks before it
+    DevBuf<uint8_t> touched;         // per record: does a range hold a byte of it?
+    PinnedBuf<uint8_t> host_touched;
+    DevBuf<uint64_t> words;          // kQw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint8_t> file;            // the host forms: the records
+    DevBuf<uint64_t> starts, ends;   // ... and the ranges
+    DevBuf<uint8_t> out;
+    uint64_t stats[FCX_RANGES_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -648,6 +726,8 @@ struct fcx_dctx {
     fcx::DigestScratch dg;
     fcx::FindScratch fd;
     fcx::LinesScratch ln;
+    fcx::GrepScratch gp;
+    fcx::RangesScratch rq;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

@@ -1,7 +1,7 @@
 // fcx_ld16.h — what the kernels over record runs share (fcx_verify.hip, fcx_repair.hip, fcx_digest.hip,
-// fcx_find.hip, fcx_lines.hip; DESIGN.md §1a, "run core"): the bounded 16-byte read of a byte range that sits anywhere, a
-// block's length, the "no entry" mark of the entry map, and the tail of the two summary kernels.  Device
-// code only, and included by those five files alone: no compress-path or decoder object sees it.
+// fcx_find.hip, fcx_lines.hip, fcx_grep.hip, fcx_ranges.hip; DESIGN.md §1a, "run core"): the bounded 16-byte read of a
+// byte range that sits anywhere, a block's length, the "no entry" mark of the entry map, and the tail of the two
+// summary kernels.  Device code only, and included by those files alone: no compress-path or decoder object sees it.
 #ifndef FCX_LD16_H
 #define FCX_LD16_H
 

@@ -928,6 +928,87 @@ int fcx_lines_of_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, uint8_
     return fcx_lines_of_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, delim, offsets, noff, lines);
 }
 
+// ---- the grep's and the multi-range decode's stream forms (include/fcx.h) ------------
+
+int fcx_grep_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, const uint8_t *pattern,
+                    uint32_t plen, fcx_range_fn on_line, void *user_line, uint64_t *stats) {
+    if (!dctx || !rd || !pattern) return fail(FCX_ERR_ARG, "fcx_grep_stream: NULL argument");
+    if (plen < 1 || plen > FCX_FIND_MAX_PATTERN)
+        return fail(FCX_ERR_ARG, "fcx_grep_stream: pattern length outside [1, FCX_FIND_MAX_PATTERN]");
+    if (memchr(pattern, delim, plen)) return fail(FCX_ERR_ARG, "fcx_grep_stream: the pattern holds the delimiter");
+    GrepSink sink;
+    sink.on_line = on_line;
+    sink.user = user_line;
+    GrepCarry carry;
+    uint64_t gs[FCX_GREP_STATS] = {};
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        return fcx::grep_run(dctx, lz78 ? '8' : '7', x.din, used, nb, delim, pattern, plen, sink, &carry, gs, st, before);
+    });
+    if (r) return r;
+    if (carry.held) {   // the file ends inside a selected line
+        if (on_line) on_line(user_line, carry.held_start, carry.base);
+        carry.held = false;
+    }
+    // (the bytes of a line still open at the end: the words hold its start, with or without a callback)
+    if (gs[0] && dctx->gp.host_words && dctx->gp.host_words[kGwOpen]) gs[1] += carry.base - dctx->gp.host_words[kGwLast];
+    gs[4] = carry.base;
+    for (int i = 0; i < FCX_GREP_STATS && stats; i++) stats[i] = gs[i];
+    return FCX_OK;
+}
+
+int fcx_decompress_ranges_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
+                                 const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *out_len) {
+    if (!dctx || !rd || !wr || (n && (!starts || !ends))) return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: NULL argument");
+    for (uint64_t i = 0; i < n; i++)
+        if (starts[i] > ends[i] || (i && ends[i - 1] > starts[i]))
+            return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: range " + std::to_string(i) +
+                                         " breaks start <= end or starts in front of the end of the range before it");
+    if (out_len) *out_len = 0;
+    if (n == 0) return FCX_OK;         // nothing to decode: nothing is read
+    uint64_t done = 0;                 // ranges that lie wholly in front of the groups still to come
+    uint64_t pos = 0, tout = 0;        // decoded bytes before the group, bytes written
+    std::vector<uint64_t> gs, ge;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t, hipStream_t st) -> int {
+        const char kind = lz78 ? '8' : '7';
+        RangeScratch &R = dctx->rg;
+        RangesScratch &Q = dctx->rq;
+        FCX_TRY(R.rec_off.reserve(8ull * nb + 8, "index"));
+        FCX_TRY(R.dec_off.reserve(8ull * nb + 8, "index"));
+        uint64_t gtotal = 0;
+        FCX_TRY(fcx_index_shard(dctx, kind, x.din, used, nb, R.rec_off, R.dec_off, &gtotal, st));
+        const uint64_t hi = pos + gtotal;
+        // the slice of the ranges that meets [pos, hi), clipped to it and counted from the group's first byte
+        gs.clear();
+        ge.clear();
+        for (uint64_t i = done; i < n && starts[i] < hi; i++) {
+            const uint64_t s = std::max(starts[i], pos), e = std::min(ends[i], hi);
+            if (s < e) {
+                gs.push_back(s - pos);
+                ge.push_back(e - pos);
+            }
+        }
+        while (done < n && ends[done] <= hi) done++;
+        pos = hi;
+        if (!gs.empty()) {
+            FCX_TRY(Q.starts.reserve(8 * gs.size(), "ranges"));
+            FCX_TRY(Q.ends.reserve(8 * gs.size(), "ranges"));
+            FCX_HIP(hipMemcpyAsync(Q.starts, gs.data(), 8 * gs.size(), hipMemcpyHostToDevice, st));
+            FCX_HIP(hipMemcpyAsync(Q.ends, ge.data(), 8 * ge.size(), hipMemcpyHostToDevice, st));
+            uint64_t got = 0;
+            FCX_TRY(fcx::ranges_run(dctx, kind, x.din, used, nb, R.rec_off, R.dec_off, Q.starts, Q.ends, gs.size(), x.dout, out_cap, &got, st));
+            if (got) FCX_TRY(write_group(x, got, wr, user, st, &tout));
+        }
+        return done == n ? kStopReading : FCX_OK;
+    });
+    if (r) return r;
+    if (out_len) *out_len = tout;
+    if (done < n)
+        return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: range " + std::to_string(done) + " ends behind the file's end");
+    return FCX_OK;
+}
+
 int fcx_digest_stream(fcx_dctx *c, fcx_read_fn rd, void *user, uint32_t block_bytes, fcx_write_fn wr, void *user_wr,
                       uint64_t *stats) {
     if (!c || !rd || !wr) return fail(FCX_ERR_ARG, "fcx_digest_stream: NULL argument");
