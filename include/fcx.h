@@ -776,6 +776,68 @@ int fcx_decompress_ranges_stream(fcx_dctx *ctx, fcx_read_fn read_comp, fcx_write
 int fcx_decompress_ranges_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *starts, const uint64_t *ends,
                                uint64_t nranges, uint8_t *out, uint64_t cap, uint64_t *out_len);
 
+/* ---- pattern sets: many patterns and ASCII case folding in one scan (FCX7 and FCX8) -------------------------
+ * D, T, the delimiter d and the lines s_j / e_j are those of the search, the line calls and the grep above.
+ * A set holds npat patterns pat_k of len_k bytes.  fold(b) = b + 0x20 for 0x41 <= b <= 0x5A and b otherwise
+ * with FCX_SET_FOLD_ASCII (bytes >= 0x80 are never folded), the identity without it.  Pattern k occurs at p iff
+ * p + len_k <= T and fold(D[p + i]) == fold(pat_k[i]) for all i < len_k.  A hit is a position p at which at
+ * least one pattern occurs; hits are reported ascending, each position once however many patterns occur
+ * there.  counts[k] (host, npat values, may be NULL) is the number of positions at which pattern k occurs,
+ * over the whole run whatever cap is, so sum(counts) >= hits; duplicates and prefixes of one another are
+ * allowed and each counts for itself.  Positions judged after a whole run = max(T - min_len + 1, 0): no
+ * position is judged twice or skipped.  Grep: line j is selected iff a hit p has s_j <= p < e_j; a pattern
+ * that holds d, or with the flag a folded pattern that holds fold(d), is FCX_ERR_ARG (`a` against the
+ * delimiter `A` would match across a line end).  A set of one pattern without the flag gives exactly
+ * fcx_find_shard's and fcx_grep_shard's hits, lines and judged positions.
+ * How a run is scanned: every record group is scanned behind the last min(max_len - 1, bytes seen) bytes; a
+ * group that is not the run's last judges the positions p with p + max_len <= group end against all
+ * patterns, the last max_len - 1 positions wait for the next group, and at the run's end they are judged
+ * with pattern k admitted iff p + len_k <= T (the stream forms: a final pass over the carry alone once the
+ * reader has ended). */
+#define FCX_SET_MAX_PATTERNS 64u
+#define FCX_SET_MAX_BYTES    4096u      /* sum of the lengths */
+#define FCX_SET_FOLD_ASCII   1u         /* flags */
+#define FCX_SET_SCAN_STATS   6          /* judged, candidate positions, full compares, hits, groups, final passes */
+typedef struct fcx_pattern_set fcx_pattern_set;
+/* Compiles npat patterns (bytes: their concatenation, lens[k] in [1, FCX_FIND_MAX_PATTERN], npat in
+ * [1, FCX_SET_MAX_PATTERNS], sum of the lengths <= FCX_SET_MAX_BYTES) into what the scan kernel reads: the
+ * folded pattern bytes padded to dwords, their offsets and lengths, the two filter tables.  Pure host code:
+ * no device is touched.  FCX_ERR_ARG for NULL arguments, npat, a length or the sum out of range, unknown
+ * flag bits. */
+int fcx_pattern_set_create(fcx_pattern_set **set, const uint8_t *bytes, const uint32_t *lens, uint32_t npat, uint32_t flags);
+void fcx_pattern_set_destroy(fcx_pattern_set *set);
+/* any of the outputs may be NULL */
+int fcx_pattern_set_info(const fcx_pattern_set *set, uint32_t *npat, uint32_t *min_len, uint32_t *max_len, uint32_t *flags);
+/* fcx_find_shard / fcx_find_stream / fcx_find_host for a set: the same arguments, checks, cap rule, windows
+ * (fcx_dctx_set_find_window) and stage table, with `set` in the place of (pattern, plen) and counts behind
+ * nhits / stats.  nblocks == 0 gives zeros and touches no device.  Scratch is the search's own plus the set's
+ * device copy (8.7 KB) and 64 counters: it does not grow with hits or patterns. */
+int fcx_find_set_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                       const fcx_pattern_set *set, uint64_t *d_hits, uint64_t cap, uint64_t *nhits, uint64_t *counts,
+                       void *stream);
+int fcx_find_set_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, const fcx_pattern_set *set,
+                        fcx_hit_fn on_hit, void *user_cb, uint64_t *stats, uint64_t *counts);
+int fcx_find_set_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const fcx_pattern_set *set, uint64_t *hits,
+                      uint64_t cap, uint64_t *nhits, uint64_t *counts);
+/* fcx_grep_shard / fcx_grep_stream / fcx_grep_host for a set: stats are FCX_GREP_STATS values with stats[3],
+ * the positions judged, max(T - min_len + 1, 0); the held-back open line, the windows and the chaining into
+ * fcx_decompress_ranges_shard are the one-pattern calls'.  FCX_ERR_ARG also when a pattern holds delim or,
+ * with FCX_SET_FOLD_ASCII, a folded pattern holds fold(delim). */
+int fcx_grep_set_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                       const fcx_pattern_set *set, uint64_t *d_start, uint64_t *d_end, uint64_t cap, uint64_t *stats,
+                       uint64_t *counts, void *stream);
+int fcx_grep_set_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim,
+                        const fcx_pattern_set *set, fcx_range_fn on_line, void *user_line, uint64_t *stats, uint64_t *counts);
+int fcx_grep_set_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, const fcx_pattern_set *set,
+                      uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats, uint64_t *counts);
+/* Counters of the last set call on the context, summed over its groups (the stream and host forms: over the
+ * file), min(n, FCX_SET_SCAN_STATS) values: positions judged; of those, positions whose candidate mask
+ * T0[b0] & T1[b1] was not zero; (position, pattern) pairs of more than two bytes taken to the full compare;
+ * hits; groups scanned; final passes run: 1 after every call that had records, in the shard forms the scan of the
+ * last group and in the stream and host forms the pass behind the last group, which scans nothing when no
+ * position is left (max_len == 1, or nothing was decoded); 0 after a call without records. */
+int fcx_dctx_set_scan_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -215,6 +215,24 @@ def lib():
                                       RANGE_FN, ctypes.c_void_p, P64]
         L.fcx_decompress_ranges_stream.argtypes = [ctypes.c_void_p, READ_FN, WRITE_FN, ctypes.c_void_p, ctypes.c_uint64, P64, P64,
                                                    ctypes.c_uint64, P64]
+    if hasattr(L, "fcx_pattern_set_create"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]
+        P32 = ctypes.POINTER(ctypes.c_uint32)
+        L.fcx_pattern_set_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), c_u8p, P32, ctypes.c_uint32, ctypes.c_uint32]
+        L.fcx_pattern_set_destroy.argtypes = [ctypes.c_void_p]
+        L.fcx_pattern_set_destroy.restype = None
+        L.fcx_pattern_set_info.argtypes = [ctypes.c_void_p, P32, P32, P32, P32]
+        L.fcx_find_set_shard.argtypes = run + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, P64, P64, ctypes.c_void_p]
+        L.fcx_find_set_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, HIT_FN,
+                                          ctypes.c_void_p, P64, P64]
+        L.fcx_find_set_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_void_p, P64, ctypes.c_uint64, P64, P64]
+        L.fcx_grep_set_shard.argtypes = run + [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, P64,
+                                               P64, ctypes.c_void_p]
+        L.fcx_grep_set_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p,
+                                          RANGE_FN, ctypes.c_void_p, P64, P64]
+        L.fcx_grep_set_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, c_u8p, ctypes.c_uint64,
+                                        P64, P64, P64]
+        L.fcx_dctx_set_scan_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -916,6 +934,90 @@ class DContext:
                "fcx_decompress_ranges_stream")
         return int(got.value)
 
+    # ---- pattern sets (fcx_*_set_*): up to 64 patterns, with or without ASCII case folding, in one scan ----
+    SET_SCAN_STATS = ("judged", "candidates", "compares", "hits", "groups", "final_passes")
+
+    def find_set_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, pset: "PatternSet", d_hits: int = 0, cap: int = 0,
+                       stream: int = 0):
+        """searches device records (no header) for the patterns of `pset`; returns (hits, counts): the positions at
+        which at least one occurs and, per pattern, the positions at which it does; the first min(cap, hits) offsets
+        go to d_hits (u64 on the device), ascending, each once"""
+        n = ctypes.c_uint64(0)
+        counts = (ctypes.c_uint64 * len(pset))()
+        _check(lib().fcx_find_set_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, pset.handle,
+                                        ctypes.c_void_p(d_hits or None), cap, ctypes.byref(n), counts, ctypes.c_void_p(stream)),
+               "fcx_find_set_shard")
+        return int(n.value), [int(v) for v in counts]
+
+    def find_set(self, blob: bytes, pset: "PatternSet", max_hits: int = None):
+        """a whole FCX7 or FCX8 file in memory -> (count, [offsets], counts): every offset of the decoded file at which
+        a pattern of `pset` occurs, ascending, the first max_hits of them when that is given (0: the counts alone)"""
+        n = ctypes.c_uint64(0)
+        counts = (ctypes.c_uint64 * len(pset))()
+        if not max_hits:
+            _check(lib().fcx_find_set_host(self._h, blob, len(blob), pset.handle, None, 0, ctypes.byref(n), counts), "fcx_find_set_host")
+            if max_hits == 0 or n.value == 0:
+                return int(n.value), [], [int(v) for v in counts]
+            max_hits = int(n.value)
+        out = (ctypes.c_uint64 * max_hits)()
+        _check(lib().fcx_find_set_host(self._h, blob, len(blob), pset.handle, out, max_hits, ctypes.byref(n), counts), "fcx_find_set_host")
+        return int(n.value), [int(v) for v in out[:min(max_hits, int(n.value))]], [int(v) for v in counts]
+
+    def find_set_stream(self, src, pset: "PatternSet", max_in: int = 0, want_hits: bool = True):
+        """an FCX7 or FCX8 file from src (binary reader) -> ({hits, decoded, records, judged}, [offsets], counts)"""
+        rd, _ = _stream_fns(src, None)
+        got = []
+        cb = HIT_FN(lambda _u, off: got.append(int(off))) if want_hits else ctypes.cast(None, HIT_FN)
+        vals = (ctypes.c_uint64 * 4)()
+        counts = (ctypes.c_uint64 * len(pset))()
+        _check(lib().fcx_find_set_stream(self._h, rd, None, max_in, pset.handle, cb, None, vals, counts), "fcx_find_set_stream")
+        return dict(zip(("hits", "decoded", "records", "judged"), [int(v) for v in vals])), got, [int(v) for v in counts]
+
+    def grep_set_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, pset: "PatternSet", delim=b"\n", d_start: int = 0,
+                       d_end: int = 0, cap: int = 0, stream: int = 0):
+        """the lines of device records (no header) that hold a pattern of `pset`: returns ({lines, bytes, hits, judged,
+        decoded}, counts); start and end of the first min(cap, lines) go to d_start / d_end (u64 on the device)"""
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        _check(lib().fcx_grep_set_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, self._delim(delim),
+                                        pset.handle, ctypes.c_void_p(d_start or None), ctypes.c_void_p(d_end or None), cap, vals, counts,
+                                        ctypes.c_void_p(stream)), "fcx_grep_set_shard")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals])), [int(v) for v in counts]
+
+    def grep_set_host(self, blob: bytes, pset: "PatternSet", delim=b"\n"):
+        """a whole FCX7 or FCX8 file in memory -> (stats, the bytes of the lines that hold a pattern of `pset`, counts):
+        grep -F -f; the lines are found and gathered on the GPU, only their bytes come back"""
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        need = ctypes.c_uint64(0)
+        args = (self._h, blob, len(blob), self._delim(delim), pset.handle)
+        rc = lib().fcx_grep_set_host(*args, None, 0, ctypes.byref(need), vals, counts)   # the size
+        if rc != -2:
+            _check(rc, "fcx_grep_set_host")
+            return dict(zip(self.GREP_STATS, [int(v) for v in vals])), b"", [int(v) for v in counts]
+        out = ctypes.create_string_buffer(need.value)
+        _check(lib().fcx_grep_set_host(*args, out, need.value, ctypes.byref(need), vals, counts), "fcx_grep_set_host")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals])), out.raw[:need.value], [int(v) for v in counts]
+
+    def grep_set_stream(self, src, pset: "PatternSet", delim=b"\n", max_in: int = 0, want_lines: bool = True):
+        """an FCX7 or FCX8 file from src (binary reader) -> (stats, [(start, end)] of every line that holds a pattern of
+        `pset`, ascending, each once and with its true end, counts); want_lines False: the totals alone"""
+        rd, _ = _stream_fns(src, None)
+        got = []
+        cb = RANGE_FN(lambda _u, s, e: got.append((int(s), int(e)))) if want_lines else ctypes.cast(None, RANGE_FN)
+        vals = (ctypes.c_uint64 * len(self.GREP_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        _check(lib().fcx_grep_set_stream(self._h, rd, None, max_in, self._delim(delim), pset.handle, cb, None, vals, counts),
+               "fcx_grep_set_stream")
+        return dict(zip(self.GREP_STATS, [int(v) for v in vals])), got, [int(v) for v in counts]
+
+    def set_scan_stats(self) -> dict:
+        """counters of the last pattern-set call (fcx_dctx_set_scan_stats)"""
+        n = len(self.SET_SCAN_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_set_scan_stats(self._h, vals, n), "fcx_dctx_set_scan_stats")
+        return dict(zip(self.SET_SCAN_STATS, [int(v) for v in vals]))
+
     # ---- lines (fcx_lines_*): count, locate, decode and number the lines of the decoded run; lines are 0-based,
     # delim is one byte, count None means "to the end" ----
     LINES_STATS = ("delimiters", "lines", "decoded", "tail_bytes")
@@ -1129,6 +1231,78 @@ def find(blob: bytes, pattern: bytes, max_hits: int = None, device: int = 0):
         return ctx.find(blob, pattern, max_hits)
     finally:
         ctx.close()
+
+
+class PatternSet:
+    """up to 64 byte patterns of 1 to 256 bytes (4096 in all) compiled for the set calls (fcx_pattern_set_create);
+    ignore_case folds A to Z, and nothing else, in patterns and text"""
+    FOLD_ASCII = 1
+
+    def __init__(self, patterns, ignore_case: bool = False, flags: int = None):
+        pats = [bytes(p) for p in patterns]
+        lens = (ctypes.c_uint32 * max(len(pats), 1))(*[len(p) for p in pats])
+        h = ctypes.c_void_p()
+        self._h = None
+        _check(lib().fcx_pattern_set_create(ctypes.byref(h), b"".join(pats) or b"\0", lens, len(pats),
+                                            (self.FOLD_ASCII if ignore_case else 0) if flags is None else flags),
+               "fcx_pattern_set_create")
+        self._h = h
+        self._n = len(pats)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return self._n
+
+    def info(self) -> dict:
+        v = [ctypes.c_uint32(0) for _ in range(4)]
+        _check(lib().fcx_pattern_set_info(self._h, *[ctypes.byref(x) for x in v]), "fcx_pattern_set_info")
+        return dict(zip(("npat", "min_len", "max_len", "flags"), [int(x.value) for x in v]))
+
+    def close(self):
+        if self._h:
+            lib().fcx_pattern_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def find_any(blob: bytes, patterns, ignore_case: bool = False, max_hits: int = None, device: int = 0):
+    """(hits, counts): the offsets of what `blob` (FCX7 or FCX8) decodes to at which at least one of `patterns` occurs,
+    ascending and each once (the first max_hits when given), and per pattern the number of positions at which it
+    occurs; one scan on the GPU whatever the number of patterns"""
+    ps = PatternSet(patterns, ignore_case)
+    try:
+        _n, hits, counts = _with_dctx(device, lambda c: c.find_set(blob, ps, max_hits))
+        return hits, counts
+    finally:
+        ps.close()
+
+
+def grep_any(blob: bytes, patterns, delim=b"\n", ignore_case: bool = False, device: int = 0) -> bytes:
+    """the lines of what `blob` decodes to that hold at least one of `patterns`, each once, in order: grep -F -f (-i)"""
+    ps = PatternSet(patterns, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_set_host(blob, ps, delim)[1])
+    finally:
+        ps.close()
+
+
+def grep_any_ranges(blob: bytes, patterns, delim=b"\n", ignore_case: bool = False, device: int = 0):
+    """(stats, [(start, end)], counts) of the lines grep_any() returns, through the stream form"""
+    import io
+
+    ps = PatternSet(patterns, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_set_stream(io.BytesIO(blob), ps, delim, max(0, len(blob) - HEADER_BYTES)))
+    finally:
+        ps.close()
 
 
 def _with_dctx(device, fn):

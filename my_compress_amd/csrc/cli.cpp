@@ -71,6 +71,20 @@
 // The last line printed is "grep: L lines, B bytes, H hits, decoded bytes = T".  Usage errors: --grep or --grep-hex with
 // -c, --range, --list, --compare, --verify, --repair, --digest, --test, --find, --find-hex, --count-lines, --lines,
 // --line-numbers or each other; a pattern that holds the delimiter; an empty or over-long pattern.
+//
+// Pattern sets, decompress mode only (fcx_find_set_stream / fcx_grep_set_stream: up to 64 patterns in one scan):
+//   --find-set FILE   --find for every pattern of FILE: patterns are separated by 0x0A, one trailing 0x0A is allowed;
+//                     an offset is printed once however many patterns occur there
+//   --grep-set FILE   --grep for every pattern of FILE (grep -F -f): a line is written once
+//   --set-hex         every line of FILE is an even number of hex digits
+//   --ignore-case     A to Z match a to z and the other way round, nothing else folds (grep -i for ASCII); also with
+//                     --find, --find-hex, --grep, --grep-hex, which then run as a set of one
+//   --count, --delim  as with --find and --grep
+// The totals lines end with ", patterns: P".  Usage errors: an empty pattern line (grep -f would match every line), more
+// than 64 patterns, a pattern over 256 bytes, over 4096 bytes in all, bad hex, an unreadable FILE; both set options; a
+// set option with --find, --find-hex, --grep or --grep-hex; --set-hex without a set; --ignore-case without a search;
+// any of them with --line-numbers; for a grep a pattern that holds the delimiter or, with --ignore-case, that holds it
+// after folding both; and whatever is a usage error with --find or --grep.
 // Without a HIP device an FCX7 file is cut into lines on the host decoder, with the same bytes and last line; FCX8 fails.
 #include <getopt.h>
 
@@ -78,6 +92,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -97,7 +112,9 @@ static int usage() {
             "[--find <string> | --find-hex <hex digits> [--count | --line-numbers] (decompress only: search the decoded bytes)] "
             "[--count-lines | --lines <first line>:[<count>] (decompress only: the lines of the decoded bytes)] "
             "[--grep <string> | --grep-hex <hex digits> [--count] (decompress only: the lines that hold the bytes, to -o)] "
-            "[--delim <two hex digits> (the line delimiter, default 0a)]\n");
+            "[--delim <two hex digits> (the line delimiter, default 0a)] "
+            "[--find-set <pattern file> | --grep-set <pattern file> [--set-hex] [--count] (decompress only: up to 64 patterns, one a line)] "
+            "[--ignore-case (with a search: ASCII letters match in either case)]\n");
     return -1;
 }
 
@@ -687,6 +704,101 @@ static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t>
     return fcx_cli::grep_totals(stats[0], stats[1], stats[2], stats[4]);
 }
 
+// --find-set, or --find with --ignore-case: do_find for a pattern set
+// (set: the library's, through its public calls alone; host_set: the command line's own compilation of the same
+// patterns for the no-device path, fcx_patset.h)
+static int do_find_set(FILE *fin, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, bool count_only) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_find_set(fin, nblocks, host_set, count_only, nullptr, nullptr);
+    }
+    uint64_t max_in = 0, stats[4] = {};
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    const fcx_hit_fn line = [](void *, uint64_t off) { fcx_cli::find_line(off); };
+    uint32_t npat = 0;
+    int r = fcx_pattern_set_info(set, &npat, nullptr, nullptr, nullptr);
+    if (r == FCX_OK) r = fcx_find_set_stream(d, file_read, fin, max_in, set, count_only ? nullptr : line, nullptr, stats, nullptr);
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::find_set_totals(stats[0], stats[1], npat);
+}
+
+// --grep-set, or --grep with --ignore-case: do_grep for a pattern set
+static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, uint8_t delim) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_grep_set(fin, nblocks, delim, host_set, fout, nullptr, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_GREP_STATS] = {}, got = 0;
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    struct Lines {
+        std::vector<uint64_t> starts, ends;
+    } lines;
+    const fcx_range_fn keep = [](void *u, uint64_t s, uint64_t e) {
+        ((Lines *)u)->starts.push_back(s);
+        ((Lines *)u)->ends.push_back(e);
+    };
+    uint32_t npat = 0;
+    int r = fcx_pattern_set_info(set, &npat, nullptr, nullptr, nullptr);
+    if (r == FCX_OK) r = fcx_grep_set_stream(d, file_read, fin, max_in, delim, set, fout ? keep : nullptr, &lines, stats, nullptr);
+    if (r == FCX_OK && fout && !lines.starts.empty()) {
+        rewind(fin);
+        Files io{fin, fout};
+        r = fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
+                                         lines.starts.size(), &got);
+        if (r == FCX_OK && got != stats[1]) {
+            fprintf(stderr, "fcx: the lines' bytes disagree with the grep's sum\n");
+            fcx_dctx_destroy(d);
+            return -1;
+        }
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::grep_set_totals(stats[0], stats[1], stats[2], stats[4], npat);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -776,6 +888,10 @@ int main(int argc, char **argv) {
                                            {"delim", required_argument, nullptr, 'M'},
                                            {"grep", required_argument, nullptr, 'G'},
                                            {"grep-hex", required_argument, nullptr, 'H'},
+                                           {"find-set", required_argument, nullptr, 1001},
+                                           {"grep-set", required_argument, nullptr, 1002},
+                                           {"set-hex", no_argument, nullptr, 1003},
+                                           {"ignore-case", no_argument, nullptr, 1004},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -792,6 +908,8 @@ int main(int argc, char **argv) {
     bool count_lines = false, lines = false, line_numbers = false, delim_given = false;
     uint64_t line_first = 0, line_count = 0;
     uint8_t delim = 0x0A;
+    std::string find_set, grep_set;
+    bool set_hex = false, ignore_case = false;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -844,10 +962,42 @@ int main(int argc, char **argv) {
             if (!fcx_cli::parse_delim(optarg, &delim)) return usage();
             delim_given = true;
             break;
+        case 1001: find_set = optarg; break;
+        case 1002: grep_set = optarg; break;
+        case 1003: set_hex = true; break;
+        case 1004: ignore_case = true; break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
+    // the set options: a set file stands for --find or --grep in every rule below
+    const bool set_file = !find_set.empty() || !grep_set.empty();
+    if ((!find_set.empty() && !grep_set.empty()) || (set_file && (finds || greps)) || (set_hex && !set_file)) return usage();
+    if (ignore_case && !(finds || greps || set_file)) return usage();
+    if ((set_file || ignore_case) && line_numbers) return usage();
+    // the library's set, destroyed when main returns, and the command line's own compilation of the same patterns:
+    // the delimiter rule and the no-device path read that one, never the library's object
+    std::unique_ptr<fcx_pattern_set, void (*)(fcx_pattern_set *)> pset_own(nullptr, fcx_pattern_set_destroy);
+    std::unique_ptr<fcx_pattern_set> host_set;
+    fcx_pattern_set *pset = nullptr;
+    if (set_file || ignore_case) {
+        std::vector<uint8_t> sbytes;
+        std::vector<uint32_t> slens;
+        if (set_file) {
+            if (!fcx_cli::load_patterns((find_set.empty() ? grep_set : find_set).c_str(), set_hex, &sbytes, &slens)) return usage();
+        } else {
+            sbytes = finds ? pattern : grep_pattern;
+            slens.push_back((uint32_t)sbytes.size());
+        }
+        const uint32_t sflags = ignore_case ? FCX_SET_FOLD_ASCII : 0u;
+        host_set.reset(new fcx_pattern_set());
+        if (fcx::patset_compile(host_set.get(), sbytes.data(), slens.data(), (uint32_t)slens.size(), sflags)) return usage();
+        if (fcx_pattern_set_create(&pset, sbytes.data(), slens.data(), (uint32_t)slens.size(), sflags)) return usage();
+        pset_own.reset(pset);
+        finds += !find_set.empty();
+        greps += !grep_set.empty();
+        if (greps && (host_set->holds(delim) || (ignore_case && host_set->holds(fcx::fold_ascii(delim))))) return usage();
+    }
     if ((want.range || want.list) && (compress || (want.range && want.list))) return usage();
     if ((compare && (compress || want.range || want.list || verify)) || (verify && !compress)) return usage();
     if (!repair.empty() && (want.range || want.list)) return usage();
@@ -879,12 +1029,14 @@ int main(int argc, char **argv) {
         return -1;
     }
     if (finds) {
-        const int r = line_numbers ? do_find_numbered(fin, device, pattern, delim) : do_find(fin, device, pattern, count_only);
+        const int r = pset           ? do_find_set(fin, device, pset, *host_set, count_only)
+                      : line_numbers ? do_find_numbered(fin, device, pattern, delim)
+                                     : do_find(fin, device, pattern, count_only);
         fclose(fin);
         return r;
     }
     if (greps) {
-        const int r = do_grep(fin, fout, device, grep_pattern, delim);
+        const int r = pset ? do_grep_set(fin, fout, device, pset, *host_set, delim) : do_grep(fin, fout, device, grep_pattern, delim);
         fclose(fin);
         if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;

@@ -1,9 +1,9 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
 // (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest, --find,
-// --count-lines, --lines and --grep.  Host code
+// --count-lines, --lines, --grep, --find-set and --grep-set.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
-// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp).
+// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -11,11 +11,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "fcx.h"
 #include "fcx_crc32.h"
 #include "fcx_digest_file.h"
+#include "fcx_patset.h"
 #include "fcx_repair_file.h"
 
 namespace fcx_cli {
@@ -620,6 +622,155 @@ inline int host_grep(FILE *fin, uint16_t nblocks, uint8_t delim, const uint8_t *
         stats[3] = pos;
     }
     return grep_totals(lines, bytes, hits, pos);
+}
+
+// ---- --find-set / --grep-set / --ignore-case: the pattern file, the printout and the host paths ----
+inline int find_set_totals(uint64_t hits, uint64_t decoded, uint32_t npat) {
+    printf("find: %llu hits, decoded bytes = %llu, patterns: %u\n", (unsigned long long)hits, (unsigned long long)decoded, npat);
+    return 0;
+}
+inline int grep_set_totals(uint64_t lines, uint64_t bytes, uint64_t hits, uint64_t decoded, uint32_t npat) {
+    printf("grep: %llu lines, %llu bytes, %llu hits, decoded bytes = %llu, patterns: %u\n", (unsigned long long)lines,
+           (unsigned long long)bytes, (unsigned long long)hits, (unsigned long long)decoded, npat);
+    return 0;
+}
+
+// The patterns of a pattern file's bytes: separated by 0x0A, one trailing 0x0A allowed; hex: every line is an even
+// number of hex digits.  bytes: their concatenation, lens: their lengths.  False for an empty pattern (grep -f
+// would match every line there), more than FCX_SET_MAX_PATTERNS patterns, a pattern of more than
+// FCX_FIND_MAX_PATTERN bytes, more than FCX_SET_MAX_BYTES in all, bad hex, or no pattern at all.
+inline bool parse_patterns(const uint8_t *text, uint64_t n, bool hex, std::vector<uint8_t> *bytes, std::vector<uint32_t> *lens) {
+    bytes->clear();
+    lens->clear();
+    if (n && text[n - 1] == 0x0A) n--;
+    if (n == 0) return false;
+    for (uint64_t p = 0; p <= n;) {
+        const uint8_t *at = p < n ? (const uint8_t *)memchr(text + p, 0x0A, (size_t)(n - p)) : nullptr;
+        const uint64_t q = at ? (uint64_t)(at - text) : n;
+        std::vector<uint8_t> pat(text + p, text + q);
+        if (hex) {
+            const std::string digits(pat.begin(), pat.end());
+            if (digits.find('\0') != std::string::npos || !parse_hex(digits.c_str(), &pat)) return false;
+        }
+        if (pat.empty() || pat.size() > FCX_FIND_MAX_PATTERN || lens->size() == FCX_SET_MAX_PATTERNS) return false;
+        bytes->insert(bytes->end(), pat.begin(), pat.end());
+        lens->push_back((uint32_t)pat.size());
+        if (bytes->size() > FCX_SET_MAX_BYTES) return false;
+        p = q + 1;
+    }
+    return true;
+}
+inline bool load_patterns(const char *path, bool hex, std::vector<uint8_t> *bytes, std::vector<uint32_t> *lens) {
+    FILE *f = fopen(path, "rb");
+    if (!f) return false;
+    std::vector<uint8_t> text;
+    uint8_t buf[4096];
+    for (size_t g; (g = fread(buf, 1, sizeof(buf), f)) > 0 && text.size() <= 4 * FCX_SET_MAX_BYTES + 4096;) text.insert(text.end(), buf, buf + g);
+    fclose(f);
+    return parse_patterns(text.data(), text.size(), hex, bytes, lens);
+}
+
+// the patterns of the set that occur at win[p] and end at or in front of `end`: bit k per pattern (win: folded bytes)
+inline uint64_t set_occurs(const fcx_pattern_set &S, const uint8_t *win, uint64_t p, uint64_t end) {
+    uint64_t mk = ((const uint64_t *)(S.block + fcx::kPsT0))[win[p]], got = 0;
+    for (; mk; mk &= mk - 1) {
+        const uint32_t k = (uint32_t)__builtin_ctzll(mk);
+        if (p + S.len[k] <= end && memcmp(win + p, S.pat(k), S.len[k]) == 0) got |= 1ull << k;
+    }
+    return got;
+}
+
+// --find-set without a device: every FCX7 record through the host decoder, folded when the set folds, searched
+// behind a rolling tail of the last M - 1 decoded bytes (M the longest pattern): a record's scan judges the
+// positions every pattern fits behind, the file's end the rest with each pattern bounded by it.  One line per hit
+// unless count_only, then the totals.  stats (2 values, may be null): hits, decoded bytes; counts (may be null):
+// per pattern the positions at which it occurs.
+inline int host_find_set(FILE *fin, uint16_t nblocks, const fcx_pattern_set &S, bool count_only, uint64_t *stats, uint64_t *counts) {
+    std::vector<uint8_t> win;   // [tail | record], folded
+    std::vector<uint64_t> per(S.npat, 0);
+    uint64_t pos = 0, hits = 0, tail = 0;
+    const uint64_t M = S.max_len;
+    auto judge = [&](uint64_t p0, uint64_t p1, uint64_t first) {
+        for (uint64_t p = p0; p < p1; p++) {
+            const uint64_t got = set_occurs(S, win.data(), p, win.size());
+            if (!got) continue;
+            for (uint64_t g = got; g; g &= g - 1) per[__builtin_ctzll(g)]++;
+            if (!count_only) find_line(first + p);
+            hits++;
+        }
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        win.resize(tail);
+        for (uint64_t i = 0; i < n; i++) win.push_back(S.fold(plain[i]));
+        const uint64_t len = win.size();
+        judge(0, len >= M ? len - M + 1 : 0, pos - tail);
+        pos += n;
+        tail = len < M - 1 ? len : M - 1;
+        win.erase(win.begin(), win.end() - (ptrdiff_t)tail);
+        return true;
+    });
+    if (r) return r;
+    judge(0, win.size(), pos - win.size());   // the positions the last record carried, each pattern bounded by the end
+    if (stats) {
+        stats[0] = hits;
+        stats[1] = pos;
+    }
+    for (uint32_t k = 0; k < S.npat && counts; k++) counts[k] = per[k];
+    return find_set_totals(hits, pos, S.npat);
+}
+
+// --grep-set without a device: host_grep with a set: the open line is buffered, raw for the output and folded for
+// the search; a line is searched once, when it closes or the file ends.  stats (4 values, may be null): lines,
+// bytes, hits, decoded bytes; counts as host_find_set's.
+inline int host_grep_set(FILE *fin, uint16_t nblocks, uint8_t delim, const fcx_pattern_set &S, FILE *fout, uint64_t *stats,
+                         uint64_t *counts) {
+    std::vector<uint8_t> line, folded;   // the open line so far
+    std::vector<uint64_t> per(S.npat, 0);
+    uint64_t pos = 0, lines = 0, bytes = 0, hits = 0;
+    bool failed = false;
+    auto close_line = [&]() {
+        uint64_t h = 0;
+        const uint64_t len = line.size();
+        folded.resize(len);
+        for (uint64_t i = 0; i < len; i++) folded[i] = S.fold(line[i]);
+        for (uint64_t p = 0; p < len; p++) {
+            const uint64_t got = set_occurs(S, folded.data(), p, len);
+            for (uint64_t g = got; g; g &= g - 1) per[__builtin_ctzll(g)]++;
+            h += got != 0;
+        }
+        if (h) {
+            hits += h;
+            lines++;
+            bytes += len;
+            if (fout && fwrite(line.data(), 1, (size_t)len, fout) != len) failed = true;
+        }
+        line.clear();
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        for (uint64_t p = 0; p < n;) {
+            const uint8_t *at = (const uint8_t *)memchr(plain + p, delim, (size_t)(n - p));
+            const uint64_t q = at ? (uint64_t)(at - plain) + 1 : n;   // the line's bytes in this record end here
+            line.insert(line.end(), plain + p, plain + q);
+            if (at) close_line();
+            p = q;
+        }
+        pos += n;
+        return !failed;
+    });
+    if (r) return r;
+    if (!line.empty()) close_line();   // the unterminated tail is a line
+    if (failed) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (stats) {
+        stats[0] = lines;
+        stats[1] = bytes;
+        stats[2] = hits;
+        stats[3] = pos;
+    }
+    for (uint32_t k = 0; k < S.npat && counts; k++) counts[k] = per[k];
+    return grep_set_totals(lines, bytes, hits, pos, S.npat);
 }
 
 }  // namespace fcx_cli

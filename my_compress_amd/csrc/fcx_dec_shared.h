@@ -693,6 +693,63 @@ struct RangesScratch {
     uint64_t stats[FCX_RANGES_STATS] = {};
 };
 
+// ---- pattern sets (fcx_set.hip): its own scan kernel in front of the search's and the grep's
+// downstream kernels, which are defined in fcx_find.hip and fcx_grep.hip and launched from fcx_set.hip too ----
+__global__ void k_fbase(const uint32_t *__restrict__ tile_count, uint32_t ntiles, uint32_t *__restrict__ tile_base,
+                        uint64_t *__restrict__ words);
+__global__ void k_fwrite(const uint16_t *__restrict__ bitmap, const uint32_t *__restrict__ tile_count,
+                         const uint32_t *__restrict__ tile_base, uint32_t ntiles, const uint64_t *__restrict__ words,
+                         uint64_t pos_base, uint64_t win0, uint64_t winlen, uint64_t *__restrict__ out);
+__global__ void k_fcarry(const uint8_t *__restrict__ src, uint64_t len, uint32_t keep, uint8_t *__restrict__ carry);
+__global__ void k_gtiles(const uint32_t *__restrict__ tile_sum, uint32_t ntiles, uint64_t pos_base, uint64_t *__restrict__ tile_ctx,
+                         uint64_t *__restrict__ words, uint64_t *__restrict__ d_end, uint64_t cap);
+__global__ void k_gmark(uint16_t *__restrict__ hit_bits, const uint16_t *__restrict__ delim_bits, const uint32_t *__restrict__ tile_sum,
+                        const uint64_t *__restrict__ tile_ctx, uint32_t ntiles, uint64_t pos_base, uint32_t *__restrict__ tile_count,
+                        uint64_t *__restrict__ words);
+__global__ void k_gbase(const uint32_t *__restrict__ tile_count, uint32_t ntiles, uint32_t *__restrict__ tile_base,
+                        uint64_t *__restrict__ words);
+__global__ void k_gwrite(const uint16_t *__restrict__ hit_bits, const uint16_t *__restrict__ delim_bits,
+                         const uint64_t *__restrict__ tile_ctx, const uint32_t *__restrict__ tile_count,
+                         const uint32_t *__restrict__ tile_base, uint32_t ntiles, const uint64_t *__restrict__ words,
+                         uint64_t pos_base, uint64_t win0, uint64_t winlen, uint64_t *__restrict__ d_start,
+                         uint64_t *__restrict__ d_end);
+__global__ void k_gfinish(uint64_t *__restrict__ words, uint64_t total, uint64_t *__restrict__ d_end, uint64_t cap);
+__global__ void k_gcarry(const uint8_t *__restrict__ src, uint64_t len, uint32_t keep, uint8_t *__restrict__ carry);
+
+// status words of a set scan (fcx_dctx's ps.words, u64 each): the counters of k_sscan, then the 64 per-pattern counts
+constexpr uint32_t kSwJudged = 0;      // start positions judged
+constexpr uint32_t kSwCand = 1;        // of those, the ones with a non-zero candidate mask
+constexpr uint32_t kSwCompares = 2;    // (position, pattern) pairs taken to the full compare
+constexpr uint32_t kSwHits = 3;        // positions at which a pattern occurs
+constexpr uint32_t kSwCounts = 8;      // FCX_SET_MAX_PATTERNS words: positions at which pattern k occurs
+constexpr uint32_t kSwWords = kSwCounts + FCX_SET_MAX_PATTERNS;
+
+// fcx_find_set_shard / fcx_grep_set_shard behind their argument checks (fcx_set.hip), for the stream path's groups
+// of a longer file as find_run and grep_run are.  last: the run ends the file, so its last group judges the
+// positions that are left with every pattern bounded by the end; without it they stay in the carry, for the next
+// run or for set_final.  counts (may be null): the file's per-pattern counts so far.
+int find_set_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const fcx_pattern_set *set,
+                 uint64_t base, const FindSink &sink, bool last, uint64_t *nhits, uint64_t *decoded, uint64_t *counts, hipStream_t st,
+                 uint64_t rec_base);
+int grep_set_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                 const fcx_pattern_set *set, const GrepSink &sink, GrepCarry *carry, uint64_t *stats, uint64_t *counts, hipStream_t st,
+                 uint64_t rec_base);
+// the stream forms' final pass over the carry alone, once the reader has ended at `total` decoded bytes
+int find_set_final(fcx_dctx *c, const fcx_pattern_set *set, uint64_t total, const FindSink &sink, uint64_t *nhits, uint64_t *counts,
+                   hipStream_t st);
+int grep_set_final(fcx_dctx *c, uint8_t delim, const fcx_pattern_set *set, const GrepSink &sink, GrepCarry *carry, uint64_t *stats,
+                   uint64_t *counts, hipStream_t st);
+// the argument checks the six entry points share; `fn` names the entry point, delim < 0: a find
+int set_args(const char *fn, const fcx_pattern_set *set, int delim);
+
+// scratch of the set calls beside the search's (fd) and the grep's (gp), which they use as those do
+struct SetScratch {
+    DevBuf<uint32_t> block;          // the set's compiled block (fcx_patset.h)
+    DevBuf<uint64_t> words;          // kSw*
+    PinnedBuf<uint64_t> host_words;
+    uint64_t stats[FCX_SET_SCAN_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -728,6 +785,7 @@ struct fcx_dctx {
     fcx::LinesScratch ln;
     fcx::GrepScratch gp;
     fcx::RangesScratch rq;
+    fcx::SetScratch ps;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

@@ -479,4 +479,44 @@ int fcx_grep_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, uint8_t delim
     return fetch_out(c, out, got);
 }
 
+// fcx_grep_host for a pattern set: fcx_grep_set_shard's arrays chained into the multi-range decode
+int fcx_grep_set_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, uint8_t delim, const fcx_pattern_set *set, uint8_t *out,
+                      uint64_t cap, uint64_t *out_len, uint64_t *stats, uint64_t *counts) {
+    if (!c || !in || !set || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_grep_set_host: NULL argument");
+    FCX_TRY(set_args("fcx_grep_set_host", set, delim));
+    char kind = 0;
+    uint32_t nblocks = 0;
+    uint64_t rec_len = 0;
+    FCX_TRY(walk_file(in, in_len, &kind, &nblocks, &rec_len));
+    uint64_t gs[FCX_GREP_STATS] = {};
+    *out_len = 0;
+    for (int i = 0; i < FCX_GREP_STATS && stats; i++) stats[i] = 0;
+    GrepSink sink;
+    if (nblocks == 0) return grep_set_run(c, kind, nullptr, 0, 0, delim, set, sink, nullptr, gs, counts, nullptr, 0);
+    RangesScratch &Q = c->rq;
+    FCX_TRY(stage_file(c, in, rec_len));
+    // room for the lines: what the context holds already or a guess, and once more when the run has more
+    uint64_t room = std::max<uint64_t>(std::min(Q.starts.bytes, Q.ends.bytes) / 8, kQGuessLines);
+    for (int pass = 0; pass < 2; pass++) {
+        FCX_TRY(Q.starts.reserve(8 * room, "ranges"));
+        FCX_TRY(Q.ends.reserve(8 * room, "ranges"));
+        sink.d_start = Q.starts;
+        sink.d_end = Q.ends;
+        sink.cap = room;
+        FCX_TRY(grep_set_run(c, kind, Q.file, rec_len, nblocks, delim, set, sink, nullptr, gs, counts, nullptr, 0));
+        if (gs[0] <= room) break;
+        room = gs[0];
+    }
+    for (int i = 0; i < FCX_GREP_STATS && stats; i++) stats[i] = gs[i];
+    *out_len = gs[1];
+    if (gs[1] > cap) return fail(FCX_ERR_CAPACITY, "fcx_grep_set_host: output capacity too small");
+    if (gs[1] == 0) return FCX_OK;
+    FCX_TRY(Q.out.reserve(gs[1], "ranges output"));
+    uint64_t got = 0;
+    FCX_TRY(ranges_run(c, kind, Q.file, rec_len, nblocks, c->rg.rec_off, c->rg.dec_off, Q.starts, Q.ends, gs[0], Q.out, gs[1], &got,
+                       nullptr));
+    if (got != gs[1]) return fail(FCX_ERR_INTERNAL, "fcx_grep_set_host: the lines' bytes disagree with the grep's sum");
+    return fetch_out(c, out, got);
+}
+
 }  // extern "C"

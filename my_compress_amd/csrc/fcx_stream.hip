@@ -957,6 +957,94 @@ int fcx_grep_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in,
     return FCX_OK;
 }
 
+// ---- the pattern sets' stream and host forms (include/fcx.h): where the file ends shows only when
+// the reader has ended, so the positions the last group carried are judged by a final pass over the carry alone ----
+
+int fcx_find_set_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, const fcx_pattern_set *set, fcx_hit_fn on_hit,
+                        void *user_cb, uint64_t *stats, uint64_t *counts) {
+    if (!dctx || !rd || !set) return fail(FCX_ERR_ARG, "fcx_find_set_stream: NULL argument");
+    FCX_TRY(fcx::set_args("fcx_find_set_stream", set, -1));
+    uint64_t sum[4] = {0, 0, 0, 0};
+    FindSink sink;
+    sink.on_hit = on_hit;
+    sink.user = user_cb;
+    hipStream_t last_st = nullptr;
+    bool any = false;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        uint64_t hits = 0, dec = 0;
+        FCX_TRY(fcx::find_set_run(dctx, lz78 ? '8' : '7', x.din, used, nb, set, sum[1], sink, false, &hits, &dec, counts, st, before));
+        sum[0] += hits;
+        sum[1] += dec;
+        sum[2] += nb;
+        last_st = st;
+        any = true;
+        return FCX_OK;
+    });
+    if (r) return r;
+    if (any) {
+        uint64_t hits = 0;
+        FCX_TRY(fcx::find_set_final(dctx, set, sum[1], sink, &hits, counts, last_st));
+        sum[0] += hits;
+    } else {   // a file without records: nothing ran, so nothing of an earlier call may show
+        uint64_t none = 0;
+        FCX_TRY(fcx::find_set_run(dctx, '7', nullptr, 0, 0, set, 0, sink, true, &none, nullptr, counts, nullptr, 0));
+    }
+    sum[3] = dctx->ps.stats[0];
+    for (int i = 0; i < 4 && stats; i++) stats[i] = sum[i];
+    return FCX_OK;
+}
+
+int fcx_find_set_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const fcx_pattern_set *set, uint64_t *hits, uint64_t cap,
+                      uint64_t *nhits, uint64_t *counts) {
+    if (!dctx || !in || !set || !nhits || (cap && !hits)) return fail(FCX_ERR_ARG, "fcx_find_set_host: NULL argument");
+    FCX_TRY(fcx::set_args("fcx_find_set_host", set, -1));
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    struct Take {
+        uint64_t *hits, cap, n;
+    } take{hits, cap, 0};
+    MemIO comp{in, in_len, 0, nullptr, 0, 0};
+    uint64_t stats[4] = {};
+    const fcx_hit_fn keep = [](void *u, uint64_t off) {
+        Take *k = (Take *)u;
+        if (k->n < k->cap) k->hits[k->n] = off;
+        k->n++;
+    };
+    FCX_TRY(fcx_find_set_stream(dctx, mem_read, &comp, in_len - FCX_HEADER_BYTES, set, cap ? keep : nullptr, &take, stats, counts));
+    *nhits = stats[0];
+    return FCX_OK;
+}
+
+int fcx_grep_set_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, uint8_t delim, const fcx_pattern_set *set,
+                        fcx_range_fn on_line, void *user_line, uint64_t *stats, uint64_t *counts) {
+    if (!dctx || !rd || !set) return fail(FCX_ERR_ARG, "fcx_grep_set_stream: NULL argument");
+    FCX_TRY(fcx::set_args("fcx_grep_set_stream", set, delim));
+    GrepSink sink;
+    sink.on_line = on_line;
+    sink.user = user_line;
+    GrepCarry carry;
+    uint64_t gs[FCX_GREP_STATS] = {};
+    hipStream_t last_st = nullptr;
+    bool any = false;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        last_st = st;
+        any = true;
+        return fcx::grep_set_run(dctx, lz78 ? '8' : '7', x.din, used, nb, delim, set, sink, &carry, gs, counts, st, before);
+    });
+    if (r) return r;
+    if (any) FCX_TRY(fcx::grep_set_final(dctx, delim, set, sink, &carry, gs, counts, last_st));
+    else FCX_TRY(fcx::grep_set_run(dctx, '7', nullptr, 0, 0, delim, set, sink, &carry, gs, counts, nullptr, 0));
+    if (carry.held) {   // the file ends inside a selected line
+        if (on_line) on_line(user_line, carry.held_start, carry.base);
+        carry.held = false;
+    }
+    if (gs[0] && dctx->gp.host_words && dctx->gp.host_words[kGwOpen]) gs[1] += carry.base - dctx->gp.host_words[kGwLast];
+    gs[4] = carry.base;
+    for (int i = 0; i < FCX_GREP_STATS && stats; i++) stats[i] = gs[i];
+    return FCX_OK;
+}
+
 int fcx_decompress_ranges_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
                                  const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *out_len) {
     if (!dctx || !rd || !wr || (n && (!starts || !ends))) return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: NULL argument");
