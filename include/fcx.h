@@ -722,7 +722,8 @@ int fcx_grep_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_
                    const uint8_t *pattern /* host */, uint32_t plen, uint64_t *d_start, uint64_t *d_end, uint64_t cap,
                    uint64_t *stats, void *stream);
 /* Device bytes the last fcx_grep_shard call on the context reserved beside the decoded group (the bitmaps and the
- * tile words of its largest group; 0 after a call without records). */
+ * tile words of its largest group; 0 after a call without records).  After a fcx_grep_blocks_* call: those
+ * and what the select stage reserved beside them (its bitmaps, tile words, ring and words). */
 int fcx_dctx_grep_scratch(fcx_dctx *ctx, uint64_t *bytes);
 /* Decodes nranges byte ranges [d_start[i], d_end[i]) of D (device arrays) in one call: d_out[0, sum) is the
  * concatenation of D[start_i, end_i) in order, *out_len is always the sum.  Rules: start_i <= end_i <= T and
@@ -837,6 +838,55 @@ int fcx_grep_set_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t
  * last group and in the stream and host forms the pass behind the last group, which scans nothing when no
  * position is left (max_len == 1, or nothing was decoded); 0 after a call without records. */
 int fcx_dctx_set_scan_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
+/* ---- context and inverted grep: grep -v, -A, -B, -C on a run (FCX7 and FCX8) ------------------------------
+ * D, T, the delimiter d, the lines s_j / e_j and their number L are those of the line calls; a hit is the
+ * pattern sets' hit.  Line j matches iff a hit p has s_j <= p < e_j.  Line j is a base line iff it matches, or
+ * with FCX_GREP_INVERT iff it does not.  Line j is selected iff some base line k has j - after <= k <= j +
+ * before: `after` lines follow a base line, `before` lines precede one; with the invert flag the context
+ * surrounds the lines that do not match, as in GNU grep.  The result is the blocks: the maximal runs of
+ * consecutive selected lines, ascending, each as (start = s of its first line, end = e of its last line, line =
+ * the 0-based number of its first line).  Two selected lines that touch are one block (GNU grep prints its
+ * `--` between blocks).  Blocks are disjoint and ascending, so d_start / d_end feed
+ * fcx_decompress_ranges_shard unchanged.  Blocks and not lines, because -v on a run with few hits selects
+ * nearly every line: that is one range per gap between hits, at most hits + 1 of them, instead of 16 bytes
+ * per line.  T == 0 has no lines and no blocks; an unterminated tail is a line like any other (with the invert
+ * flag it can be a base line); a run without a delimiter is one line; empty lines are lines that never match,
+ * so with the invert flag they are base lines.
+ * stats (FCX_GREP_BLOCK_STATS values): blocks, selected lines, bytes (sum of end - start), base lines, hits,
+ * positions judged, decoded bytes T, lines L; all over the whole run whatever cap is.  The answer does not
+ * depend on record, tile, decode-group or stream-group boundaries (fcx_dctx_set_verify_group,
+ * fcx_dctx_set_find_window); the run is decoded once; scratch beside the grep's own is three bitmaps and 56
+ * bytes per tile of a decode group plus a ring of before + 1 line starts (at most 32 KiB), whatever the hits,
+ * the lines or the blocks, and nothing of a line's bytes travels between groups. */
+#define FCX_GREP_INVERT 1u
+#define FCX_GREP_MAX_CONTEXT 4096u
+typedef struct fcx_grep_opts { uint32_t flags, before, after; } fcx_grep_opts;
+#define FCX_GREP_BLOCK_STATS 8  /* blocks, selected lines, bytes (sum of end - start), base lines,
+                                   hits, judged, decoded (T), lines (L) */
+/* fcx_grep_set_shard's arguments, checks, cap rule and size query, with the options and a third array: the
+ * first min(cap, blocks) blocks to d_start / d_end / d_line (device; all three NULL with cap == 0 for the
+ * counts alone); FCX_OK whether or not cap was reached, and nothing behind min(cap, blocks) is written.  A set
+ * of one pattern without flags and zero options is the plain grep.  nblocks == 0 gives zeros and touches no
+ * device.  FCX_ERR_ARG also, before the device is touched: NULL opts, unknown flag bits, before or after above
+ * FCX_GREP_MAX_CONTEXT.  Synchronises `stream`.  Stage table with profiling: index, decode, scan, select,
+ * summary. */
+int fcx_grep_blocks_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+                          const fcx_pattern_set *set, const fcx_grep_opts *opts, uint64_t *d_start, uint64_t *d_end,
+                          uint64_t *d_line, uint64_t cap, uint64_t *stats, uint64_t *counts, void *stream);
+typedef void (*fcx_block_fn)(void *user, uint64_t start, uint64_t end, uint64_t line, uint64_t nlines);
+/* fcx_grep_set_stream's twin: the file is one run.  on_block (may be NULL: the totals alone) is called for every
+ * block once, in order, with its true end and the number of its lines: a block still open at a stream group's
+ * end is held back (its start and first line), and lines that only a base line of a later group can select
+ * wait on the device (the ring) until that group shows whether and where their block starts. */
+int fcx_grep_blocks_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, uint8_t delim,
+                           const fcx_pattern_set *set, const fcx_grep_opts *opts, fcx_block_fn on_block, void *user_block,
+                           uint64_t *stats, uint64_t *counts);
+/* fcx_grep_set_host's twin: the records go to the device once, the blocks feed fcx_decompress_ranges_shard
+ * there, and only the blocks' bytes come back, concatenated; the size query and FCX_ERR_CAPACITY as there. */
+int fcx_grep_blocks_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t delim, const fcx_pattern_set *set,
+                         const fcx_grep_opts *opts, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats,
+                         uint64_t *counts);
 
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so

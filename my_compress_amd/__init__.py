@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "grep_context", "grep_context_blocks", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -233,6 +233,14 @@ def lib():
         L.fcx_grep_set_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, c_u8p, ctypes.c_uint64,
                                         P64, P64, P64]
         L.fcx_dctx_set_scan_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+    if hasattr(L, "fcx_grep_blocks_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]
+        L.fcx_grep_blocks_shard.argtypes = run + [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_uint64, P64, P64, ctypes.c_void_p]
+        L.fcx_grep_blocks_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p,
+                                             ctypes.c_void_p, BLOCK_FN, ctypes.c_void_p, P64, P64]
+        L.fcx_grep_blocks_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
+                                           c_u8p, ctypes.c_uint64, P64, P64, P64]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -279,6 +287,12 @@ HIT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64)
 FIND_MAX_PATTERN = 256     # FCX_FIND_MAX_PATTERN
 # fcx_range_fn: start and end of a selected line
 RANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
+BLOCK_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64)
+
+
+class GrepOpts(ctypes.Structure):
+    """fcx_grep_opts"""
+    _fields_ = [("flags", ctypes.c_uint32), ("before", ctypes.c_uint32), ("after", ctypes.c_uint32)]
 
 
 # the repair sidecar (include/fcx.h): one 32-byte entry layout on the device, in the FCXR file and here
@@ -1011,6 +1025,63 @@ class DContext:
                "fcx_grep_set_stream")
         return dict(zip(self.GREP_STATS, [int(v) for v in vals])), got, [int(v) for v in counts]
 
+    # ---- context and inverted grep (fcx_grep_blocks_*): grep -v / -A / -B / -C as blocks of consecutive selected lines ----
+    GREP_BLOCK_STATS = ("blocks", "lines", "bytes", "base_lines", "hits", "judged", "decoded", "total_lines")
+    GREP_INVERT = 1
+    GREP_MAX_CONTEXT = 4096
+
+    @classmethod
+    def _opts(cls, invert, before, after) -> "GrepOpts":
+        if not (0 <= before < 1 << 32 and 0 <= after < 1 << 32):
+            raise ValueError("before and after are counts of lines")
+        return GrepOpts(cls.GREP_INVERT if invert else 0, before, after)
+
+    def grep_blocks_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, pset: "PatternSet", delim=b"\n", invert: bool = False,
+                          before: int = 0, after: int = 0, d_start: int = 0, d_end: int = 0, d_line: int = 0, cap: int = 0,
+                          stream: int = 0):
+        """the blocks of device records (no header): the maximal runs of lines that hold a pattern of `pset` (invert: that
+        hold none) or lie within `before` lines in front of or `after` lines behind such a line.  Returns
+        (GREP_BLOCK_STATS, counts); start, end and first line of the first min(cap, blocks) go to d_start / d_end /
+        d_line (u64 on the device)"""
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        opts = self._opts(invert, before, after)
+        _check(lib().fcx_grep_blocks_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, self._delim(delim),
+                                           pset.handle, ctypes.byref(opts), ctypes.c_void_p(d_start or None),
+                                           ctypes.c_void_p(d_end or None), ctypes.c_void_p(d_line or None), cap, vals, counts,
+                                           ctypes.c_void_p(stream)), "fcx_grep_blocks_shard")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), [int(v) for v in counts]
+
+    def grep_blocks_host(self, blob: bytes, pset: "PatternSet", delim=b"\n", invert: bool = False, before: int = 0, after: int = 0):
+        """a whole FCX7 or FCX8 file in memory -> (stats, the blocks' bytes concatenated, counts): grep -F -f with -v, -B
+        and -A, without the `--` lines; found and gathered on the GPU, only the blocks' bytes come back"""
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        need = ctypes.c_uint64(0)
+        opts = self._opts(invert, before, after)
+        args = (self._h, blob, len(blob), self._delim(delim), pset.handle, ctypes.byref(opts))
+        rc = lib().fcx_grep_blocks_host(*args, None, 0, ctypes.byref(need), vals, counts)   # the size
+        if rc != -2:
+            _check(rc, "fcx_grep_blocks_host")
+            return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), b"", [int(v) for v in counts]
+        out = ctypes.create_string_buffer(need.value)
+        _check(lib().fcx_grep_blocks_host(*args, out, need.value, ctypes.byref(need), vals, counts), "fcx_grep_blocks_host")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), out.raw[:need.value], [int(v) for v in counts]
+
+    def grep_blocks_stream(self, src, pset: "PatternSet", delim=b"\n", invert: bool = False, before: int = 0, after: int = 0,
+                           max_in: int = 0, want_blocks: bool = True):
+        """an FCX7 or FCX8 file from src (binary reader) -> (stats, [(start, end, line, nlines)] of every block, ascending,
+        each once and with its true end, counts); want_blocks False: the totals alone"""
+        rd, _ = _stream_fns(src, None)
+        got = []
+        cb = BLOCK_FN(lambda _u, s, e, ln, n: got.append((int(s), int(e), int(ln), int(n)))) if want_blocks else ctypes.cast(None, BLOCK_FN)
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        counts = (ctypes.c_uint64 * len(pset))()
+        opts = self._opts(invert, before, after)
+        _check(lib().fcx_grep_blocks_stream(self._h, rd, None, max_in, self._delim(delim), pset.handle, ctypes.byref(opts), cb, None, vals,
+                                            counts), "fcx_grep_blocks_stream")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), got, [int(v) for v in counts]
+
     def set_scan_stats(self) -> dict:
         """counters of the last pattern-set call (fcx_dctx_set_scan_stats)"""
         n = len(self.SET_SCAN_STATS)
@@ -1301,6 +1372,31 @@ def grep_any_ranges(blob: bytes, patterns, delim=b"\n", ignore_case: bool = Fals
     ps = PatternSet(patterns, ignore_case)
     try:
         return _with_dctx(device, lambda c: c.grep_set_stream(io.BytesIO(blob), ps, delim, max(0, len(blob) - HEADER_BYTES)))
+    finally:
+        ps.close()
+
+
+def grep_context(blob: bytes, patterns, delim=b"\n", ignore_case: bool = False, invert: bool = False, before: int = 0, after: int = 0,
+                 device: int = 0) -> bytes:
+    """grep -F -f (-i) (-v) -B before -A after over what `blob` decodes to: the bytes of the selected lines, in order,
+    without the `--` lines between blocks (grep_context_blocks() says where the blocks are)"""
+    ps = PatternSet(patterns, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_blocks_host(blob, ps, delim, invert, before, after)[1])
+    finally:
+        ps.close()
+
+
+def grep_context_blocks(blob: bytes, patterns, delim=b"\n", ignore_case: bool = False, invert: bool = False, before: int = 0,
+                        after: int = 0, device: int = 0):
+    """(stats, [(start, end, line, nlines)], counts) of the blocks whose bytes grep_context() returns, through the stream
+    form"""
+    import io
+
+    ps = PatternSet(patterns, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_blocks_stream(io.BytesIO(blob), ps, delim, invert, before, after,
+                                                                 max(0, len(blob) - HEADER_BYTES)))
     finally:
         ps.close()
 

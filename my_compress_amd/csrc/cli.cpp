@@ -86,8 +86,20 @@
 // any of them with --line-numbers; for a grep a pattern that holds the delimiter or, with --ignore-case, that holds it
 // after folding both; and whatever is a usage error with --find or --grep.
 // Without a HIP device an FCX7 file is cut into lines on the host decoder, with the same bytes and last line; FCX8 fails.
+//
+// Context and inverted grep, with --grep, --grep-hex or --grep-set only (fcx_grep_blocks_stream, then
+// fcx_decompress_ranges_stream over the blocks):
+//   --invert          the lines that hold no pattern (grep -v)
+//   --before N        N lines in front of every such line too (grep -B), N <= 4096
+//   --after N         N lines behind it (grep -A)
+//   --context N       both (grep -C)
+// They combine with --ignore-case, --delim and --count.  The output is the selected lines in order; with a context a
+// line "--" goes between two runs of consecutive selected lines, as GNU grep prints it.  The last line printed is
+// "grep: K blocks, L lines, S base lines, B bytes, H hits, decoded bytes = T".  Usage errors: a value that is not a
+// number or lies above 4096; one of the four without a grep option.
 #include <getopt.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -114,7 +126,9 @@ static int usage() {
             "[--grep <string> | --grep-hex <hex digits> [--count] (decompress only: the lines that hold the bytes, to -o)] "
             "[--delim <two hex digits> (the line delimiter, default 0a)] "
             "[--find-set <pattern file> | --grep-set <pattern file> [--set-hex] [--count] (decompress only: up to 64 patterns, one a line)] "
-            "[--ignore-case (with a search: ASCII letters match in either case)]\n");
+            "[--ignore-case (with a search: ASCII letters match in either case)] "
+            "[--invert] [--before <lines>] [--after <lines>] [--context <lines>] (with a grep: the lines without a pattern, "
+            "lines of context, at most 4096)\n");
     return -1;
 }
 
@@ -799,6 +813,84 @@ static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set 
     return fcx_cli::grep_set_totals(stats[0], stats[1], stats[2], stats[4], npat);
 }
 
+// --grep, --grep-hex or --grep-set with --invert, --before, --after or --context: the blocks of selected lines
+struct BlockOut {
+    FILE *in, *out;
+    std::vector<uint64_t> starts, ends;
+    const char *sep;       // what goes between two blocks ("": nothing)
+    uint64_t at = 0;       // bytes of the blocks written so far
+    uint64_t sum = 0;      // ... and up to the end of block k
+    size_t k = 0;
+};
+static int64_t blocks_read(void *u, uint8_t *buf, uint64_t cap) { return file_read(((BlockOut *)u)->in, buf, cap); }
+// the blocks' bytes arrive back to back: the separator goes in where one block ends and the next begins
+static int blocks_write(void *u, const uint8_t *buf, uint64_t n) {
+    BlockOut *b = (BlockOut *)u;
+    while (n) {
+        while (b->k < b->starts.size() && b->at == b->sum) {   // block k begins (empty blocks do not occur)
+            if (b->k && fputs(b->sep, b->out) < 0) return -1;
+            b->sum += b->ends[b->k] - b->starts[b->k];
+            b->k++;
+        }
+        const uint64_t take = std::min<uint64_t>(n, b->sum - b->at);
+        if (take == 0 || fwrite(buf, 1, (size_t)take, b->out) != take) return -1;
+        buf += take;
+        n -= take;
+        b->at += take;
+    }
+    return 0;
+}
+
+static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, uint8_t delim,
+                          const fcx_grep_opts &opts) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_grep_blocks(fin, nblocks, delim, host_set, opts, fout, nullptr, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_GREP_BLOCK_STATS] = {}, got = 0;
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    BlockOut io{fin, fout, {}, {}, fcx_cli::block_separator(opts)};
+    const fcx_block_fn keep = [](void *u, uint64_t s, uint64_t e, uint64_t, uint64_t) {
+        ((BlockOut *)u)->starts.push_back(s);
+        ((BlockOut *)u)->ends.push_back(e);
+    };
+    int r = fcx_grep_blocks_stream(d, file_read, fin, max_in, delim, set, &opts, fout ? keep : nullptr, &io, stats, nullptr);
+    if (r == FCX_OK && fout && !io.starts.empty()) {
+        rewind(fin);
+        r = fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(), io.starts.size(),
+                                         &got);
+        if (r == FCX_OK && got != stats[2]) {
+            fprintf(stderr, "fcx: the blocks' bytes disagree with the grep's sum\n");
+            fcx_dctx_destroy(d);
+            return -1;
+        }
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::grep_blocks_totals(stats[0], stats[1], stats[3], stats[2], stats[4], stats[6]);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -892,6 +984,10 @@ int main(int argc, char **argv) {
                                            {"grep-set", required_argument, nullptr, 1002},
                                            {"set-hex", no_argument, nullptr, 1003},
                                            {"ignore-case", no_argument, nullptr, 1004},
+                                           {"invert", no_argument, nullptr, 1005},
+                                           {"before", required_argument, nullptr, 1006},
+                                           {"after", required_argument, nullptr, 1007},
+                                           {"context", required_argument, nullptr, 1008},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -910,6 +1006,8 @@ int main(int argc, char **argv) {
     uint8_t delim = 0x0A;
     std::string find_set, grep_set;
     bool set_hex = false, ignore_case = false;
+    fcx_grep_opts gopts = {0, 0, 0};
+    bool blocks = false;   // --invert, --before, --after or --context seen
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -966,6 +1064,20 @@ int main(int argc, char **argv) {
         case 1002: grep_set = optarg; break;
         case 1003: set_hex = true; break;
         case 1004: ignore_case = true; break;
+        case 1005:
+            gopts.flags |= FCX_GREP_INVERT;
+            blocks = true;
+            break;
+        case 1006:
+        case 1007:
+        case 1008: {
+            uint32_t n = 0;
+            if (!fcx_cli::parse_context(optarg, &n)) return usage();
+            if (opt != 1007) gopts.before = n;
+            if (opt != 1006) gopts.after = n;
+            blocks = true;
+            break;
+        }
         default: return usage();
         }
     }
@@ -975,12 +1087,13 @@ int main(int argc, char **argv) {
     if ((!find_set.empty() && !grep_set.empty()) || (set_file && (finds || greps)) || (set_hex && !set_file)) return usage();
     if (ignore_case && !(finds || greps || set_file)) return usage();
     if ((set_file || ignore_case) && line_numbers) return usage();
+    if (blocks && !(greps || !grep_set.empty())) return usage();   // (the blocks run as a set, of one pattern if need be)
     // the library's set, destroyed when main returns, and the command line's own compilation of the same patterns:
     // the delimiter rule and the no-device path read that one, never the library's object
     std::unique_ptr<fcx_pattern_set, void (*)(fcx_pattern_set *)> pset_own(nullptr, fcx_pattern_set_destroy);
     std::unique_ptr<fcx_pattern_set> host_set;
     fcx_pattern_set *pset = nullptr;
-    if (set_file || ignore_case) {
+    if (set_file || ignore_case || blocks) {
         std::vector<uint8_t> sbytes;
         std::vector<uint32_t> slens;
         if (set_file) {
@@ -1036,7 +1149,9 @@ int main(int argc, char **argv) {
         return r;
     }
     if (greps) {
-        const int r = pset ? do_grep_set(fin, fout, device, pset, *host_set, delim) : do_grep(fin, fout, device, grep_pattern, delim);
+        const int r = blocks ? do_grep_blocks(fin, fout, device, pset, *host_set, delim, gopts)
+                      : pset ? do_grep_set(fin, fout, device, pset, *host_set, delim)
+                             : do_grep(fin, fout, device, grep_pattern, delim);
         fclose(fin);
         if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;

@@ -1,9 +1,9 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
 // (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest, --find,
-// --count-lines, --lines, --grep, --find-set and --grep-set.  Host code
+// --count-lines, --lines, --grep, --find-set, --grep-set and the context grep (--invert, --before, --after).  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
-// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp).
+// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp, tools/context_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -771,6 +771,110 @@ inline int host_grep_set(FILE *fin, uint16_t nblocks, uint8_t delim, const fcx_p
     }
     for (uint32_t k = 0; k < S.npat && counts; k++) counts[k] = per[k];
     return grep_set_totals(lines, bytes, hits, pos, S.npat);
+}
+
+// ---- --invert / --before / --after / --context: the value parser, the printout and the host path ----
+// a count of context lines: decimal digits alone, at most FCX_GREP_MAX_CONTEXT
+inline bool parse_context(const char *s, uint32_t *n) {
+    const size_t len = strlen(s);
+    if (len < 1 || len > 9 || strspn(s, "0123456789") != len) return false;
+    const unsigned long v = strtoul(s, nullptr, 10);
+    if (v > FCX_GREP_MAX_CONTEXT) return false;
+    *n = (uint32_t)v;
+    return true;
+}
+inline int grep_blocks_totals(uint64_t blocks, uint64_t lines, uint64_t base, uint64_t bytes, uint64_t hits, uint64_t decoded) {
+    printf("grep: %llu blocks, %llu lines, %llu base lines, %llu bytes, %llu hits, decoded bytes = %llu\n", (unsigned long long)blocks,
+           (unsigned long long)lines, (unsigned long long)base, (unsigned long long)bytes, (unsigned long long)hits,
+           (unsigned long long)decoded);
+    return 0;
+}
+// the line GNU grep prints between two blocks when a context was asked for
+inline const char *block_separator(const fcx_grep_opts &o) { return o.before || o.after ? "--\n" : ""; }
+
+// The context grep without a device: host_grep_set's lines, each judged when it closes.  A base line (it holds a
+// pattern, or with FCX_GREP_INVERT holds none) is written behind the lines waiting in front of it and opens an
+// after-context of opts.after lines; a line that is neither waits, the last opts.before of them at most.  A line
+// written behind a line that was dropped starts a block: block_separator() goes in front of every block but the first.
+// stats (6 values, may be null): blocks, lines, base lines, bytes, hits, decoded bytes; counts as host_find_set's.
+inline int host_grep_blocks(FILE *fin, uint16_t nblocks, uint8_t delim, const fcx_pattern_set &S, const fcx_grep_opts &opts, FILE *fout,
+                            uint64_t *stats, uint64_t *counts) {
+    std::vector<uint8_t> line, folded;       // the open line so far
+    std::vector<std::vector<uint8_t>> wait;  // the unselected lines right in front of the open one, opts.before at most
+    std::vector<uint64_t> per(S.npat, 0);
+    const std::string sep = block_separator(opts);
+    const bool invert = (opts.flags & FCX_GREP_INVERT) != 0;
+    uint64_t pos = 0, blocks = 0, lines = 0, base = 0, bytes = 0, hits = 0, after_left = 0;
+    uint64_t dropped = 0;   // lines since the last written one that no longer wait: a line written behind them starts a block
+    bool failed = false;
+    auto put = [&](const std::vector<uint8_t> &l) {
+        if (lines == 0 || dropped) {
+            if (blocks && fout && !sep.empty() && fwrite(sep.data(), 1, sep.size(), fout) != sep.size()) failed = true;
+            blocks++;
+        }
+        dropped = 0;
+        lines++;
+        bytes += l.size();
+        if (fout && fwrite(l.data(), 1, l.size(), fout) != l.size()) failed = true;
+    };
+    auto close_line = [&]() {
+        uint64_t h = 0;
+        const uint64_t len = line.size();
+        folded.resize(len);
+        for (uint64_t i = 0; i < len; i++) folded[i] = S.fold(line[i]);
+        for (uint64_t p = 0; p < len; p++) {
+            const uint64_t got = set_occurs(S, folded.data(), p, len);
+            for (uint64_t g = got; g; g &= g - 1) per[__builtin_ctzll(g)]++;
+            h += got != 0;
+        }
+        hits += h;
+        if ((h != 0) != invert) {
+            base++;
+            for (const std::vector<uint8_t> &w : wait) put(w);
+            wait.clear();
+            put(line);
+            after_left = opts.after;
+        } else if (after_left) {
+            put(line);
+            after_left--;
+        } else if (opts.before == 0) {
+            dropped++;
+        } else {
+            if (wait.size() == opts.before) {
+                wait.erase(wait.begin());
+                dropped++;
+            }
+            wait.push_back(line);
+        }
+        line.clear();
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        for (uint64_t p = 0; p < n;) {
+            const uint8_t *at = (const uint8_t *)memchr(plain + p, delim, (size_t)(n - p));
+            const uint64_t q = at ? (uint64_t)(at - plain) + 1 : n;   // the line's bytes in this record end here
+            line.insert(line.end(), plain + p, plain + q);
+            if (at) close_line();
+            p = q;
+        }
+        pos += n;
+        return !failed;
+    });
+    if (r) return r;
+    if (!line.empty()) close_line();   // the unterminated tail is a line
+    if (failed) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (stats) {
+        stats[0] = blocks;
+        stats[1] = lines;
+        stats[2] = base;
+        stats[3] = bytes;
+        stats[4] = hits;
+        stats[5] = pos;
+    }
+    for (uint32_t k = 0; k < S.npat && counts; k++) counts[k] = per[k];
+    return grep_blocks_totals(blocks, lines, base, bytes, hits, pos);
 }
 
 }  // namespace fcx_cli

@@ -750,6 +750,80 @@ struct SetScratch {
     uint64_t stats[FCX_SET_SCAN_STATS] = {};
 };
 
+// ---- context and inverted grep (fcx_context.hip): a select stage in line-number space behind
+// k_sscan<true> and k_gtiles.  Status words of a blocks call (fcx_dctx's cx.words, u64 each; host_words mirrors
+// them); lines are numbered from 0, "1 + line" words use 0 for none ----
+constexpr uint32_t kXwLines = 0;       // delimiters seen so far: the closed lines, and the open line's number
+constexpr uint32_t kXwLastBase = 1;    // 1 + the number of the last base line seen (0: none)
+constexpr uint32_t kXwBase = 2;        // base lines so far
+constexpr uint32_t kXwStarts = 3;      // block starts so far: the blocks
+constexpr uint32_t kXwEnds = 4;        // block ends so far (kXwStarts or one less)
+constexpr uint32_t kXwSumStart = 5;    // sum of the starts, of the ends, of the first lines, of 1 + the last lines:
+constexpr uint32_t kXwSumEnd = 6;      // ... bytes and selected lines are differences of these
+constexpr uint32_t kXwSumSLine = 7;
+constexpr uint32_t kXwSumELine = 8;
+constexpr uint32_t kXwPendEnd = 9;     // the end of line kXwLastBase - 1 + after, closed with no base line behind it
+constexpr uint32_t kXwPendLine = 10;   // ... yet (0: none), and that line's number: the open block's end unless a later base line reaches it
+constexpr uint32_t kXwGroupS = 11;     // starts and ends before the group's own (k_clines) ...
+constexpr uint32_t kXwGroupE = 12;
+constexpr uint32_t kXwGroupNS = 13;    // ... and the group's own (k_cscan)
+constexpr uint32_t kXwGroupNE = 14;
+constexpr uint32_t kXwTotal = 15;      // the run's lines (k_cfinish)
+constexpr uint32_t kXwResEnd = 16;     // 3 words each (flag, position, line): the pending end and the pending start
+constexpr uint32_t kXwResStart = 19;   // ... that k_clines or k_cfinish resolved, and the end k_cfinish gave the
+constexpr uint32_t kXwFinEnd = 22;     // ... block open at the run's end (the stream forms read them)
+constexpr uint32_t kXwWords = 32;
+constexpr uint32_t kCRing = FCX_GREP_MAX_CONTEXT + 1;   // starts of the last before + 1 lines, by line number mod (before + 1)
+
+// where a blocks call leaves its blocks: the first `cap` at d_start / d_end / d_line (device, the shard form), or
+// every block through on_block in order (the stream form, by windows of fd.window)
+struct BlockSink {
+    uint64_t *d_start = nullptr, *d_end = nullptr, *d_line = nullptr;
+    uint64_t cap = 0;
+    fcx_block_fn on_block = nullptr;
+    void *user = nullptr;
+};
+// what the stream form keeps between its runs: the decoded offset of the next run's first byte, and the start and
+// first line of the block that is still open
+struct BlockCarry {
+    uint64_t base = 0;
+    bool held = false;
+    uint64_t held_start = 0, held_line = 0;
+};
+// fcx_grep_blocks_shard behind its argument checks (fcx_context.hip), shaped as grep_set_run and grep_set_final
+int blocks_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, uint8_t delim,
+               const fcx_pattern_set *set, const fcx_grep_opts &opts, const BlockSink &sink, BlockCarry *carry, uint64_t *stats,
+               uint64_t *counts, hipStream_t st, uint64_t rec_base);
+int blocks_final(fcx_dctx *c, uint8_t delim, const fcx_pattern_set *set, const fcx_grep_opts &opts, const BlockSink &sink,
+                 BlockCarry *carry, uint64_t *stats, uint64_t *counts, hipStream_t st);
+// the argument checks the three entry points share
+int blocks_args(const char *fn, const fcx_pattern_set *set, uint8_t delim, const fcx_grep_opts *opts);
+// what fcx_set.hip does for the blocks calls: its scratch and the set's block made ready, the grep's tile scratch,
+// k_sscan<true> over one range (*ntiles: its tiles), and the set's counters fetched and published
+int context_ready(fcx_dctx *c, const fcx_pattern_set *set, bool fresh, hipStream_t st);
+int context_reserve(fcx_dctx *c, uint64_t range_bytes);
+int context_scan(fcx_dctx *c, const fcx_pattern_set *set, uint8_t delim, const uint8_t *src, uint64_t len, bool final,
+                 uint32_t *ntiles, hipStream_t st);
+int context_fetch(fcx_dctx *c, hipStream_t st);
+void context_publish(fcx_dctx *c, const fcx_pattern_set *set, uint64_t *counts);
+
+// scratch of the blocks calls beside the grep's (gp) and the set's (ps)
+struct ContextScratch {
+    DevBuf<uint16_t> base_bits;      // per tile 512 B each: the delimiters that end a base line, ...
+    DevBuf<uint16_t> start_bits;     // ... those behind which a block starts, ...
+    DevBuf<uint16_t> end_bits;       // ... and those that end a block
+    DevBuf<uint32_t> tile_cs;        // per tile 4 words: delimiters, base lines, its first base line, 1 + its last (tile-local)
+    DevBuf<uint64_t> tile_lctx;      // per tile 3 words: its first line, 1 + the last base line before it, the first behind it
+    DevBuf<uint32_t> tile_cnt;       // per tile its block starts and ends, and ...
+    DevBuf<uint32_t> tile_rank;      // ... those of the group's tiles before it
+    DevBuf<uint64_t> ring;           // kCRing line starts
+    DevBuf<uint64_t> words;          // kXw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint64_t> win[4];         // the stream form's window: starts, first lines, ends, last lines
+    DevBuf<uint64_t> lines;          // the host form's first lines
+    uint64_t grep_bytes = 0, extra_bytes = 0;   // what the call reserved of the grep's scratch and beside it
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -786,6 +860,7 @@ struct fcx_dctx {
     fcx::GrepScratch gp;
     fcx::RangesScratch rq;
     fcx::SetScratch ps;
+    fcx::ContextScratch cx;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

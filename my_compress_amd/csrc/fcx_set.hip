@@ -468,6 +468,31 @@ int set_args(const char *fn, const fcx_pattern_set *set, int delim) {
     return FCX_OK;
 }
 
+// ---- what the blocks calls (fcx_context.hip) take from here: the one scan path and its scratch ----
+int context_ready(fcx_dctx *c, const fcx_pattern_set *set, bool fresh, hipStream_t st) {
+    FCX_TRY(ready_grep(c));
+    return ready_set(c, set, fresh, st);
+}
+int context_reserve(fcx_dctx *c, uint64_t range_bytes) { return reserve_grep_tiles(c, range_bytes); }
+int context_scan(fcx_dctx *c, const fcx_pattern_set *set, uint8_t delim, const uint8_t *src, uint64_t len, bool final,
+                 uint32_t *ntiles, hipStream_t st) {
+    GrepScratch &G = c->gp;
+    SetScratch &S = c->ps;
+    // (grep_scan's rule: hit bits and delimiter bits over the same positions, each seen by exactly one range)
+    const uint64_t njudged = set_njudged(set, len, final), ndelim = final ? len : njudged;
+    *ntiles = (uint32_t)((ndelim + kSTile - 1) / kSTile);
+    if (*ntiles)
+        hipLaunchKernelGGL(k_sscan<true>, dim3(std::min(*ntiles, kSMaxGrid)), dim3(kSThreads), 0, st, src, len, njudged, ndelim,
+                           set->max_len, set->flags & FCX_SET_FOLD_ASCII, (uint32_t)delim, (const uint32_t *)S.block, *ntiles,
+                           (uint16_t *)G.hit_bits, (uint16_t *)G.delim_bits, (uint32_t *)G.tile_sum, (uint64_t *)G.words + kGwJudged,
+                           (uint64_t *)G.words + kGwHits, (uint64_t *)S.words);
+    S.stats[4]++;
+    if (final) S.stats[5]++;
+    return FCX_OK;
+}
+int context_fetch(fcx_dctx *c, hipStream_t st) { return set_fetch(c, st); }
+void context_publish(fcx_dctx *c, const fcx_pattern_set *set, uint64_t *counts) { set_publish(c, set, counts); }
+
 int find_set_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const fcx_pattern_set *set,
                  uint64_t base, const FindSink &sink, bool last, uint64_t *nhits, uint64_t *decoded, uint64_t *counts, hipStream_t st,
                  uint64_t rec_base) {
