@@ -888,6 +888,58 @@ int fcx_grep_blocks_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, uint
                          const fcx_grep_opts *opts, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats,
                          uint64_t *counts);
 
+/* ---- regular-expression grep: grep -E with -v, -A, -B, -C on a run (FCX7 and FCX8) ---------------------------
+ * The expression is a subset of POSIX ERE over bytes (LC_ALL=C), compiled on the host into a DFA of at most
+ * FCX_REGEX_MAX_STATES states over byte classes.  The delimiter d is fixed at compile time, since `.` and negated
+ * sets exclude it; the grep calls take no delimiter of their own.
+ *   literal bytes; \ and a punctuation byte as that byte; . (any byte but d)
+ *   [...] and [^...] with ranges and [:alpha:] [:digit:] [:alnum:] [:upper:] [:lower:] [:space:] [:punct:]
+ *   [:xdigit:] (inside a set a backslash is a backslash, as in POSIX); a negated set never matches d
+ *   \w \W \s \S        ( ) and |        * + ? {m} {m,} {m,n} with n <= 255
+ *   ^ only as the first and $ only as the last item of a top-level alternative (which the whole expression is
+ *   when it has no top-level |)
+ * FCX_ERR_ARG, the message naming the offset: a back-reference, \b \B \< \>, any other escape of a letter or digit,
+ * an anchor elsewhere, an empty alternative or group, {0} and {0,0}, d as a literal or inside a range or single byte of a set
+ * that is not negated (with the fold flag: also a byte that folds to what d folds to; the named classes and the
+ * shorthands leave d out instead), an expression that matches the empty string (a*, ^$: it would select every
+ * line, and an empty line has no position to carry a hit), more than 1024 positions after expanding the counted
+ * repetitions, more than 4096 states during subset construction, more than FCX_REGEX_MAX_STATES after
+ * minimisation.  With FCX_SET_FOLD_ASCII letters of literals and sets match both ASCII cases (bytes >= 0x80
+ * never fold): in the byte classes, the scan reads the bytes as they are.
+ * Semantics.  D, T, d and the lines s_j / e_j are those of the line calls; the body of line j is D[s_j, b_j) with
+ * b_j = e_j - 1 if the line is terminated and e_j otherwise.  A position p, s_j <= p < b_j, is a hit iff for some
+ * top-level alternative A and some q: s_j <= q <= p, D[q..p] is in L(A), q == s_j if A begins with ^, and
+ * p == b_j - 1 if A ends with $.  A hit is the position at which a match ends, always a byte of the matching line
+ * that is not d.  A line matches iff it holds a hit; base lines, selected lines, blocks and the eight stats are
+ * those of the blocks calls above, `hits` the number of hit positions, `judged` T after a whole run.  The answer
+ * does not depend on record, tile, decode-group or stream-group boundaries. */
+#define FCX_REGEX_MAX_PATTERN 1024u   /* bytes of the expression */
+#define FCX_REGEX_MAX_STATES  64u     /* DFA states after minimisation, dead state included */
+#define FCX_REGEX_SCAN_STATS  4       /* judged, hits, groups, final passes */
+typedef struct fcx_regex fcx_regex;
+/* flags: FCX_SET_FOLD_ASCII or 0.  *re is NULL on failure. */
+int  fcx_regex_create(fcx_regex **re, const uint8_t *expr, uint32_t len, uint8_t delim, uint32_t flags);
+void fcx_regex_destroy(fcx_regex *re);
+/* any of the outputs may be NULL: DFA states, byte classes, the flags, the delimiter */
+int  fcx_regex_info(const fcx_regex *re, uint32_t *states, uint32_t *classes, uint32_t *flags, uint8_t *delim);
+/* fcx_grep_blocks_shard / _stream / _host with a regex for the set, its delimiter, and no counts array: the same
+ * argument checks before the device is touched, cap rule and size query, nblocks == 0 touching no device, 4 GiB
+ * group refusal, stage table (index, decode, scan, select, summary), held-back open block in the stream form and
+ * chaining into the multi-range decode in the host form.  With zero options the blocks are the matching lines
+ * of grep -E, runs of adjacent ones merged, and `selected lines` is their count.  Between groups one byte ($
+ * looks one byte ahead) and the DFA state in front of it stay on the device.  Scratch beside the blocks calls'
+ * (fcx_dctx_grep_scratch counts it): states + 1 bytes per tile of a decode group. */
+int fcx_grep_regex_blocks_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                                const fcx_regex *re, const fcx_grep_opts *opts, uint64_t *d_start, uint64_t *d_end,
+                                uint64_t *d_line, uint64_t cap, uint64_t *stats, void *stream);
+int fcx_grep_regex_blocks_stream(fcx_dctx *ctx, fcx_read_fn read_comp, void *user_comp, uint64_t max_in, const fcx_regex *re,
+                                 const fcx_grep_opts *opts, fcx_block_fn on_block, void *user_block, uint64_t *stats);
+int fcx_grep_regex_blocks_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const fcx_regex *re, const fcx_grep_opts *opts,
+                               uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats);
+/* counters of the last regex call (the stream form: of the whole file), min(n, FCX_REGEX_SCAN_STATS) values:
+ * positions judged, hits, ranges scanned, final passes */
+int fcx_dctx_regex_scan_stats(fcx_dctx *ctx, uint64_t *out, int n);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

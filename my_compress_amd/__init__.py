@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "grep_context", "grep_context_blocks", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "grep_context", "grep_context_blocks", "Regex", "grep_regex", "grep_regex_blocks", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -241,6 +241,20 @@ def lib():
                                              ctypes.c_void_p, BLOCK_FN, ctypes.c_void_p, P64, P64]
         L.fcx_grep_blocks_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
                                            c_u8p, ctypes.c_uint64, P64, P64, P64]
+    if hasattr(L, "fcx_grep_regex_blocks_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]
+        P32 = ctypes.POINTER(ctypes.c_uint32)
+        L.fcx_regex_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), c_u8p, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint32]
+        L.fcx_regex_destroy.argtypes = [ctypes.c_void_p]
+        L.fcx_regex_destroy.restype = None
+        L.fcx_regex_info.argtypes = [ctypes.c_void_p, P32, P32, P32, ctypes.POINTER(ctypes.c_uint8)]
+        L.fcx_grep_regex_blocks_shard.argtypes = run + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_uint64, P64, ctypes.c_void_p]
+        L.fcx_grep_regex_blocks_stream.argtypes = [ctypes.c_void_p, READ_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_void_p, BLOCK_FN, ctypes.c_void_p, P64]
+        L.fcx_grep_regex_blocks_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, c_u8p,
+                                                 ctypes.c_uint64, P64, P64]
+        L.fcx_dctx_regex_scan_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -1082,6 +1096,57 @@ class DContext:
                                             counts), "fcx_grep_blocks_stream")
         return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), got, [int(v) for v in counts]
 
+    # ---- regular-expression grep (fcx_grep_regex_blocks_*): grep -E with -v / -A / -B / -C; the delimiter is the regex's ----
+    REGEX_SCAN_STATS = ("judged", "hits", "groups", "final_passes")
+
+    def grep_regex_blocks_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, regex: "Regex", invert: bool = False,
+                                before: int = 0, after: int = 0, d_start: int = 0, d_end: int = 0, d_line: int = 0, cap: int = 0,
+                                stream: int = 0) -> dict:
+        """grep_blocks_shard with a Regex for the set: the blocks of the lines in which a match of `regex` ends.  Returns
+        GREP_BLOCK_STATS; start, end and first line of the first min(cap, blocks) go to d_start / d_end / d_line"""
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        opts = self._opts(invert, before, after)
+        _check(lib().fcx_grep_regex_blocks_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, regex.handle,
+                                                 ctypes.byref(opts), ctypes.c_void_p(d_start or None), ctypes.c_void_p(d_end or None),
+                                                 ctypes.c_void_p(d_line or None), cap, vals, ctypes.c_void_p(stream)),
+               "fcx_grep_regex_blocks_shard")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals]))
+
+    def grep_regex_blocks_host(self, blob: bytes, regex: "Regex", invert: bool = False, before: int = 0, after: int = 0):
+        """a whole FCX7 or FCX8 file in memory -> (stats, the blocks' bytes concatenated): grep -E with -v, -B and -A,
+        without the `--` lines; found and gathered on the GPU, only the blocks' bytes come back"""
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        need = ctypes.c_uint64(0)
+        opts = self._opts(invert, before, after)
+        args = (self._h, blob, len(blob), regex.handle, ctypes.byref(opts))
+        rc = lib().fcx_grep_regex_blocks_host(*args, None, 0, ctypes.byref(need), vals)   # the size
+        if rc != -2:
+            _check(rc, "fcx_grep_regex_blocks_host")
+            return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), b""
+        out = ctypes.create_string_buffer(need.value)
+        _check(lib().fcx_grep_regex_blocks_host(*args, out, need.value, ctypes.byref(need), vals), "fcx_grep_regex_blocks_host")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), out.raw[:need.value]
+
+    def grep_regex_blocks_stream(self, src, regex: "Regex", invert: bool = False, before: int = 0, after: int = 0, max_in: int = 0,
+                                 want_blocks: bool = True):
+        """an FCX7 or FCX8 file from src (binary reader) -> (stats, [(start, end, line, nlines)] of every block, ascending,
+        each once and with its true end); want_blocks False: the totals alone"""
+        rd, _ = _stream_fns(src, None)
+        got = []
+        cb = BLOCK_FN(lambda _u, s, e, ln, n: got.append((int(s), int(e), int(ln), int(n)))) if want_blocks else ctypes.cast(None, BLOCK_FN)
+        vals = (ctypes.c_uint64 * len(self.GREP_BLOCK_STATS))()
+        opts = self._opts(invert, before, after)
+        _check(lib().fcx_grep_regex_blocks_stream(self._h, rd, None, max_in, regex.handle, ctypes.byref(opts), cb, None, vals),
+               "fcx_grep_regex_blocks_stream")
+        return dict(zip(self.GREP_BLOCK_STATS, [int(v) for v in vals])), got
+
+    def regex_scan_stats(self) -> dict:
+        """counters of the last regex call (fcx_dctx_regex_scan_stats)"""
+        n = len(self.REGEX_SCAN_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_regex_scan_stats(self._h, vals, n), "fcx_dctx_regex_scan_stats")
+        return dict(zip(self.REGEX_SCAN_STATS, [int(v) for v in vals]))
+
     def set_scan_stats(self) -> dict:
         """counters of the last pattern-set call (fcx_dctx_set_scan_stats)"""
         n = len(self.SET_SCAN_STATS)
@@ -1399,6 +1464,72 @@ def grep_context_blocks(blob: bytes, patterns, delim=b"\n", ignore_case: bool = 
                                                                  max(0, len(blob) - HEADER_BYTES)))
     finally:
         ps.close()
+
+
+class Regex:
+    """a POSIX ERE subset over bytes compiled into a DFA of at most 64 states for the regex calls (fcx_regex_create; the
+    syntax and the refusals: include/fcx.h).  `delim` is fixed here, since `.` and negated sets exclude it; ignore_case
+    lets the letters of literals and sets match both ASCII cases"""
+    FOLD_ASCII = 1
+    MAX_PATTERN = 1024
+    MAX_STATES = 64
+
+    def __init__(self, expr: bytes, delim=0x0A, ignore_case: bool = False, flags: int = None):
+        expr = bytes(expr)
+        if isinstance(delim, (bytes, bytearray)):
+            if len(delim) != 1:
+                raise ValueError("delim is one byte")
+            delim = delim[0]
+        h = ctypes.c_void_p()
+        self._h = None
+        _check(lib().fcx_regex_create(ctypes.byref(h), expr or b"\0", len(expr), delim,
+                                      (self.FOLD_ASCII if ignore_case else 0) if flags is None else flags), "fcx_regex_create")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        v = [ctypes.c_uint32(0) for _ in range(3)]
+        d = ctypes.c_uint8(0)
+        _check(lib().fcx_regex_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(d)), "fcx_regex_info")
+        return dict(zip(("states", "classes", "flags", "delim"), [int(x.value) for x in v] + [int(d.value)]))
+
+    def close(self):
+        if self._h:
+            lib().fcx_regex_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def grep_regex(blob: bytes, expr: bytes, delim=b"\n", ignore_case: bool = False, invert: bool = False, before: int = 0, after: int = 0,
+               device: int = 0) -> bytes:
+    """grep -E (-i) (-v) -B before -A after over what `blob` decodes to: the bytes of the selected lines, in order, without
+    the `--` lines between blocks (grep_regex_blocks() says where the blocks are)"""
+    rx = Regex(expr, delim, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_regex_blocks_host(blob, rx, invert, before, after)[1])
+    finally:
+        rx.close()
+
+
+def grep_regex_blocks(blob: bytes, expr: bytes, delim=b"\n", ignore_case: bool = False, invert: bool = False, before: int = 0,
+                      after: int = 0, device: int = 0):
+    """(stats, [(start, end, line, nlines)]) of the blocks whose bytes grep_regex() returns, through the stream form"""
+    import io
+
+    rx = Regex(expr, delim, ignore_case)
+    try:
+        return _with_dctx(device, lambda c: c.grep_regex_blocks_stream(io.BytesIO(blob), rx, invert, before, after,
+                                                                       max(0, len(blob) - HEADER_BYTES)))
+    finally:
+        rx.close()
 
 
 def _with_dctx(device, fn):

@@ -97,6 +97,13 @@
 // line "--" goes between two runs of consecutive selected lines, as GNU grep prints it.  The last line printed is
 // "grep: K blocks, L lines, S base lines, B bytes, H hits, decoded bytes = T".  Usage errors: a value that is not a
 // number or lies above 4096; one of the four without a grep option.
+//
+// Regular expressions, decompress mode only (fcx_grep_regex_blocks_stream, then fcx_decompress_ranges_stream):
+//   --grep-regex EXPR the lines in which a match of the POSIX ERE subset of include/fcx.h ends (grep -E); with
+//                     --count, --delim HH, --ignore-case, --invert, --before / --after / --context N as --grep-set takes
+//                     them, and with its output and totals lines ("patterns: 1")
+// Usage errors: an expression the compiler refuses (the reason and the offset are printed first); --grep-regex twice or
+// with --find, --grep, their -hex and -set forms, --set-hex or --line-numbers.
 #include <getopt.h>
 
 #include <algorithm>
@@ -128,7 +135,8 @@ static int usage() {
             "[--find-set <pattern file> | --grep-set <pattern file> [--set-hex] [--count] (decompress only: up to 64 patterns, one a line)] "
             "[--ignore-case (with a search: ASCII letters match in either case)] "
             "[--invert] [--before <lines>] [--after <lines>] [--context <lines>] (with a grep: the lines without a pattern, "
-            "lines of context, at most 4096)\n");
+            "lines of context, at most 4096) "
+            "[--grep-regex <POSIX ERE> [--count] (decompress only: the lines in which a match ends, to -o)]\n");
     return -1;
 }
 
@@ -891,6 +899,58 @@ static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_s
     return fcx_cli::grep_blocks_totals(stats[0], stats[1], stats[3], stats[2], stats[4], stats[6]);
 }
 
+// --grep-regex: do_grep_blocks for a regex; without --invert, --before, --after or --context the totals are the set grep's
+static int do_grep_regex(FILE *fin, FILE *fout, int device, const fcx_regex *re, const fcx_regex &host_re, const fcx_grep_opts &opts,
+                         bool blocks_form) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_grep_regex(fin, nblocks, host_re, opts, blocks_form, fout, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_GREP_BLOCK_STATS] = {}, got = 0;
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    BlockOut io{fin, fout, {}, {}, fcx_cli::block_separator(opts)};
+    const fcx_block_fn keep = [](void *u, uint64_t s, uint64_t e, uint64_t, uint64_t) {
+        ((BlockOut *)u)->starts.push_back(s);
+        ((BlockOut *)u)->ends.push_back(e);
+    };
+    int r = fcx_grep_regex_blocks_stream(d, file_read, fin, max_in, re, &opts, fout ? keep : nullptr, &io, stats);
+    if (r == FCX_OK && fout && !io.starts.empty()) {
+        rewind(fin);
+        r = fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(), io.starts.size(),
+                                         &got);
+        if (r == FCX_OK && got != stats[2]) {
+            fprintf(stderr, "fcx: the blocks' bytes disagree with the grep's sum\n");
+            fcx_dctx_destroy(d);
+            return -1;
+        }
+    }
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return blocks_form ? fcx_cli::grep_blocks_totals(stats[0], stats[1], stats[3], stats[2], stats[4], stats[6])
+                       : fcx_cli::grep_set_totals(stats[1], stats[2], stats[4], stats[6], 1);
+}
+
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
     uint8_t hdr[FCX_HEADER_BYTES];
     if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
@@ -988,6 +1048,7 @@ int main(int argc, char **argv) {
                                            {"before", required_argument, nullptr, 1006},
                                            {"after", required_argument, nullptr, 1007},
                                            {"context", required_argument, nullptr, 1008},
+                                           {"grep-regex", required_argument, nullptr, 1009},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -1004,7 +1065,8 @@ int main(int argc, char **argv) {
     bool count_lines = false, lines = false, line_numbers = false, delim_given = false;
     uint64_t line_first = 0, line_count = 0;
     uint8_t delim = 0x0A;
-    std::string find_set, grep_set;
+    std::string find_set, grep_set, grep_regex;
+    bool regex_given = false;
     bool set_hex = false, ignore_case = false;
     fcx_grep_opts gopts = {0, 0, 0};
     bool blocks = false;   // --invert, --before, --after or --context seen
@@ -1078,10 +1140,33 @@ int main(int argc, char **argv) {
             blocks = true;
             break;
         }
+        case 1009:
+            if (regex_given) return usage();
+            grep_regex = optarg;
+            regex_given = true;
+            break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
+    // --grep-regex: a grep of its own kind; the expression is compiled once the delimiter is known
+    std::unique_ptr<fcx_regex, void (*)(fcx_regex *)> regex_own(nullptr, fcx_regex_destroy);
+    std::unique_ptr<fcx_regex> host_regex;
+    if (regex_given) {
+        if (finds || greps || !find_set.empty() || !grep_set.empty() || set_hex || line_numbers) return usage();
+        host_regex.reset(new fcx_regex());
+        const std::string why = fcx::regex_compile(host_regex.get(), (const uint8_t *)grep_regex.data(), (uint32_t)grep_regex.size(), delim,
+                                                   ignore_case ? FCX_SET_FOLD_ASCII : 0u);
+        if (!why.empty()) {
+            fprintf(stderr, "--grep-regex: %s\n", why.c_str());
+            return usage();
+        }
+        fcx_regex *re = nullptr;
+        if (fcx_regex_create(&re, (const uint8_t *)grep_regex.data(), (uint32_t)grep_regex.size(), delim, ignore_case ? FCX_SET_FOLD_ASCII : 0u))
+            return usage();
+        regex_own.reset(re);
+        greps++;
+    }
     // the set options: a set file stands for --find or --grep in every rule below
     const bool set_file = !find_set.empty() || !grep_set.empty();
     if ((!find_set.empty() && !grep_set.empty()) || (set_file && (finds || greps)) || (set_hex && !set_file)) return usage();
@@ -1093,7 +1178,7 @@ int main(int argc, char **argv) {
     std::unique_ptr<fcx_pattern_set, void (*)(fcx_pattern_set *)> pset_own(nullptr, fcx_pattern_set_destroy);
     std::unique_ptr<fcx_pattern_set> host_set;
     fcx_pattern_set *pset = nullptr;
-    if (set_file || ignore_case || blocks) {
+    if (!regex_given && (set_file || ignore_case || blocks)) {
         std::vector<uint8_t> sbytes;
         std::vector<uint32_t> slens;
         if (set_file) {
@@ -1149,7 +1234,8 @@ int main(int argc, char **argv) {
         return r;
     }
     if (greps) {
-        const int r = blocks ? do_grep_blocks(fin, fout, device, pset, *host_set, delim, gopts)
+        const int r = regex_given ? do_grep_regex(fin, fout, device, regex_own.get(), *host_regex, gopts, blocks)
+                      : blocks ? do_grep_blocks(fin, fout, device, pset, *host_set, delim, gopts)
                       : pset ? do_grep_set(fin, fout, device, pset, *host_set, delim)
                              : do_grep(fin, fout, device, grep_pattern, delim);
         fclose(fin);

@@ -1,9 +1,10 @@
 // fcx_cli_host.h — the command line's no-device paths over an FCX7 file: the host decoder
 // (fcx_decode.cpp) record by record, for the whole decompress, --list, --range, --compare, --repair, --digest, --find,
-// --count-lines, --lines, --grep, --find-set, --grep-set and the context grep (--invert, --before, --after).  Host code
+// --count-lines, --lines, --grep, --find-set, --grep-set, the context grep (--invert, --before, --after) and --grep-regex.  Host code
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
-// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp, tools/context_host_check.cpp).
+// tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp, tools/context_host_check.cpp,
+// tools/regex_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -18,6 +19,7 @@
 #include "fcx_crc32.h"
 #include "fcx_digest_file.h"
 #include "fcx_patset.h"
+#include "fcx_regex.h"
 #include "fcx_repair_file.h"
 
 namespace fcx_cli {
@@ -875,6 +877,89 @@ inline int host_grep_blocks(FILE *fin, uint16_t nblocks, uint8_t delim, const fc
     }
     for (uint32_t k = 0; k < S.npat && counts; k++) counts[k] = per[k];
     return grep_blocks_totals(blocks, lines, base, bytes, hits, pos);
+}
+
+// ---- --grep-regex: the host path ----
+// The regex grep without a device: host_grep_blocks with the compiled table (fcx_regex.h) run byte by byte over every
+// closed line in the place of the set's compare; the delimiter is the regex's.  A position is a hit when the state
+// behind its byte is in acc, or in acc_eol with the delimiter or the line's end behind it.  `blocks`: the options were
+// given, so the totals are the context grep's (and block_separator() goes between blocks); otherwise the set grep's
+// with one pattern.  stats (6 values, may be null): blocks, lines, base lines, bytes, hits, decoded bytes.
+inline int host_grep_regex(FILE *fin, uint16_t nblocks, const fcx_regex &R, const fcx_grep_opts &opts, bool blocks_form, FILE *fout,
+                           uint64_t *stats) {
+    std::vector<uint8_t> line;               // the open line so far
+    std::vector<std::vector<uint8_t>> wait;  // the unselected lines right in front of the open one, opts.before at most
+    const std::string sep = block_separator(opts);
+    const bool invert = (opts.flags & FCX_GREP_INVERT) != 0;
+    const uint8_t delim = R.delim;
+    uint64_t pos = 0, blocks = 0, lines = 0, base = 0, bytes = 0, hits = 0, after_left = 0;
+    uint64_t dropped = 0;   // lines since the last written one that no longer wait: a line written behind them starts a block
+    bool failed = false;
+    auto put = [&](const std::vector<uint8_t> &l) {
+        if (lines == 0 || dropped) {
+            if (blocks && fout && !sep.empty() && fwrite(sep.data(), 1, sep.size(), fout) != sep.size()) failed = true;
+            blocks++;
+        }
+        dropped = 0;
+        lines++;
+        bytes += l.size();
+        if (fout && fwrite(l.data(), 1, l.size(), fout) != l.size()) failed = true;
+    };
+    auto close_line = [&]() {
+        uint64_t h = 0;
+        const uint64_t len = line.size(), body = len && line[len - 1] == delim ? len - 1 : len;
+        uint8_t st = (uint8_t)R.start;
+        for (uint64_t p = 0; p < body; p++) {
+            st = R.step(st, line[p]);
+            h += R.hit(st, p + 1 == body);
+        }
+        hits += h;
+        if ((h != 0) != invert) {
+            base++;
+            for (const std::vector<uint8_t> &w : wait) put(w);
+            wait.clear();
+            put(line);
+            after_left = opts.after;
+        } else if (after_left) {
+            put(line);
+            after_left--;
+        } else if (opts.before == 0) {
+            dropped++;
+        } else {
+            if (wait.size() == opts.before) {
+                wait.erase(wait.begin());
+                dropped++;
+            }
+            wait.push_back(line);
+        }
+        line.clear();
+    };
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        for (uint64_t p = 0; p < n;) {
+            const uint8_t *at = (const uint8_t *)memchr(plain + p, delim, (size_t)(n - p));
+            const uint64_t q = at ? (uint64_t)(at - plain) + 1 : n;   // the line's bytes in this record end here
+            line.insert(line.end(), plain + p, plain + q);
+            if (at) close_line();
+            p = q;
+        }
+        pos += n;
+        return !failed;
+    });
+    if (r) return r;
+    if (!line.empty()) close_line();   // the unterminated tail is a line
+    if (failed) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (stats) {
+        stats[0] = blocks;
+        stats[1] = lines;
+        stats[2] = base;
+        stats[3] = bytes;
+        stats[4] = hits;
+        stats[5] = pos;
+    }
+    return blocks_form ? grep_blocks_totals(blocks, lines, base, bytes, hits, pos) : grep_set_totals(lines, bytes, hits, pos, 1);
 }
 
 }  // namespace fcx_cli

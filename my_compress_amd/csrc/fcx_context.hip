@@ -52,11 +52,6 @@ constexpr uint32_t kCCs = 4, kCLctx = 3;          // words per tile of tile_cs /
 constexpr uint32_t kCWindow = 1u << 20;           // blocks per window of the stream form by default
 constexpr uint64_t kCMaxRange = 0xFFFF0000ull;    // bytes of [carry | group] at most
 
-struct CxOut {
-    uint64_t *d_start, *d_end, *d_line;
-    uint64_t cap;
-};
-
 // exclusive prefix of v over the tile's 256 lanes (every thread calls it; sN: kCWaves words)
 __device__ inline uint32_t tile_xscan(uint32_t v, uint32_t *sN) {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -524,6 +519,7 @@ __global__ void k_cfinish(uint64_t *__restrict__ words, const uint64_t *__restri
 namespace {
 const char *kCStageNames[] = {"index", "decode", "scan", "select", "summary"};
 constexpr int kCStages = 5;
+}  // namespace
 
 int ready_context(fcx_dctx *c) {
     ContextScratch &C = c->cx;
@@ -573,6 +569,7 @@ void host_resolved(const BlockSink &sink, BlockCarry *carry, const uint64_t *hw)
     if (hw[kXwFinEnd]) host_close(sink, carry, hw[kXwFinEnd + 1], hw[kXwFinEnd + 2]);
 }
 
+namespace {
 // One range of a blocks call: scan, the select kernels, the first cap blocks or the windows of the stream form with
 // the open block held back; the carry for the range behind it.
 int blocks_scan(fcx_dctx *c, const fcx_pattern_set *set, uint8_t delim, const fcx_grep_opts &opts, const uint8_t *src, uint64_t len,
@@ -645,6 +642,7 @@ int blocks_scan(fcx_dctx *c, const fcx_pattern_set *set, uint8_t delim, const fc
     }
     return FCX_OK;
 }
+}  // namespace
 
 // the eight stats from the words (the caller has synchronised)
 void blocks_stats_out(fcx_dctx *c, uint64_t total, uint64_t *stats) {
@@ -659,6 +657,7 @@ void blocks_stats_out(fcx_dctx *c, uint64_t total, uint64_t *stats) {
     stats[7] = w[kXwTotal];
 }
 
+namespace {
 // the run's end on the device, and the words to the host
 int blocks_finish(fcx_dctx *c, const fcx_grep_opts &opts, const BlockSink &sink, uint64_t total, hipStream_t st) {
     GrepScratch &G = c->gp;

@@ -824,6 +824,60 @@ struct ContextScratch {
     uint64_t grep_bytes = 0, extra_bytes = 0;   // what the call reserved of the grep's scratch and beside it
 };
 
+// what the select kernels write through: the first cap blocks of a call
+struct CxOut {
+    uint64_t *d_start, *d_end, *d_line;
+    uint64_t cap;
+};
+
+// ---- regular-expression grep (fcx_regex.hip): its own scan stage (k_rmap, k_rentry, k_rmark) in front
+// of k_gtiles and the select stage of fcx_context.hip, whose kernels and host helpers it launches and calls as they
+// are ----
+__global__ void k_cbase(const uint16_t *__restrict__ hit_bits, const uint16_t *__restrict__ delim_bits,
+                        const uint32_t *__restrict__ tile_sum, const uint64_t *__restrict__ gctx, uint32_t ntiles, uint64_t pos_base,
+                        uint32_t invert, uint16_t *__restrict__ base_bits, uint32_t *__restrict__ tile_cs);
+__global__ void k_clines(const uint32_t *__restrict__ tile_cs, uint32_t ntiles, uint32_t before, uint32_t after,
+                         uint64_t *__restrict__ tile_lctx, uint64_t *__restrict__ words, const uint64_t *__restrict__ ring, CxOut out);
+__global__ void k_cmark(const uint16_t *__restrict__ delim_bits, const uint16_t *__restrict__ base_bits,
+                        const uint32_t *__restrict__ tile_cs, const uint64_t *__restrict__ tile_lctx, uint32_t ntiles, uint64_t pos_base,
+                        uint32_t before, uint32_t after, uint16_t *__restrict__ start_bits, uint16_t *__restrict__ end_bits,
+                        uint32_t *__restrict__ tile_cnt, uint64_t *__restrict__ words, uint64_t *__restrict__ ring);
+__global__ void k_cscan(const uint32_t *__restrict__ tile_cnt, uint32_t ntiles, uint32_t *__restrict__ tile_rank,
+                        uint64_t *__restrict__ words);
+__global__ void k_cwrite(const uint16_t *__restrict__ delim_bits, const uint16_t *__restrict__ start_bits,
+                         const uint16_t *__restrict__ end_bits, const uint32_t *__restrict__ tile_cnt,
+                         const uint32_t *__restrict__ tile_rank, const uint64_t *__restrict__ tile_lctx, uint32_t ntiles,
+                         const uint64_t *__restrict__ words, uint64_t pos_base, uint32_t local, uint64_t win_s, uint64_t win_e,
+                         uint64_t winlen, uint64_t *__restrict__ o_start, uint64_t *__restrict__ o_line, uint64_t *__restrict__ o_end,
+                         uint64_t *__restrict__ o_eline);
+__global__ void k_cfinish(uint64_t *__restrict__ words, const uint64_t *__restrict__ gwords, const uint64_t *__restrict__ ring,
+                          uint32_t before, uint32_t after, uint32_t invert, uint64_t total, CxOut out);
+int ready_context(fcx_dctx *c);
+int reserve_context_tiles(fcx_dctx *c, uint64_t range_bytes);
+CxOut out_of(const BlockSink &sink);
+void host_close(const BlockSink &sink, BlockCarry *carry, uint64_t end, uint64_t eline);
+void host_open(BlockCarry *carry, uint64_t start, uint64_t line);
+void host_resolved(const BlockSink &sink, BlockCarry *carry, const uint64_t *hw);
+void blocks_stats_out(fcx_dctx *c, uint64_t total, uint64_t *stats);
+
+// fcx_grep_regex_blocks_shard behind its argument checks, shaped as blocks_run and blocks_final
+int regex_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const fcx_regex *re,
+              const fcx_grep_opts &opts, const BlockSink &sink, BlockCarry *carry, uint64_t *stats, hipStream_t st, uint64_t rec_base);
+int regex_final(fcx_dctx *c, const fcx_regex *re, const fcx_grep_opts &opts, const BlockSink &sink, BlockCarry *carry, uint64_t *stats,
+                hipStream_t st);
+// the argument checks the three entry points share
+int regex_args(const char *fn, const fcx_regex *re, const fcx_grep_opts *opts);
+
+// scratch of the regex calls beside the grep's (gp) and the blocks calls' (cx)
+struct RegexScratch {
+    DevBuf<uint8_t> block;           // the compiled regex (fcx_regex.h)
+    DevBuf<uint8_t> tile_map;        // per tile the map state -> state of its positions, `states` bytes each
+    DevBuf<uint8_t> tile_entry;      // per tile the state in front of its first position
+    DevBuf<uint32_t> state;          // the state in front of the next range's first judged position
+    uint64_t tile_bytes = 0;         // what the call reserved of the two tile arrays (part of fcx_dctx_grep_scratch)
+    uint64_t stats[FCX_REGEX_SCAN_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -861,6 +915,7 @@ struct fcx_dctx {
     fcx::RangesScratch rq;
     fcx::SetScratch ps;
     fcx::ContextScratch cx;
+    fcx::RegexScratch rx;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

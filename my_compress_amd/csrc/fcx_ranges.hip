@@ -561,4 +561,46 @@ int fcx_grep_blocks_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, uint8_
     return fetch_out(c, out, got);
 }
 
+// fcx_grep_blocks_host with the regex's run function
+int fcx_grep_regex_blocks_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, const fcx_regex *re, const fcx_grep_opts *opts,
+                               uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats) {
+    if (!c || !in || !re || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_grep_regex_blocks_host: NULL argument");
+    FCX_TRY(regex_args("fcx_grep_regex_blocks_host", re, opts));
+    char kind = 0;
+    uint32_t nblocks = 0;
+    uint64_t rec_len = 0;
+    FCX_TRY(walk_file(in, in_len, &kind, &nblocks, &rec_len));
+    uint64_t gs[FCX_GREP_BLOCK_STATS] = {};
+    *out_len = 0;
+    for (int i = 0; i < FCX_GREP_BLOCK_STATS && stats; i++) stats[i] = 0;
+    BlockSink sink;
+    if (nblocks == 0) return regex_run(c, kind, nullptr, 0, 0, re, *opts, sink, nullptr, gs, nullptr, 0);
+    RangesScratch &Q = c->rq;
+    FCX_TRY(stage_file(c, in, rec_len));
+    // room for the blocks: what the context holds already or a guess, and once more when the run has more
+    uint64_t room = std::max<uint64_t>(std::min({Q.starts.bytes, Q.ends.bytes, c->cx.lines.bytes}) / 8, kQGuessLines);
+    for (int pass = 0; pass < 2; pass++) {
+        FCX_TRY(Q.starts.reserve(8 * room, "ranges"));
+        FCX_TRY(Q.ends.reserve(8 * room, "ranges"));
+        FCX_TRY(c->cx.lines.reserve(8 * room, "ranges"));
+        sink.d_start = Q.starts;
+        sink.d_end = Q.ends;
+        sink.d_line = c->cx.lines;
+        sink.cap = room;
+        FCX_TRY(regex_run(c, kind, Q.file, rec_len, nblocks, re, *opts, sink, nullptr, gs, nullptr, 0));
+        if (gs[0] <= room) break;
+        room = gs[0];
+    }
+    for (int i = 0; i < FCX_GREP_BLOCK_STATS && stats; i++) stats[i] = gs[i];
+    *out_len = gs[2];
+    if (gs[2] > cap) return fail(FCX_ERR_CAPACITY, "fcx_grep_regex_blocks_host: output capacity too small");
+    if (gs[2] == 0) return FCX_OK;
+    FCX_TRY(Q.out.reserve(gs[2], "ranges output"));
+    uint64_t got = 0;
+    FCX_TRY(ranges_run(c, kind, Q.file, rec_len, nblocks, c->rg.rec_off, c->rg.dec_off, Q.starts, Q.ends, gs[0], Q.out, gs[2], &got,
+                       nullptr));
+    if (got != gs[2]) return fail(FCX_ERR_INTERNAL, "fcx_grep_regex_blocks_host: the blocks' bytes disagree with the sum");
+    return fetch_out(c, out, got);
+}
+
 }  // extern "C"

@@ -1072,6 +1072,32 @@ int fcx_grep_blocks_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t 
     return FCX_OK;
 }
 
+// ---- regular-expression grep (include/fcx.h): fcx_grep_blocks_stream with the regex's run functions ----
+int fcx_grep_regex_blocks_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uint64_t max_in, const fcx_regex *re,
+                                 const fcx_grep_opts *opts, fcx_block_fn on_block, void *user_block, uint64_t *stats) {
+    if (!dctx || !rd || !re) return fail(FCX_ERR_ARG, "fcx_grep_regex_blocks_stream: NULL argument");
+    FCX_TRY(fcx::regex_args("fcx_grep_regex_blocks_stream", re, opts));
+    BlockSink sink;
+    sink.on_block = on_block;
+    sink.user = user_block;
+    BlockCarry carry;
+    uint64_t gs[FCX_GREP_BLOCK_STATS] = {};
+    hipStream_t last_st = nullptr;
+    bool any = false;
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t, uint64_t before, hipStream_t st) -> int {
+        last_st = st;
+        any = true;
+        return fcx::regex_run(dctx, lz78 ? '8' : '7', x.din, used, nb, re, *opts, sink, &carry, gs, st, before);
+    });
+    if (r) return r;
+    if (any) FCX_TRY(fcx::regex_final(dctx, re, *opts, sink, &carry, gs, last_st));
+    else FCX_TRY(fcx::regex_run(dctx, '7', nullptr, 0, 0, re, *opts, sink, &carry, gs, nullptr, 0));
+    gs[6] = carry.base;
+    for (int i = 0; i < FCX_GREP_BLOCK_STATS && stats; i++) stats[i] = gs[i];
+    return FCX_OK;
+}
+
 int fcx_decompress_ranges_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
                                  const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *out_len) {
     if (!dctx || !rd || !wr || (n && (!starts || !ends))) return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: NULL argument");
