@@ -14,6 +14,7 @@
 #include "fcx_device.h"
 #include "fcx_host.h"
 #include "fcx_sparse_filter.h"
+#include "fcx_sparse_tail.h"
 
 using namespace fcx;
 
@@ -148,7 +149,7 @@ int ensure_scratch(fcx_ctx *c, uint64_t n) {
     FCX_TRY(c->chain_pfx.reserve(8ull * (kTile / 64) * nt, "chain_pfx"));
     FCX_TRY(c->tinfo.reserve(32 * nt, "tinfo"));
     FCX_TRY(c->tile_off.reserve(12 * (nt + 1), "tile_off"));   // (+1: k_emit reads tile tix + 1's)
-    FCX_TRY(c->mtok.reserve(4ull * kTileMatches * nt, "mtok"));
+    FCX_TRY(c->mtok.reserve(4ull * kTileMatches * nt + sparse_tail_bytes(nt), "mtok"));   // (+ the sparse unit's tail flags)
     FCX_TRY(c->tconv.reserve(4 * nt, "tconv"));
     FCX_TRY(c->fp.reserve(96 * nt, "fp"));   // 12 u64 per tile (k_resolve record)
     FCX_TRY(c->binfo.reserve(sizeof(BlockInfo) * nb, "binfo"));
@@ -210,6 +211,10 @@ int match_routed(fcx_ctx *c, const MatchArgs &ma, hipStream_t st, hipEvent_t *ev
         const MatchRoute launch = direct && plan.every ? MatchRoute{} : rt;
         kUnits[u].launch(ma, st, 0u, &launch, direct ? 0u : plan.grid[u]);
         c->last_grid[u] = plan.grid[u];
+        // the sparse unit's second phase right after a direct launch, which has every tile of its kind:
+        // over every tile of the shard it also flagged tiles of other kinds, whose own units search them
+        // again below and reuse their mtok slots
+        if (u == kRouteSparse && direct) launch_sparse_tail(ma, st);
     }
     c->last_kernel = est[kRouteUniform] > est[plan.best] ? kMatchUniform
                      : est[plan.best]                    ? kUnits[plan.best].kernel
@@ -221,6 +226,8 @@ int match_routed(fcx_ctx *c, const MatchArgs &ma, hipStream_t st, hipEvent_t *ev
         if (rs.none()) continue;
         const RouteRest rest{list_of(u), rc + u, rs.start, rs.word >= 0 ? rc + rs.word : nullptr};
         kUnits[u].rest(ma, rest, rts[u], kRestGrid, st);
+        // (listed, the sparse unit has its own tiles only: one tail launch after its remainder)
+        if (u == kRouteSparse) launch_sparse_tail(ma, st);
     }
     return FCX_OK;
 }
@@ -381,11 +388,14 @@ int fcx_compress_shard(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_o
     c->last_cold = routed && !c->hint.have;
     c->last_kernel = routed ? kMatchGeneral : c->kernel;
     FCX_HIP(hipMemsetAsync(c->dev_words, 0, kWordBytes, st));
-    if (ev) FCX_HIP(hipEventRecord(ev[0], st));   // (the memset above is not timed)
     const MatchArgs ma{d_in, L, c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok};
+    const bool tail = routed || c->kernel == kMatchSparse;   // the sparse unit may run: its tail flags start clear
+    if (tail) FCX_HIP(hipMemsetAsync(sparse_tail_head(ma.mtok, L.nblocks * L.tpb), 0, sparse_tail_flag_bytes(L.nblocks * L.tpb), st));
+    if (ev) FCX_HIP(hipEventRecord(ev[0], st));   // (the memsets above are not timed)
     if (!routed) {
         if (ev) FCX_HIP(hipEventRecord(ev[1], st));
         match_unit(c->kernel).launch(ma, st, c->match_mode, nullptr, 0);
+        if (tail) launch_sparse_tail(ma, st);
     } else {
         FCX_TRY(match_routed(c, ma, st, ev));
     }
@@ -476,8 +486,31 @@ int fcx_debug_match(fcx_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t dbg, v
     FCX_HIP(hipSetDevice(c->device));
     FCX_TRY(ensure_scratch(c, n));
     const MatchArgs ma{d_in, make_layout(n, c->B), c->m, c->mbits, c->chain, c->chain_pfx, c->tinfo, c->mtok};
+    // the sparse unit: its tail kernel follows unless the bits end the kernel at a phase (16, 4096, 32:
+    // staging, filter, search; 64: the end of phase 1, the tail flags written; 256-2048, 8192: the
+    // parse's and the run table's exits).  Bit 131072 keeps every tile's queries in the workgroup.
+    const bool tail = c->kernel == kMatchSparse;
+    if (tail)
+        FCX_HIP(hipMemsetAsync(sparse_tail_head(ma.mtok, ma.L.nblocks * ma.L.tpb), 0,
+                               sparse_tail_flag_bytes(ma.L.nblocks * ma.L.tpb), (hipStream_t)stream));
     match_unit(c->kernel).launch(ma, (hipStream_t)stream, dbg, nullptr, 0);
+    if (tail && !(dbg & (16u | 32u | 64u | 256u | 512u | 1024u | 2048u | 4096u | 8192u)))
+        launch_sparse_tail(ma, (hipStream_t)stream);
     FCX_HIP(hipGetLastError());
+    return FCX_OK;
+}
+
+// development only (not in fcx.h): the tiles of the last compress call that k_match_sparse left to its
+// tail kernel (the tail list's length; 0 when the sparse unit did not run)
+int fcx_debug_sparse_tail_count(fcx_ctx *c, uint64_t *listed) {
+    if (!c || !listed) return fail(FCX_ERR_ARG, "fcx_debug_sparse_tail_count: NULL");
+    *listed = 0;
+    if (!c->last.nblocks || !(c->last_routed || c->last_kernel == kMatchSparse)) return FCX_OK;
+    FCX_HIP(hipSetDevice(c->device));
+    FCX_HIP(hipDeviceSynchronize());
+    uint32_t n = 0;
+    FCX_HIP(hipMemcpy(&n, sparse_tail_head(c->mtok, c->last.nblocks * c->last.tpb), 4, hipMemcpyDeviceToHost));
+    *listed = n;
     return FCX_OK;
 }
 

@@ -91,6 +91,12 @@
 #endif
 #if FCX_SPARSE
 #include "fcx_sparse_filter.h"   // the unit's own repeat filter (sparse_pairs below)
+#include "fcx_sparse_tail.h"     // where a tile's second phase finds what the first left (k_sparse_tail)
+#endif
+// FCX_TAIL (fcx_sparse_tail.hip): this file's device functions under the sparse unit's switches, for
+// the tail kernel; no match kernel and no launcher of the unit is defined
+#ifndef FCX_TAIL
+#define FCX_TAIL 0
 #endif
 // FCX_NOBUCKET: no bucket search; a tile the repeat filter does not send to the sparse search takes
 // the whole-tile run-table mode (the sparse and runs units)
@@ -746,15 +752,30 @@ __device__ FCX_SPARSE_CALL void sparse_search(const uint32_t *sdw, uint32_t *reg
 // key in [x - 2047, x) as candidates, through scan_candidate.  No dup bitmap, no sort.
 // fm: this lane's flagged keys (bit r: window position 12 tid + r), fwave: its wave's flagged keys,
 // nflag: the window's (<= kSfFlagCap; their list and R entries are in place; the match words are 0
-// since the staging).  Writes step (LDS), m and the tile's mbits words like
-// sparse_search.  Returns false, with nothing of the tile written, when R overflows
-// (workgroup-uniform): the tile is not sparse.
+// since the staging).
+//
+// The eight-wave workgroup ends where its wide work ends.  After the search's barrier
+// R is final, and every wave reads it into its lanes and counts each in-tile entry's candidates -- the
+// R entries of its key bits in [x - 2047, x), what the queries below hand to scan_candidate -- so all
+// waves decide alike without another barrier:
+//   no candidate anywhere (6 random tiles in 10): all literals, which match_tile wrote before the
+//     filter; the tile is done (kSpDone);
+//   some, R within kTailR entries and no entry with more than kExtBudget of them (so no query can
+//     come out unknown): R goes to the tile's mtok slot and its length to the tile's tail flag;
+//     k_sparse_tail runs the queries and the parse with one wave (kSpDone, nothing else written);
+//   else (planted runs of one key; the development bits kSpStayBits): the queries run here -- step
+//     (LDS), m and the tile's mbits words written like sparse_search (kSpHere).
+// kSpNot, with nothing of the tile written, when R overflows (workgroup-uniform): the tile is not sparse.
+enum : uint32_t { kSpNot = 0, kSpHere = 1, kSpDone = 2 };
+constexpr uint32_t kSpStayBits = 1u | 2u | 65536u | 131072u;   // k_match<true>: no queries, no extension, no
+                                                               // sparse_parse; 131072: every tile's queries here
 template <bool kDev>
-__device__ __forceinline__ bool sparse_pairs(const uint32_t *sdw, uint32_t *region, uint32_t kw0, uint32_t kw1,
-                                             uint32_t kw2, uint32_t kw3, uint32_t fm, uint32_t fwave, uint32_t nflag,
-                                             uint32_t *s_np, uint32_t *s_unknown, uint32_t *s_match, uint32_t *mrow,
-                                             uint64_t *mbw, uint32_t q0, uint32_t npos, uint32_t ins_end, uint32_t w0,
-                                             uint32_t blen, uint32_t ntile, uint32_t dbg_in) {
+__device__ __forceinline__ uint32_t sparse_pairs(const uint32_t *sdw, uint32_t *region, uint32_t kw0, uint32_t kw1,
+                                                 uint32_t kw2, uint32_t kw3, uint32_t fm, uint32_t fwave, uint32_t nflag,
+                                                 uint32_t *s_np, uint32_t *s_unknown, uint32_t *s_match, uint32_t *mrow,
+                                                 uint64_t *mbw, uint32_t q0, uint32_t npos, uint32_t ins_end, uint32_t w0,
+                                                 uint32_t blen, uint32_t ntile, uint32_t dbg_in, uint32_t *mslot,
+                                                 uint8_t *tflag) {
     const uint32_t dbg = kDev ? uni(dbg_in) : 0u;
     const uint32_t tid = FCX_TID, lane = tid & 63;
     const uint32_t kw[4] = {kw0, kw1, kw2, kw3};
@@ -762,9 +783,6 @@ __device__ __forceinline__ bool sparse_pairs(const uint32_t *sdw, uint32_t *regi
     const uint32_t *lkey = region + kSpKey;
     uint32_t *R = region + kSpR;
     uint64_t *mbl = (uint64_t *)(region + kSpMb);
-    // (the bitmap is dead: the caller's barrier after the filter)
-    static_assert(kTile / 2 / 4 == kMT, "one 16-B store per lane fills step");
-    ((uint4 *)region)[tid] = make_uint4(0x00010001u, 0x00010001u, 0x00010001u, 0x00010001u);   // step = 1 (literal)
     // equal-key search: acc[r] = the wave's lanes whose key r equals a listed key
     uint32_t ky[kIns];
 #pragma unroll
@@ -804,8 +822,32 @@ __device__ __forceinline__ bool sparse_pairs(const uint32_t *sdw, uint32_t *regi
     }
     __syncthreads();
     const uint32_t nr = nflag + *s_np;
-    if (nr > kSfRCap) return false;   // not sparse (nothing but this workgroup's LDS was written)
-    if (dbg & 32u) return true;       // timing: + filter and equal-key search
+    if (nr > kSfRCap) return kSpNot;   // not sparse (nothing but this workgroup's LDS was written)
+    if (dbg & 32u) return kSpHere;     // timing: + filter and equal-key search
+    if (nr <= kTailR && !(kDev && (dbg & kSpStayBits))) {
+        // R entry `lane` and its candidates among the nr entries (every wave the same)
+        const uint32_t me = lane < nr ? R[lane] : 0u, x = me & 0x1FFFu;
+        const uint32_t i = w0 + x;
+        const bool q = lane < nr && !(x < q0 || x >= npos || i == 0 || blen - i < 4);
+        const uint32_t xlo = max(i, kWin) - kWin - w0;
+        uint32_t nc = 0;
+        for (uint32_t e = 0; e < nr; e++) {
+            const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)me, (int)e), xe = o & 0x1FFFu;
+            nc += (q && ((o ^ me) >> 13) == 0 && xe < x && xe >= xlo) ? 1u : 0u;
+        }
+        if (__ballot(nc > kExtBudget) == 0ull) {
+            if (__ballot(nc != 0) != 0ull) {   // (else no candidate pair: every position is a literal token)
+                if (tid < nr) mslot[tid] = me;
+                if (tid == 0) *tflag = (uint8_t)nr;
+            }
+            return kSpDone;
+        }
+    }
+    // (the bitmap is dead: the caller's barrier after the filter)
+    static_assert(kTile / 2 / 4 == kMT, "one 16-B store per lane fills step");
+    ((uint4 *)region)[tid] = make_uint4(0x00010001u, 0x00010001u, 0x00010001u, 0x00010001u);   // step = 1 (literal)
+    __syncthreads();   // (the queries below overwrite the steps of their matches; and every store of the
+                       //  real outputs comes after a barrier that follows the all-literal ones)
     if ((tid & ~63u) < nr) {   // R entry tid is this lane's query; each wave holds 64 entries at a time
         const uint32_t me = tid < nr ? R[tid] : 0u, x = me & 0x1FFFu;
         const uint32_t i = w0 + x;
@@ -840,7 +882,7 @@ __device__ __forceinline__ bool sparse_pairs(const uint32_t *sdw, uint32_t *regi
     }
     __syncthreads();
     if (tid < (ntile + 63) / 64) mbw[tid] = mbl[tid];
-    return true;
+    return kSpHere;
 }
 #endif
 
@@ -1209,6 +1251,22 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
     if (s_sample <= kSampleEvents && !(dbg & 128u)) {
 #endif
 #if FCX_SPARSE
+    // The tile's outputs as if it had no match -- chain words, prefix words, zero mbits words, tinfo:
+    // what 6 random tiles in 10 end with -- go out now, so their stores complete under the filter
+    // and the search; written at the tile's end, the workgroup kept its LDS and wave slots until they
+    // were acknowledged.  Whatever finishes the tile otherwise writes them again:
+    // k_sparse_tail or another unit's kernel, or this workgroup after a barrier (wave 0 stores these
+    // words, and a barrier orders a workgroup's later stores to them after these).
+    if (tid < (t1 - t0 + 63) / 64) {
+        const uint32_t nb = min(64u, t1 - t0 - 64 * tid);
+        chain[(uint64_t)b * L.wpb + (uint64_t)k * (kTile / 64) + tid] = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
+        chain_pfx[(uint64_t)bx * (kTile / 64) + tid] = 64ull * tid;   // tokens before; no matches
+        mbits[(uint64_t)b * L.wpb + (t0 >> 6) + tid] = 0ull;
+    }
+    if (tid == 0) {
+        uint32_t *ti = tinfo + 8ull * bx;
+        ti[0] = 0; ti[1] = t1; ti[2] = t1 - t0; ti[3] = 0; ti[4] = 0;
+    }
     // (the sparse unit: one bitmap, kSfK bits per key in one word (fcx_sparse_filter.h); a key is
     // flagged when all its bits were set.  Random data flags about 3 keys per window, so
     // sparse_pairs finds the equal keys directly.)
@@ -1304,10 +1362,14 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
 
 #if FCX_SPARSE
     // (R may overflow its capacity: the tile is then not sparse, with nothing of it written yet)
-    if (sparse)
-        sparse = sparse_pairs<kDev>(sdw, region, kw[0], kw[1], kw[2], kw[3], sp_fm, sp_wave, s_events, &s_np, &s_unknown,
-                                    &s_match, m + bstart + w0, mbits + (uint64_t)b * L.wpb + (t0 >> 6), q0, npos, ins_end,
-                                    w0, blen, t1 - t0, dbg);
+    if (sparse) {
+        const uint32_t sp = sparse_pairs<kDev>(
+            sdw, region, kw[0], kw[1], kw[2], kw[3], sp_fm, sp_wave, s_events, &s_np, &s_unknown, &s_match,
+            m + bstart + w0, mbits + (uint64_t)b * L.wpb + (t0 >> 6), q0, npos, ins_end, w0, blen, t1 - t0, dbg,
+            mtok + (uint64_t)bx * kTileMatches, sparse_tail_flags(mtok, L.nblocks * L.tpb) + bx);
+        if (sp == kSpDone) return;   // all literals, or left to k_sparse_tail
+        sparse = sp != kSpNot;
+    }
     if (sparse) {
         __syncthreads();
         if (dbg & 32u) return;
@@ -1879,7 +1941,7 @@ __device__ __forceinline__ void match_tile(const uint8_t *__restrict__ in, const
 // the grid is every tile of the shard; routed (fcx_route.hip) the grid is a host estimate of the
 // unit's list and workgroup i takes list entry i, if there is one (the entries past the grid go to
 // k_match_rest).  Either way each XCD takes a contiguous run of entries (xcd_tile).
-#if !FCX_REST
+#if !FCX_REST && !FCX_TAIL
 // kRouted = false: the route is a constant empty one (unrouted calls, and a direct launch over a call
 // whose tiles the estimate gives all to this unit): the list read, the kind check and the hand-on
 // branch fold away, and the kernel is the unrouted unit's code exactly.  Every unit is exact for any
@@ -1939,7 +2001,7 @@ void launch_match_rest(const MatchArgs &a, const RouteRest &rest, const MatchRou
 }
 #endif
 
-#if FCX_UNIT && !FCX_REST
+#if FCX_UNIT && !FCX_REST && !FCX_TAIL
 // the unit's routed instances, each defined in its own translation unit (FCX_LISTED, FCX_DIRECT)
 void launch_match_listed(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid);
 void launch_match_direct(const MatchArgs &a, hipStream_t st, const MatchRoute &rt, uint32_t grid);
@@ -1954,7 +2016,7 @@ void launch_match_direct(const MatchArgs &a, hipStream_t st, const MatchRoute &r
     hipLaunchKernelGGL((k_match<false, false, true>), dim3(grid), dim3(kMT), 0, st, a.in, a.L, a.m, a.mbits, a.chain,
                        a.chain_pfx, a.tinfo, a.mtok, 0u, rt);
 }
-#elif !FCX_REST
+#elif !FCX_REST && !FCX_TAIL
 void launch_match(const MatchArgs &a, hipStream_t st, uint32_t dbg_override, const MatchRoute *route,
                   uint32_t grid_override) {
     // dbg bits (k_match<true> only): fcx_debug_match's phase exits and experiment bits

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """k_match per-phase timing (development): the kernel alone through fcx_debug_match
 with phase exits (16: staging + run count, 4096: + repeat filter, 32: + sort (the sparse unit: +
-equal-key search), 64: + queries, 0: whole)."""
+equal-key search), 64: + queries, 0: whole).  The sparse unit (--mode 7) ends most tiles after the
+search and leaves the listed ones to k_sparse_tail: there 64 is the end of phase 1
+(k_match_sparse whole, the tail kernel not launched), 0 adds the tail kernel, so whole - +queries is
+the tail kernel alone, and "in-wg" (131072) keeps every tile's queries and parse in the workgroup
+(no tile listed: the kernel before the split)."""
 import argparse, ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -24,7 +28,7 @@ L = mc.lib()
 L.fcx_debug_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
 s = torch.cuda.current_stream()
 res = {}
-for name, bits in [("stage+count", 16), ("+filter", 4096), ("+sort", 32), ("+runtable", 8192 | 64), ("+eval-noloop", 16384 | 64), ("+eval-nofold", 32768 | 64), ("+queries", 64), ("+q-nocand", (1 << 22) | 64), ("+q-allA", (1 << 20) | 64), ("+q-allB", (1 << 21) | 64), ("+rmA1", 1 << 18), ("+rmA2", 1 << 19), ("+walks", 512), ("+jacobi", 256), ("+counts", 1024), ("+list", 2048), ("whole", 0), ("no-search", 1)]:
+for name, bits in [("stage+count", 16), ("+filter", 4096), ("+sort", 32), ("+runtable", 8192 | 64), ("+eval-noloop", 16384 | 64), ("+eval-nofold", 32768 | 64), ("+queries", 64), ("+q-nocand", (1 << 22) | 64), ("+q-allA", (1 << 20) | 64), ("+q-allB", (1 << 21) | 64), ("+rmA1", 1 << 18), ("+rmA2", 1 << 19), ("+walks", 512), ("+jacobi", 256), ("+counts", 1024), ("+list", 2048), ("whole", 0), ("in-wg", 131072), ("no-search", 1)]:
     if a.phases and name not in a.phases.split(","):
         continue
     ts = []
