@@ -940,6 +940,91 @@ int fcx_grep_regex_blocks_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len
  * positions judged, hits, ranges scanned, final passes */
 int fcx_dctx_regex_scan_stats(fcx_dctx *ctx, uint64_t *out, int n);
 
+/* ---- cut: fields and byte columns of the lines of the decoded run (FCX7 and FCX8) ---------------------------
+ * D, T, the delimiter d and the lines s_j / e_j are those of the line calls.  A repair sidecar is not applied.
+ * A cut is compiled once on the host from a mode (FCX_CUT_FIELDS or FCX_CUT_BYTES), a LIST, a separator byte sep
+ * (fields mode only; sep == d is FCX_ERR_ARG), d and flags (FCX_CUT_COMPLEMENT or 0).
+ * LIST is GNU cut's: items joined by `,`, each N, N-M, N- or -M with N >= 1 and N <= M, no blanks.  Closed numbers
+ * are at most FCX_CUT_MAX_COLUMN; an open item N- selects every column from N on, beyond the maximum too, and its
+ * N is at most FCX_CUT_MAX_COLUMN + 1.  sel(k) is "k is in LIST", negated under the complement flag; all columns
+ * above the maximum are selected or not together, so the device counts a line's ticks up to FCX_CUT_MAX_COLUMN + 1
+ * and no further.  mn is the smallest k with sel(k).  FCX_ERR_ARG, the message naming the offset in LIST: an empty
+ * list or item, a 0, a descending range, a number above its maximum, any other byte, a list whose effective
+ * selection is empty (the complement of `1-`).
+ * Column of a byte.  For a byte at p in line j with D[p] != d, ticks(p) is the number of i in [s_j, p) that tick.
+ * Bytes mode: every byte ticks, col(p) = ticks(p) + 1.  Fields mode: a byte ticks iff it equals sep; a byte that
+ * is not sep has col(p) = ticks(p) + 1, a separator byte opens column k = ticks(p) + 2.  A line without a
+ * separator is a line of one field.
+ * Keep rule.  The output is a subsequence of D: a delimiter byte is always kept; a byte that is neither d nor (in
+ * fields mode) sep is kept iff sel(col(p)); a separator byte is kept iff sel(k) and k > mn for the column k it
+ * opens.  So `a,b,c,d\n` with the list 2,4 gives `b,d\n`, and with 5 gives `\n`.  The result does not depend on
+ * record, tile, decode-group or buffer-piece boundaries; a line may be longer than any of them.
+ * Relation to GNU cut (LC_ALL=C).  -b: the same bytes for every input whose last line is terminated.  -f: the same
+ * bytes for every such input in which each line holds a separator or field 1 is selected.  Two differences, on
+ * purpose: (1) a line with no separator and field 1 not selected is printed whole by cut (dropped with -s); here
+ * it gives an empty line, as awk -F would: cut's rule needs a look-ahead over a line of unbounded length before
+ * the line's first byte can be judged.  (2) No byte is added behind an unterminated tail.  Not built: -s,
+ * --output-delimiter, reordering or repeating fields, multi-byte separators and characters. */
+#define FCX_CUT_FIELDS 1u
+#define FCX_CUT_BYTES 2u
+#define FCX_CUT_COMPLEMENT 1u     /* flags */
+#define FCX_CUT_MAX_COLUMN 4096u
+#define FCX_CUT_STATS 6   /* output bytes (whatever cap is), bytes judged (T after a whole run), delimiters seen,
+                           * separators seen (0 in bytes mode), separators kept, groups */
+typedef struct fcx_cut fcx_cut;
+/* Pure host code.  *cut is NULL on failure. */
+int  fcx_cut_create(fcx_cut **cut, const char *list, uint32_t len, uint32_t mode, uint8_t sep, uint8_t delim, uint32_t flags);
+void fcx_cut_destroy(fcx_cut *cut);
+/* any of the outputs may be NULL: the mode, sep, d, the flags, mn (FCX_CUT_MAX_COLUMN + 1: a column above the
+ * maximum), whether LIST has an open item */
+int  fcx_cut_info(const fcx_cut *cut, uint32_t *mode, uint8_t *sep, uint8_t *delim, uint32_t *flags, uint32_t *mn, uint32_t *open_end);
+/* Cap rule of the device calls below (the search's): *out_len is always the output's total, d_out[0, min(cap,
+ * total)) receives its first bytes and nothing behind is written, FCX_OK whether or not cap was reached; d_out ==
+ * NULL with cap == 0 is the size query (it skips the gather).  The output is a subsequence, so cap >= T always
+ * suffices.  stats: FCX_CUT_STATS values on the host, may be NULL.  All synchronise `stream`.
+ * fcx_cut_buffer cuts the n plain device bytes at d_in as one text.  d_in and d_out may have any alignment; only
+ * [d_in, d_in + n) is read.  n == 0 gives zeros and touches no device.  FCX_ERR_ARG before the device is touched:
+ * a NULL ctx, cut or out_len, a NULL d_in with n > 0, a NULL d_out with cap > 0. */
+int fcx_cut_buffer(fcx_dctx *ctx, const uint8_t *d_in, uint64_t n, const fcx_cut *cut, uint8_t *d_out, uint64_t cap,
+                   uint64_t *out_len, uint64_t *stats, void *stream);
+/* Cuts the whole run: it is indexed, then decoded in fcx_verify_shard's groups into the context's bounded buffer
+ * (fcx_dctx_set_verify_group applies; the result does not depend on it; a group of 4 GiB or more is FCX_ERR_ARG).
+ * What goes from group to group is words on the device: the saturated tick count of the open line, the output
+ * bytes so far and the counters; no byte and no state visits the host between groups.  Scratch beside the decoded
+ * group: a keep bitmap (group bytes / 8) and 16 bytes per 4096-byte tile, whatever the lines or the output.
+ * nblocks == 0 gives zeros and touches no device.  FCX_ERR_ARG before the device is touched: a NULL ctx, cut or
+ * out_len, a NULL d_rec with nblocks > 0, a NULL d_out with cap > 0, a kind other than '7' or '8'.  Stage table
+ * with profiling: index, decode, cut, summary. */
+int fcx_cut_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const fcx_cut *cut,
+                  uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *stats, void *stream);
+/* Cuts the concatenation of the ranges' bytes as one text, under fcx_decompress_ranges_shard's rules and errors
+ * (an index or NULL for both arrays): with a grep's blocks as ranges this is `zgrep ... | cut`.  It runs that call
+ * into a buffer of the context of `sum` bytes and then the buffer cut: scratch that grows with the selection,
+ * unlike fcx_cut_shard's (fcx_dctx_cut_scratch counts it).  nranges == 0 gives zeros and touches no device. */
+int fcx_cut_ranges_shard(fcx_dctx *ctx, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks,
+                         const uint64_t *d_rec_off, const uint64_t *d_dec_off, const uint64_t *d_start, const uint64_t *d_end,
+                         uint64_t nranges, const fcx_cut *cut, uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *stats,
+                         void *stream);
+/* fcx_decompress_stream's twin: reads the header, then the records in that function's groups of 256, and treats the
+ * file as one run: the tick count of the open line and the counters stay on the device across stream groups, each
+ * group's kept bytes go through write_out (NULL: the totals alone, no gather).  `user` goes to both callbacks.
+ * stats (FCX_CUT_STATS values, may be NULL) over the file.  FCX_ERR_ARG before anything is read: a NULL ctx,
+ * read_comp or cut. */
+int fcx_cut_stream(fcx_dctx *ctx, fcx_read_fn read_comp, fcx_write_fn write_out, void *user, uint64_t max_in, const fcx_cut *cut,
+                   uint64_t *stats);
+/* A whole file (header + records) in host memory.  fcx_cut_host cuts all of it through the stream form;
+ * fcx_cut_ranges_host takes host ranges: the records go to the device once and only the cut bytes come back.
+ * *out_len is always the output's total, cap < *out_len is FCX_ERR_CAPACITY (fcx_cut_host has stored the first cap
+ * bytes by then, fcx_cut_ranges_host nothing), out == NULL with cap == 0 the size query, as fcx_grep_host. */
+int fcx_cut_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const fcx_cut *cut, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                 uint64_t *stats);
+int fcx_cut_ranges_host(fcx_dctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *starts, const uint64_t *ends,
+                        uint64_t nranges, const fcx_cut *cut, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats);
+/* the last cut call's FCX_CUT_STATS values, min(n, FCX_CUT_STATS) of them; the device bytes it reserved beside the
+ * decoded group (bitmap, tile words, and the ranges form's buffer) */
+int fcx_dctx_cut_stats(fcx_dctx *ctx, uint64_t *out, int n);
+int fcx_dctx_cut_scratch(fcx_dctx *ctx, uint64_t *bytes);
+
 /* ---- multi-GPU: block ranges per GPU + RCCL over xGMI -------------------------
  * Blocks are independent (the window and the parse restart per block, :1675-1703), so
  * rank r of N compresses the contiguous block range fcx_dist_block_range(nb, r, N) of the

@@ -18,7 +18,7 @@ import struct
 
 __all__ = [
     "FcxError", "lib", "lib_path", "Context", "my_compress_file_lz77", "my_decompress_file_lz77",
-    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "grep_context", "grep_context_blocks", "Regex", "grep_regex", "grep_regex_blocks", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
+    "compress", "decompress", "verify", "repair", "decompress_repaired", "parse_repair", "RepairEntry", "digest", "parse_digest", "check", "find", "count_lines", "decompress_lines", "line_numbers", "find_lines", "grep", "grep_ranges", "PatternSet", "find_any", "grep_any", "grep_any_ranges", "grep_context", "grep_context_blocks", "Regex", "grep_regex", "grep_regex_blocks", "Cut", "cut", "cut_size", "shard_bound", "write_header", "BLOCK_BYTES", "HEADER_BYTES",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -255,6 +255,26 @@ def lib():
         L.fcx_grep_regex_blocks_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, c_u8p,
                                                  ctypes.c_uint64, P64, P64]
         L.fcx_dctx_regex_scan_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+    if hasattr(L, "fcx_cut_shard"):   # (absent from an older FCX_LIB build used for A/B timing)
+        run = [ctypes.c_void_p, ctypes.c_char, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]
+        P32 = ctypes.POINTER(ctypes.c_uint32)
+        P8 = ctypes.POINTER(ctypes.c_uint8)
+        out = [ctypes.c_void_p, ctypes.c_uint64, P64, P64]
+        L.fcx_cut_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
+                                     ctypes.c_uint8, ctypes.c_uint32]
+        L.fcx_cut_destroy.argtypes = [ctypes.c_void_p]
+        L.fcx_cut_destroy.restype = None
+        L.fcx_cut_info.argtypes = [ctypes.c_void_p, P32, P8, P8, P32, P32, P32]
+        L.fcx_cut_buffer.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p] + out + [ctypes.c_void_p]
+        L.fcx_cut_shard.argtypes = run + [ctypes.c_void_p] + out + [ctypes.c_void_p]
+        L.fcx_cut_ranges_shard.argtypes = run + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_void_p] + out + [ctypes.c_void_p]
+        L.fcx_cut_stream.argtypes = [ctypes.c_void_p, READ_FN, WRITE_FN, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, P64]
+        L.fcx_cut_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_void_p, c_u8p, ctypes.c_uint64, P64, P64]
+        L.fcx_cut_ranges_host.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, P64, P64, ctypes.c_uint64, ctypes.c_void_p, c_u8p,
+                                          ctypes.c_uint64, P64, P64]
+        L.fcx_dctx_cut_stats.argtypes = [ctypes.c_void_p, P64, ctypes.c_int]
+        L.fcx_dctx_cut_scratch.argtypes = [ctypes.c_void_p, P64]
     L.fcx_dist_block_range.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P64, P64]
     L.fcx_dist_block_range.restype = None
     L.fcx_dist_block_range_w.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P64, P64]
@@ -1147,6 +1167,90 @@ class DContext:
         _check(lib().fcx_dctx_regex_scan_stats(self._h, vals, n), "fcx_dctx_regex_scan_stats")
         return dict(zip(self.REGEX_SCAN_STATS, [int(v) for v in vals]))
 
+    # ---- cut (fcx_cut_*): fields and byte columns of the lines of the decoded run; the rule and its two differences
+    # from GNU cut: include/fcx.h.  Every device call returns (total, stats): d_out receives the first min(cap, total)
+    # bytes, d_out 0 with cap 0 is the size query ----
+    CUT_STATS = ("out_bytes", "judged", "delimiters", "separators", "separators_kept", "groups")
+
+    def _cut_out(self, rc, what, total, vals):
+        _check(rc, what)
+        return int(total.value), dict(zip(self.CUT_STATS, [int(v) for v in vals]))
+
+    def cut_buffer(self, d_in: int, n: int, cut: "Cut", d_out: int = 0, cap: int = 0, stream: int = 0):
+        """cuts the n plain device bytes at d_in as one text; any alignment of d_in and d_out"""
+        vals, total = (ctypes.c_uint64 * len(self.CUT_STATS))(), ctypes.c_uint64(0)
+        rc = lib().fcx_cut_buffer(self._h, ctypes.c_void_p(d_in or None), n, cut.handle, ctypes.c_void_p(d_out or None), cap,
+                                  ctypes.byref(total), vals, ctypes.c_void_p(stream))
+        return self._cut_out(rc, "fcx_cut_buffer", total, vals)
+
+    def cut_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, cut: "Cut", d_out: int = 0, cap: int = 0, stream: int = 0):
+        """cuts what the nblocks records at d_rec decode to, group by group on the device"""
+        vals, total = (ctypes.c_uint64 * len(self.CUT_STATS))(), ctypes.c_uint64(0)
+        rc = lib().fcx_cut_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, cut.handle,
+                                 ctypes.c_void_p(d_out or None), cap, ctypes.byref(total), vals, ctypes.c_void_p(stream))
+        return self._cut_out(rc, "fcx_cut_shard", total, vals)
+
+    def cut_ranges_shard(self, kind: str, d_rec: int, rec_len: int, nblocks: int, d_start: int, d_end: int, nranges: int, cut: "Cut",
+                         d_out: int = 0, cap: int = 0, index=None, stream: int = 0):
+        """cuts the concatenation of the ranges [d_start[i], d_end[i]) (u64 on the device; a grep's lines or blocks) as
+        one text; index: the device arrays (rec_off, dec_off) of index_shard, or None"""
+        vals, total = (ctypes.c_uint64 * len(self.CUT_STATS))(), ctypes.c_uint64(0)
+        ro, do = index if index is not None else (0, 0)
+        rc = lib().fcx_cut_ranges_shard(self._h, kind.encode(), ctypes.c_void_p(d_rec or None), rec_len, nblocks, ctypes.c_void_p(ro or None),
+                                        ctypes.c_void_p(do or None), ctypes.c_void_p(d_start or None), ctypes.c_void_p(d_end or None),
+                                        nranges, cut.handle, ctypes.c_void_p(d_out or None), cap, ctypes.byref(total), vals,
+                                        ctypes.c_void_p(stream))
+        return self._cut_out(rc, "fcx_cut_ranges_shard", total, vals)
+
+    def cut_stream(self, src, sink, cut: "Cut", max_in: int = 0) -> dict:
+        """an FCX7 or FCX8 file from src (binary reader), its cut to sink (binary writer; None: the totals alone)"""
+        rd, wr = _stream_fns(src, sink)
+        vals = (ctypes.c_uint64 * len(self.CUT_STATS))()
+        _check(lib().fcx_cut_stream(self._h, rd, wr if sink is not None else ctypes.cast(None, WRITE_FN), None, max_in, cut.handle, vals),
+               "fcx_cut_stream")
+        return dict(zip(self.CUT_STATS, [int(v) for v in vals]))
+
+    def _cut_host(self, fn, what, args, size_only, room=None):
+        """room: bytes that hold the output whatever it is (one call); None: the size query first, then the call"""
+        vals, need = (ctypes.c_uint64 * len(self.CUT_STATS))(), ctypes.c_uint64(0)
+        if room is None or size_only:
+            rc = fn(*args, None, 0, ctypes.byref(need), vals)   # the size
+            if rc != -2 or size_only:
+                if rc != -2:
+                    _check(rc, what)
+                return int(need.value), dict(zip(self.CUT_STATS, [int(v) for v in vals])), b""
+            room = need.value
+        out = ctypes.create_string_buffer(max(room, 1))
+        _check(fn(*args, out, room, ctypes.byref(need), vals), what)
+        return int(need.value), dict(zip(self.CUT_STATS, [int(v) for v in vals])), out.raw[:need.value]
+
+    def cut_host(self, blob: bytes, cut: "Cut", size_only: bool = False):
+        """a whole FCX7 or FCX8 file in memory -> (total, stats, the cut's bytes; b"" with size_only).  Without size_only
+        the file is decoded and cut twice: the size query (no gather), then the call into a buffer of that size"""
+        return self._cut_host(lib().fcx_cut_host, "fcx_cut_host", (self._h, blob, len(blob), cut.handle), size_only)
+
+    def cut_ranges_host(self, blob: bytes, ranges, cut: "Cut", size_only: bool = False):
+        """cut_host over the ascending, disjoint (start, end) pairs of what the file decodes to"""
+        n = len(ranges)
+        starts = (ctypes.c_uint64 * max(n, 1))(*[r[0] for r in ranges])
+        ends = (ctypes.c_uint64 * max(n, 1))(*[r[1] for r in ranges])
+        room = sum(max(e - s, 0) for s, e in ranges)   # (the cut is a subsequence of the ranges' bytes: one call)
+        return self._cut_host(lib().fcx_cut_ranges_host, "fcx_cut_ranges_host", (self._h, blob, len(blob), starts, ends, n, cut.handle),
+                              size_only, room)
+
+    def cut_stats(self) -> dict:
+        """counters of the last cut call (fcx_dctx_cut_stats)"""
+        n = len(self.CUT_STATS)
+        vals = (ctypes.c_uint64 * n)()
+        _check(lib().fcx_dctx_cut_stats(self._h, vals, n), "fcx_dctx_cut_stats")
+        return dict(zip(self.CUT_STATS, [int(v) for v in vals]))
+
+    def cut_scratch(self) -> int:
+        """device bytes the last cut call reserved beside the decoded group"""
+        v = ctypes.c_uint64(0)
+        _check(lib().fcx_dctx_cut_scratch(self._h, ctypes.byref(v)), "fcx_dctx_cut_scratch")
+        return int(v.value)
+
     def set_scan_stats(self) -> dict:
         """counters of the last pattern-set call (fcx_dctx_set_scan_stats)"""
         n = len(self.SET_SCAN_STATS)
@@ -1530,6 +1634,79 @@ def grep_regex_blocks(blob: bytes, expr: bytes, delim=b"\n", ignore_case: bool =
                                                                        max(0, len(blob) - HEADER_BYTES)))
     finally:
         rx.close()
+
+
+class Cut:
+    """GNU cut's LIST compiled for the cut calls (fcx_cut_create): fields=LIST with a one-byte separator, or
+    byte_list=LIST; complement negates the selection.  The rule, the LIST syntax and the two differences from GNU cut
+    (a line without a separator and with field 1 unselected gives an empty line; nothing is added behind an
+    unterminated tail): include/fcx.h"""
+    FIELDS = 1
+    BYTES = 2
+    COMPLEMENT = 1
+    MAX_COLUMN = 4096
+
+    def __init__(self, fields=None, byte_list=None, sep=b"\t", delim=b"\n", complement: bool = False):
+        if (fields is None) == (byte_list is None):
+            raise ValueError("give one of fields and byte_list")
+        one = lambda b, what: b if isinstance(b, int) and 0 <= b <= 255 else (b[0] if len(b) == 1 else _one_byte(what))
+        lst = fields if fields is not None else byte_list
+        lst = lst.encode() if isinstance(lst, str) else bytes(lst)
+        h = ctypes.c_void_p()
+        self._h = None
+        _check(lib().fcx_cut_create(ctypes.byref(h), lst, len(lst), self.FIELDS if fields is not None else self.BYTES,
+                                    one(sep, "the separator"), one(delim, "the delimiter"), self.COMPLEMENT if complement else 0),
+               "fcx_cut_create")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        v = [ctypes.c_uint32(0) for _ in range(4)]
+        b = [ctypes.c_uint8(0) for _ in range(2)]
+        _check(lib().fcx_cut_info(self._h, ctypes.byref(v[0]), ctypes.byref(b[0]), ctypes.byref(b[1]), ctypes.byref(v[1]),
+                                  ctypes.byref(v[2]), ctypes.byref(v[3])), "fcx_cut_info")
+        return {"mode": int(v[0].value), "sep": int(b[0].value), "delim": int(b[1].value), "flags": int(v[1].value),
+                "mn": int(v[2].value), "open_end": bool(v[3].value)}
+
+    def close(self):
+        if self._h:
+            lib().fcx_cut_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _one_byte(what):
+    raise ValueError(what + " is one byte")
+
+
+def _cut(blob, fields, byte_list, sep, delim, complement, ranges, device, size_only):
+    ct = Cut(fields, byte_list, sep, delim, complement)
+    try:
+        if ranges is None:
+            return _with_dctx(device, lambda c: c.cut_host(blob, ct, size_only))
+        return _with_dctx(device, lambda c: c.cut_ranges_host(blob, ranges, ct, size_only))
+    finally:
+        ct.close()
+
+
+def cut(blob: bytes, fields=None, byte_list=None, sep=b"\t", delim=b"\n", complement: bool = False, ranges=None, device: int = 0) -> bytes:
+    """cut -f fields -d sep, or cut -b byte_list, (--complement) over what the FCX7 or FCX8 file `blob` decodes to, or over
+    the ascending, disjoint (start, end) ranges of it (a grep's lines or blocks): decoded and cut on the GPU, only the
+    cut bytes come back.  Without ranges the file is decoded twice (the size first: DContext.cut_host)"""
+    return _cut(blob, fields, byte_list, sep, delim, complement, ranges, device, False)[2]
+
+
+def cut_size(blob: bytes, fields=None, byte_list=None, sep=b"\t", delim=b"\n", complement: bool = False, ranges=None, device: int = 0) -> int:
+    """the number of bytes cut() would return; nothing is gathered"""
+    return _cut(blob, fields, byte_list, sep, delim, complement, ranges, device, True)[0]
 
 
 def _with_dctx(device, fn):

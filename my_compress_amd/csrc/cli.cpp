@@ -104,6 +104,20 @@
 //                     them, and with its output and totals lines ("patterns: 1")
 // Usage errors: an expression the compiler refuses (the reason and the offset are printed first); --grep-regex twice or
 // with --find, --grep, their -hex and -set forms, --set-hex or --line-numbers.
+//
+// Cut, decompress mode only (fcx_cut_stream): the fields or byte columns of every line of the decoded bytes, to -o
+//   --cut-fields LIST GNU cut's -f LIST: items N, N-M, N- or -M joined by commas; --sep HH the field separator (two hex
+//                     digits, default 09)
+//   --cut-bytes LIST  GNU cut's -b LIST
+//   --complement      what LIST does not select; --delim HH the line delimiter; --count prints the totals and writes nothing
+// The last line printed is "cut: N bytes, D delimiters, S separators (K kept), decoded bytes = T".  Two differences from
+// GNU cut (include/fcx.h): a line without a separator and with field 1 unselected gives an empty line, and nothing is
+// added behind an unterminated last line.  Usage errors: both cut options; a LIST the compiler refuses (the reason and
+// the offset are printed first); a separator equal to the delimiter; --sep or --complement without a cut option; a cut
+// option with -c, --range, --list, --find*, --count-lines, --compare, --verify, --repair, --digest or --test.
+// Together with exactly one grep option (with its modifiers) or with --lines A:N the blocks, lines or line range come as
+// they do without the cut (fcx_*_stream), and their cut comes through fcx_cut_ranges_host in a second pass; no `--` line is
+// written between blocks, since it is not a byte of the file; the grep's own totals line comes first.
 #include <getopt.h>
 
 #include <algorithm>
@@ -136,7 +150,9 @@ static int usage() {
             "[--ignore-case (with a search: ASCII letters match in either case)] "
             "[--invert] [--before <lines>] [--after <lines>] [--context <lines>] (with a grep: the lines without a pattern, "
             "lines of context, at most 4096) "
-            "[--grep-regex <POSIX ERE> [--count] (decompress only: the lines in which a match ends, to -o)]\n");
+            "[--grep-regex <POSIX ERE> [--count] (decompress only: the lines in which a match ends, to -o)] "
+            "[--cut-fields <LIST> [--sep <two hex digits, default 09>] | --cut-bytes <LIST> [--complement] [--count] "
+            "(decompress only: the fields or byte columns of every line, or of the lines a grep option or --lines selects, to -o)]\n");
     return -1;
 }
 
@@ -543,6 +559,71 @@ static int do_check(FILE *fcomp, FILE *frep, const char *digest_path, int device
     return r;
 }
 
+// ---- a cut behind a grep or --lines: the blocks, lines or line range come as they do without it, their
+// cut comes through fcx_cut_ranges_host; without a device the host path's bytes go through the rule of fcx_cut.h ----
+static int cli_fail(const char *msg) {
+    fprintf(stderr, "fcx: %s\n", msg);
+    return -1;
+}
+struct CutJob {
+    const fcx_cut *host;   // the command line's own compilation of LIST
+    std::string list;
+};
+
+// pass 2 under a cut option: the n ranges of the file at fin, cut, to fout (null: --count); *sum: the ranges' bytes
+static int cut_ranges_out(const CutJob *job, fcx_dctx *d, FILE *fin, FILE *fout, const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *sum) {
+    *sum = 0;
+    for (uint64_t i = 0; i < n; i++) *sum += ends[i] - starts[i];
+    std::vector<uint8_t> file;
+    if (fseek(fin, 0, SEEK_END) != 0 || ftell(fin) < 0) return cli_fail("cannot size the input file");
+    file.resize((size_t)ftell(fin));
+    rewind(fin);
+    if (fread(file.data(), 1, file.size(), fin) != file.size()) return cli_fail("cannot read the input file");
+    const fcx_cut &h = *job->host;
+    fcx_cut *cut = nullptr;
+    int r = fcx_cut_create(&cut, job->list.data(), (uint32_t)job->list.size(), h.mode, h.sep, h.delim, h.flags);
+    uint64_t need = 0, stats[FCX_CUT_STATS] = {};
+    std::vector<uint8_t> out;
+    if (r == FCX_OK) {   // one call: the cut is a subsequence of the ranges' bytes, so room for those always suffices
+        if (fout) out.resize((size_t)*sum);
+        r = fcx_cut_ranges_host(d, file.data(), file.size(), starts, ends, n, cut, fout && *sum ? out.data() : nullptr, fout ? *sum : 0, &need,
+                                stats);
+        if (r == FCX_ERR_CAPACITY && !fout) r = FCX_OK;   // (--count: the size query)
+    }
+    fcx_cut_destroy(cut);
+    if (r) return r;
+    if (fout && need && fwrite(out.data(), 1, (size_t)need, fout) != need) return cli_fail("write error");
+    fcx_cli::cut_totals(stats);
+    return FCX_OK;
+}
+
+// a no-device path under a cut option: what fn writes goes to memory, and from there through the rule to fout (null: --count)
+template <typename Fn>
+static int host_with_cut(const CutJob *job, FILE *fout, Fn fn) {
+    if (!job) return fn(fout);
+    char *buf = nullptr;
+    size_t len = 0;
+    FILE *mem = open_memstream(&buf, &len);
+    if (!mem) return -1;
+    int r = fn(mem);
+    if (fclose(mem) != 0) r = -1;
+    if (r == 0) {
+        uint64_t stats[FCX_CUT_STATS] = {};
+        uint32_t ticks = 0;
+        std::string kept;
+        fcx::cut_host_bytes(*job->host, (const uint8_t *)buf, len, &ticks, fout ? &kept : nullptr, stats);
+        stats[5] = len ? 1 : 0;
+        if (fout && !kept.empty() && fwrite(kept.data(), 1, kept.size(), fout) != kept.size()) {
+            fprintf(stderr, "write error\n");
+            r = -1;
+        } else {
+            fcx_cli::cut_totals(stats);
+        }
+    }
+    free(buf);
+    return r;
+}
+
 // --find / --find-hex: the pattern's offsets in the decoded file, by fcx_find_stream on the device, or for
 // an FCX7 file without one by the host decoder
 static int do_find(FILE *fin, int device, const std::vector<uint8_t> &pat, bool count_only) {
@@ -627,7 +708,7 @@ static int do_find_numbered(FILE *fin, int device, const std::vector<uint8_t> &p
 
 // --count-lines (fout null) and --lines: fcx_lines_stream, or fcx_lines_locate_stream and then the range decode
 // of what it found in a second pass; for an FCX7 file without a device the host decoder
-static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t first, uint64_t count) {
+static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t first, uint64_t count, const CutJob *job) {
     uint8_t hdr[FCX_HEADER_BYTES];
     uint32_t total = 0;
     uint16_t nblocks = 0;
@@ -647,17 +728,20 @@ static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t f
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
-        return fcx_cli::host_lines(fin, nblocks, delim, fout, first, count, nullptr);
+        return host_with_cut(job, fout, [&](FILE *f) { return fcx_cli::host_lines(fin, nblocks, delim, f, first, count, nullptr); });
     }
     uint64_t max_in = 0, stats[FCX_LINES_STATS] = {}, off = 0, len = 0, got = 0;
     if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
     rewind(fin);
     int r;
-    if (!fout) {
+    if (!fout && !job) {
         r = fcx_lines_stream(d, file_read, fin, max_in, delim, stats);
     } else {
         r = fcx_lines_locate_stream(d, file_read, fin, max_in, delim, first, count, &off, &len);
-        if (r == FCX_OK && len) {
+        if (r == FCX_OK && job) {
+            const uint64_t end = off + len;
+            r = cut_ranges_out(job, d, fin, fout, &off, &end, len ? 1 : 0, &got);
+        } else if (r == FCX_OK && len) {
             rewind(fin);
             Files io{fin, fout};
             r = fcx_decompress_range_stream(d, files_read, files_write, &io, max_in, off, len, &got);
@@ -668,13 +752,13 @@ static int do_lines(FILE *fin, FILE *fout, int device, uint8_t delim, uint64_t f
         fprintf(stderr, "fcx: %s\n", fcx_last_error());
         return -1;
     }
-    return fout ? fcx_cli::lines_done(got, off) : fcx_cli::lines_totals(stats[1], stats[0], stats[2]);
+    return fout || job ? fcx_cli::lines_done(got, off) : fcx_cli::lines_totals(stats[1], stats[0], stats[2]);
 }
 
 // --grep / --grep-hex: pass 1 collects the matching lines' byte ranges (fcx_grep_stream), pass 2 decodes them to
 // fout (fcx_decompress_ranges_stream; fout null: --count, the totals alone); for an FCX7 file without a device the
 // host decoder in one pass
-static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t> &pat, uint8_t delim) {
+static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t> &pat, uint8_t delim, const CutJob *job) {
     uint8_t hdr[FCX_HEADER_BYTES];
     uint32_t total = 0;
     uint16_t nblocks = 0;
@@ -694,7 +778,7 @@ static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t>
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
-        return fcx_cli::host_grep(fin, nblocks, delim, pat.data(), (uint32_t)pat.size(), fout, nullptr);
+        return host_with_cut(job, fout, [&](FILE *f) { return fcx_cli::host_grep(fin, nblocks, delim, pat.data(), (uint32_t)pat.size(), f, nullptr); });
     }
     uint64_t max_in = 0, stats[FCX_GREP_STATS] = {}, got = 0;
     if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
@@ -706,12 +790,13 @@ static int do_grep(FILE *fin, FILE *fout, int device, const std::vector<uint8_t>
         ((Lines *)u)->starts.push_back(s);
         ((Lines *)u)->ends.push_back(e);
     };
-    int r = fcx_grep_stream(d, file_read, fin, max_in, delim, pat.data(), (uint32_t)pat.size(), fout ? keep : nullptr, &lines, stats);
-    if (r == FCX_OK && fout && !lines.starts.empty()) {
+    int r = fcx_grep_stream(d, file_read, fin, max_in, delim, pat.data(), (uint32_t)pat.size(), (fout || job) ? keep : nullptr, &lines, stats);
+    if (r == FCX_OK && (job || (fout && !lines.starts.empty()))) {
         rewind(fin);
         Files io{fin, fout};
-        r = fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
-                                         lines.starts.size(), &got);
+        r = job ? cut_ranges_out(job, d, fin, fout, lines.starts.data(), lines.ends.data(), lines.starts.size(), &got)
+                  : fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
+                                                 lines.starts.size(), &got);
         if (r == FCX_OK && got != stats[1]) {
             fprintf(stderr, "fcx: the lines' bytes disagree with the grep's sum\n");
             fcx_dctx_destroy(d);
@@ -767,7 +852,8 @@ static int do_find_set(FILE *fin, int device, const fcx_pattern_set *set, const 
 }
 
 // --grep-set, or --grep with --ignore-case: do_grep for a pattern set
-static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, uint8_t delim) {
+static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, uint8_t delim,
+                       const CutJob *job) {
     uint8_t hdr[FCX_HEADER_BYTES];
     uint32_t total = 0;
     uint16_t nblocks = 0;
@@ -787,7 +873,7 @@ static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set 
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
-        return fcx_cli::host_grep_set(fin, nblocks, delim, host_set, fout, nullptr, nullptr);
+        return host_with_cut(job, fout, [&](FILE *f) { return fcx_cli::host_grep_set(fin, nblocks, delim, host_set, f, nullptr, nullptr); });
     }
     uint64_t max_in = 0, stats[FCX_GREP_STATS] = {}, got = 0;
     if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
@@ -801,12 +887,13 @@ static int do_grep_set(FILE *fin, FILE *fout, int device, const fcx_pattern_set 
     };
     uint32_t npat = 0;
     int r = fcx_pattern_set_info(set, &npat, nullptr, nullptr, nullptr);
-    if (r == FCX_OK) r = fcx_grep_set_stream(d, file_read, fin, max_in, delim, set, fout ? keep : nullptr, &lines, stats, nullptr);
-    if (r == FCX_OK && fout && !lines.starts.empty()) {
+    if (r == FCX_OK) r = fcx_grep_set_stream(d, file_read, fin, max_in, delim, set, (fout || job) ? keep : nullptr, &lines, stats, nullptr);
+    if (r == FCX_OK && (job || (fout && !lines.starts.empty()))) {
         rewind(fin);
         Files io{fin, fout};
-        r = fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
-                                         lines.starts.size(), &got);
+        r = job ? cut_ranges_out(job, d, fin, fout, lines.starts.data(), lines.ends.data(), lines.starts.size(), &got)
+                  : fcx_decompress_ranges_stream(d, files_read, files_write, &io, max_in, lines.starts.data(), lines.ends.data(),
+                                                 lines.starts.size(), &got);
         if (r == FCX_OK && got != stats[1]) {
             fprintf(stderr, "fcx: the lines' bytes disagree with the grep's sum\n");
             fcx_dctx_destroy(d);
@@ -850,7 +937,7 @@ static int blocks_write(void *u, const uint8_t *buf, uint64_t n) {
 }
 
 static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_set *set, const fcx_pattern_set &host_set, uint8_t delim,
-                          const fcx_grep_opts &opts) {
+                          const fcx_grep_opts &opts, const CutJob *job) {
     uint8_t hdr[FCX_HEADER_BYTES];
     uint32_t total = 0;
     uint16_t nblocks = 0;
@@ -870,7 +957,7 @@ static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_s
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
-        return fcx_cli::host_grep_blocks(fin, nblocks, delim, host_set, opts, fout, nullptr, nullptr);
+        return host_with_cut(job, fout, [&](FILE *f) { return fcx_cli::host_grep_blocks(fin, nblocks, delim, host_set, opts, f, nullptr, nullptr, !job); });
     }
     uint64_t max_in = 0, stats[FCX_GREP_BLOCK_STATS] = {}, got = 0;
     if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
@@ -880,11 +967,12 @@ static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_s
         ((BlockOut *)u)->starts.push_back(s);
         ((BlockOut *)u)->ends.push_back(e);
     };
-    int r = fcx_grep_blocks_stream(d, file_read, fin, max_in, delim, set, &opts, fout ? keep : nullptr, &io, stats, nullptr);
-    if (r == FCX_OK && fout && !io.starts.empty()) {
+    int r = fcx_grep_blocks_stream(d, file_read, fin, max_in, delim, set, &opts, (fout || job) ? keep : nullptr, &io, stats, nullptr);
+    if (r == FCX_OK && (job || (fout && !io.starts.empty()))) {
         rewind(fin);
-        r = fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(), io.starts.size(),
-                                         &got);
+        r = job ? cut_ranges_out(job, d, fin, fout, io.starts.data(), io.ends.data(), io.starts.size(), &got)
+                  : fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(),
+                                                 io.starts.size(), &got);
         if (r == FCX_OK && got != stats[2]) {
             fprintf(stderr, "fcx: the blocks' bytes disagree with the grep's sum\n");
             fcx_dctx_destroy(d);
@@ -901,7 +989,7 @@ static int do_grep_blocks(FILE *fin, FILE *fout, int device, const fcx_pattern_s
 
 // --grep-regex: do_grep_blocks for a regex; without --invert, --before, --after or --context the totals are the set grep's
 static int do_grep_regex(FILE *fin, FILE *fout, int device, const fcx_regex *re, const fcx_regex &host_re, const fcx_grep_opts &opts,
-                         bool blocks_form) {
+                         bool blocks_form, const CutJob *job) {
     uint8_t hdr[FCX_HEADER_BYTES];
     uint32_t total = 0;
     uint16_t nblocks = 0;
@@ -921,7 +1009,7 @@ static int do_grep_regex(FILE *fin, FILE *fout, int device, const fcx_regex *re,
             return -1;
         }
         fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
-        return fcx_cli::host_grep_regex(fin, nblocks, host_re, opts, blocks_form, fout, nullptr);
+        return host_with_cut(job, fout, [&](FILE *f) { return fcx_cli::host_grep_regex(fin, nblocks, host_re, opts, blocks_form, f, nullptr, !job); });
     }
     uint64_t max_in = 0, stats[FCX_GREP_BLOCK_STATS] = {}, got = 0;
     if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
@@ -931,11 +1019,12 @@ static int do_grep_regex(FILE *fin, FILE *fout, int device, const fcx_regex *re,
         ((BlockOut *)u)->starts.push_back(s);
         ((BlockOut *)u)->ends.push_back(e);
     };
-    int r = fcx_grep_regex_blocks_stream(d, file_read, fin, max_in, re, &opts, fout ? keep : nullptr, &io, stats);
-    if (r == FCX_OK && fout && !io.starts.empty()) {
+    int r = fcx_grep_regex_blocks_stream(d, file_read, fin, max_in, re, &opts, (fout || job) ? keep : nullptr, &io, stats);
+    if (r == FCX_OK && (job || (fout && !io.starts.empty()))) {
         rewind(fin);
-        r = fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(), io.starts.size(),
-                                         &got);
+        r = job ? cut_ranges_out(job, d, fin, fout, io.starts.data(), io.ends.data(), io.starts.size(), &got)
+                  : fcx_decompress_ranges_stream(d, blocks_read, blocks_write, &io, max_in, io.starts.data(), io.ends.data(),
+                                                 io.starts.size(), &got);
         if (r == FCX_OK && got != stats[2]) {
             fprintf(stderr, "fcx: the blocks' bytes disagree with the grep's sum\n");
             fcx_dctx_destroy(d);
@@ -949,6 +1038,46 @@ static int do_grep_regex(FILE *fin, FILE *fout, int device, const fcx_regex *re,
     }
     return blocks_form ? fcx_cli::grep_blocks_totals(stats[0], stats[1], stats[3], stats[2], stats[4], stats[6])
                        : fcx_cli::grep_set_totals(stats[1], stats[2], stats[4], stats[6], 1);
+}
+
+// --cut-fields / --cut-bytes: the whole file through fcx_cut_stream to fout (null: --count, the totals alone); for an
+// FCX7 file without a device the host decoder.  host_cut: the command line's own compilation of LIST
+static int do_cut(FILE *fin, FILE *fout, int device, const fcx_cut &host_cut, const std::string &list) {
+    uint8_t hdr[FCX_HEADER_BYTES];
+    uint32_t total = 0;
+    uint16_t nblocks = 0;
+    char kind = 0;
+    if (fread(hdr, 1, sizeof(hdr), fin) != sizeof(hdr)) {
+        fprintf(stderr, "Read file head infomation error!!!\n");
+        return -1;
+    }
+    if (fcx_parse_header(hdr, &total, &nblocks, &kind)) {
+        fprintf(stderr, "This file is not support to decompress!!!!\n");
+        return -1;
+    }
+    fcx_dctx *d = nullptr;
+    if (fcx_dctx_create(&d, device) != FCX_OK) {
+        if (kind != '7') {   // the FCX8 decoder is GPU-only
+            fprintf(stderr, "fcx: %s\n", fcx_last_error());
+            return -1;
+        }
+        fprintf(stderr, "fcx: %s; decoding on the host\n", fcx_last_error());
+        return fcx_cli::host_cut(fin, nblocks, host_cut, fout, nullptr);
+    }
+    uint64_t max_in = 0, stats[FCX_CUT_STATS] = {};
+    if (fseek(fin, 0, SEEK_END) == 0 && ftell(fin) > (long)FCX_HEADER_BYTES) max_in = (uint64_t)ftell(fin) - FCX_HEADER_BYTES;
+    rewind(fin);
+    fcx_cut *cut = nullptr;
+    int r = fcx_cut_create(&cut, list.data(), (uint32_t)list.size(), host_cut.mode, host_cut.sep, host_cut.delim, host_cut.flags);
+    Files io{fin, fout};
+    if (r == FCX_OK) r = fcx_cut_stream(d, files_read, fout ? files_write : nullptr, &io, max_in, cut, stats);
+    fcx_cut_destroy(cut);
+    fcx_dctx_destroy(d);
+    if (r) {
+        fprintf(stderr, "fcx: %s\n", fcx_last_error());
+        return -1;
+    }
+    return fcx_cli::cut_totals(stats);
 }
 
 static int do_decompress(FILE *fin, FILE *fout, int device, const Want &want, FILE *frep) {
@@ -1049,6 +1178,10 @@ int main(int argc, char **argv) {
                                            {"after", required_argument, nullptr, 1007},
                                            {"context", required_argument, nullptr, 1008},
                                            {"grep-regex", required_argument, nullptr, 1009},
+                                           {"cut-fields", required_argument, nullptr, 1010},
+                                           {"cut-bytes", required_argument, nullptr, 1011},
+                                           {"sep", required_argument, nullptr, 1012},
+                                           {"complement", no_argument, nullptr, 1013},
                                            {nullptr, 0, nullptr, 0}};
     std::string file_in, file_out = "./out";
     bool compress = false, lz77 = false;
@@ -1070,6 +1203,11 @@ int main(int argc, char **argv) {
     bool set_hex = false, ignore_case = false;
     fcx_grep_opts gopts = {0, 0, 0};
     bool blocks = false;   // --invert, --before, --after or --context seen
+    std::string cut_list;
+    int cuts = 0;          // --cut-fields and --cut-bytes options seen
+    uint32_t cut_mode = 0;
+    uint8_t sep = 0x09;
+    bool sep_given = false, complement = false;
     Want want;
     if (argc < 3) return usage();
     while ((opt = getopt_long(argc, argv, "i:o:c:b:d:g:", long_options, nullptr)) != -1) {
@@ -1145,10 +1283,36 @@ int main(int argc, char **argv) {
             grep_regex = optarg;
             regex_given = true;
             break;
+        case 1010:
+        case 1011:
+            cut_list = optarg;
+            cut_mode = opt == 1010 ? FCX_CUT_FIELDS : FCX_CUT_BYTES;
+            cuts++;
+            break;
+        case 1012:
+            if (!fcx_cli::parse_delim(optarg, &sep)) return usage();
+            sep_given = true;
+            break;
+        case 1013: complement = true; break;
         default: return usage();
         }
     }
     if (file_in.empty() || ngpus < 1) return usage();
+    // the cut: LIST is compiled here, by the command line's own copy of the compiler (the no-device path reads it)
+    fcx_cut host_cut;
+    if (cuts > 1 || ((sep_given || complement) && !cuts) || (sep_given && cut_mode == FCX_CUT_BYTES)) return usage();
+    if (cuts) {
+        if (compress || want.range || want.list || compare || verify || test || finds || !find_set.empty() || count_lines || line_numbers ||
+            !repair.empty() || !digest.empty())
+            return usage();
+        const std::string why = fcx::cut_compile(&host_cut, cut_list.data(), (uint32_t)cut_list.size(), cut_mode, sep, delim,
+                                                 complement ? FCX_CUT_COMPLEMENT : 0u);
+        if (!why.empty()) {
+            fprintf(stderr, "--cut-%s: %s\n", cut_mode == FCX_CUT_FIELDS ? "fields" : "bytes", why.c_str());
+            return usage();
+        }
+    }
+    CutJob cut_job{&host_cut, cut_list};
     // --grep-regex: a grep of its own kind; the expression is compiled once the delimiter is known
     std::unique_ptr<fcx_regex, void (*)(fcx_regex *)> regex_own(nullptr, fcx_regex_destroy);
     std::unique_ptr<fcx_regex> host_regex;
@@ -1201,7 +1365,7 @@ int main(int argc, char **argv) {
     if (!repair.empty() && (want.range || want.list)) return usage();
     if (!digest.empty() && (want.range || want.list)) return usage();
     if (test && (digest.empty() || compress || compare || want.range || want.list)) return usage();
-    if (finds > 1 || greps > 1 || (count_only && !finds && !greps)) return usage();
+    if (finds > 1 || greps > 1 || (count_only && !finds && !greps && !cuts) || (cuts && greps && lines)) return usage();
     if (greps && (compress || want.range || want.list || compare || verify || test || finds || count_lines || lines || line_numbers ||
                   !repair.empty() || !digest.empty() || fcx_cli::pattern_holds(grep_pattern, delim)))
         return usage();
@@ -1210,7 +1374,7 @@ int main(int argc, char **argv) {
                                    !digest.empty() || (count_lines && lines)))
         return usage();
     if (line_numbers && (!finds || count_only)) return usage();
-    if (delim_given && !(count_lines || lines || line_numbers || greps)) return usage();
+    if (delim_given && !(count_lines || lines || line_numbers || greps || cuts)) return usage();
     if (block == 0 || block > FCX_MAX_BLOCK_BYTES) {
         fprintf(stderr, "block size must be in [1, %u]\n", FCX_MAX_BLOCK_BYTES);
         return -1;
@@ -1218,7 +1382,7 @@ int main(int argc, char **argv) {
     FILE *fin = fopen(file_in.c_str(), "rb");
     if (!fin) { printf("open: %s Fail!!\n", file_in.c_str()); return -1; }
     // (--list, --compare, --test, --find, --count-lines and --grep --count write no file)
-    const bool no_out = want.list || compare || test || finds || count_lines || (greps && count_only);
+    const bool no_out = want.list || compare || test || finds || count_lines || ((greps || cuts) && count_only);
     FILE *fout = no_out ? nullptr : fopen(file_out.c_str(), "wb");
     if (!fout && !no_out) { printf("open: %s Fail!!\n", file_out.c_str()); fclose(fin); return -1; }
     if (!compress) (void)hipSetDevice(device);   // the FCX8 decoder runs on the current device
@@ -1226,6 +1390,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "fcx: no HIP device %d\n", device);
         return -1;
     }
+    // behind a grep or --lines: those paths cut what they select, no `--` line between blocks
+    const CutJob *job = cuts && (greps || lines) ? &cut_job : nullptr;
     if (finds) {
         const int r = pset           ? do_find_set(fin, device, pset, *host_set, count_only)
                       : line_numbers ? do_find_numbered(fin, device, pattern, delim)
@@ -1234,16 +1400,22 @@ int main(int argc, char **argv) {
         return r;
     }
     if (greps) {
-        const int r = regex_given ? do_grep_regex(fin, fout, device, regex_own.get(), *host_regex, gopts, blocks)
-                      : blocks ? do_grep_blocks(fin, fout, device, pset, *host_set, delim, gopts)
-                      : pset ? do_grep_set(fin, fout, device, pset, *host_set, delim)
-                             : do_grep(fin, fout, device, grep_pattern, delim);
+        const int r = regex_given ? do_grep_regex(fin, fout, device, regex_own.get(), *host_regex, gopts, blocks, job)
+                      : blocks ? do_grep_blocks(fin, fout, device, pset, *host_set, delim, gopts, job)
+                      : pset ? do_grep_set(fin, fout, device, pset, *host_set, delim, job)
+                             : do_grep(fin, fout, device, grep_pattern, delim, job);
+        fclose(fin);
+        if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
+        return r;
+    }
+    if (cuts && !job) {
+        const int r = do_cut(fin, fout, device, host_cut, cut_list);
         fclose(fin);
         if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;
     }
     if (count_lines || lines) {
-        const int r = do_lines(fin, fout, device, delim, line_first, line_count);
+        const int r = do_lines(fin, fout, device, delim, line_first, line_count, job);
         fclose(fin);
         if (fout && fclose(fout) != 0) { fprintf(stderr, "write error\n"); return -1; }
         return r;

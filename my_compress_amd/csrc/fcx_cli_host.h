@@ -4,7 +4,7 @@
 // only (stdio and fcx_decompress_block), so it also builds into stand-alone programs
 // (tools/range_host_check.cpp, tools/compare_host_check.cpp, tools/repair_host_check.cpp, tools/digest_host_check.cpp,
 // tools/find_host_check.cpp, tools/lines_host_check.cpp, tools/grep_host_check.cpp, tools/set_host_check.cpp, tools/context_host_check.cpp,
-// tools/regex_host_check.cpp).
+// tools/regex_host_check.cpp), and --cut-fields / --cut-bytes (tools/cut_host_check.cpp).
 #ifndef FCX_CLI_HOST_H
 #define FCX_CLI_HOST_H
 
@@ -17,6 +17,7 @@
 
 #include "fcx.h"
 #include "fcx_crc32.h"
+#include "fcx_cut.h"
 #include "fcx_digest_file.h"
 #include "fcx_patset.h"
 #include "fcx_regex.h"
@@ -566,6 +567,38 @@ inline int host_find_numbered(FILE *fin, uint16_t nblocks, const uint8_t *pat, u
     return find_totals(hits, pos);
 }
 
+// ---- --cut-fields / --cut-bytes: the printout, the same on the GPU and on the host ----
+// stats: the FCX_CUT_STATS values
+inline int cut_totals(const uint64_t *stats) {
+    printf("cut: %llu bytes, %llu delimiters, %llu separators (%llu kept), decoded bytes = %llu\n", (unsigned long long)stats[0],
+           (unsigned long long)stats[2], (unsigned long long)stats[3], (unsigned long long)stats[4], (unsigned long long)stats[1]);
+    return 0;
+}
+
+// The cut without a device: every FCX7 record through the host decoder and the rule of fcx_cut.h, the open line's tick
+// count carried across the records; the kept bytes to fout (null: --count).  stats (FCX_CUT_STATS values, may be null;
+// groups: the records).
+inline int host_cut(FILE *fin, uint16_t nblocks, const fcx_cut &cut, FILE *fout, uint64_t *stats) {
+    uint64_t s[FCX_CUT_STATS] = {};
+    uint32_t ticks = 0;
+    bool io_ok = true;
+    std::string kept;
+    const int r = host_each_record(fin, nblocks, [&](uint32_t, uint32_t, const uint8_t *plain, uint64_t n) {
+        kept.clear();
+        fcx::cut_host_bytes(cut, plain, n, &ticks, fout ? &kept : nullptr, s);
+        s[5]++;
+        if (fout && !kept.empty()) io_ok = fwrite(kept.data(), 1, kept.size(), fout) == kept.size();
+        return io_ok;
+    });
+    if (r) return r;
+    if (!io_ok) {
+        fprintf(stderr, "write error\n");
+        return -1;
+    }
+    if (stats) memcpy(stats, s, sizeof(s));
+    return cut_totals(s);
+}
+
 // ---- --grep / --grep-hex: the printout, the same on the GPU and on the host ----
 inline int grep_totals(uint64_t lines, uint64_t bytes, uint64_t hits, uint64_t decoded) {
     printf("grep: %llu lines, %llu bytes, %llu hits, decoded bytes = %llu\n", (unsigned long long)lines, (unsigned long long)bytes,
@@ -799,12 +832,13 @@ inline const char *block_separator(const fcx_grep_opts &o) { return o.before || 
 // after-context of opts.after lines; a line that is neither waits, the last opts.before of them at most.  A line
 // written behind a line that was dropped starts a block: block_separator() goes in front of every block but the first.
 // stats (6 values, may be null): blocks, lines, base lines, bytes, hits, decoded bytes; counts as host_find_set's.
+// separators false: no line between blocks (a caller that cuts the blocks' bytes: the `--` line is not a byte of the file).
 inline int host_grep_blocks(FILE *fin, uint16_t nblocks, uint8_t delim, const fcx_pattern_set &S, const fcx_grep_opts &opts, FILE *fout,
-                            uint64_t *stats, uint64_t *counts) {
+                            uint64_t *stats, uint64_t *counts, bool separators = true) {
     std::vector<uint8_t> line, folded;       // the open line so far
     std::vector<std::vector<uint8_t>> wait;  // the unselected lines right in front of the open one, opts.before at most
     std::vector<uint64_t> per(S.npat, 0);
-    const std::string sep = block_separator(opts);
+    const std::string sep = separators ? block_separator(opts) : "";
     const bool invert = (opts.flags & FCX_GREP_INVERT) != 0;
     uint64_t pos = 0, blocks = 0, lines = 0, base = 0, bytes = 0, hits = 0, after_left = 0;
     uint64_t dropped = 0;   // lines since the last written one that no longer wait: a line written behind them starts a block
@@ -884,12 +918,13 @@ inline int host_grep_blocks(FILE *fin, uint16_t nblocks, uint8_t delim, const fc
 // closed line in the place of the set's compare; the delimiter is the regex's.  A position is a hit when the state
 // behind its byte is in acc, or in acc_eol with the delimiter or the line's end behind it.  `blocks`: the options were
 // given, so the totals are the context grep's (and block_separator() goes between blocks); otherwise the set grep's
-// with one pattern.  stats (6 values, may be null): blocks, lines, base lines, bytes, hits, decoded bytes.
+// with one pattern.  stats (6 values, may be null): blocks, lines, base lines, bytes, hits, decoded bytes.  separators: as
+// host_grep_blocks'.
 inline int host_grep_regex(FILE *fin, uint16_t nblocks, const fcx_regex &R, const fcx_grep_opts &opts, bool blocks_form, FILE *fout,
-                           uint64_t *stats) {
+                           uint64_t *stats, bool separators = true) {
     std::vector<uint8_t> line;               // the open line so far
     std::vector<std::vector<uint8_t>> wait;  // the unselected lines right in front of the open one, opts.before at most
-    const std::string sep = block_separator(opts);
+    const std::string sep = separators ? block_separator(opts) : "";
     const bool invert = (opts.flags & FCX_GREP_INVERT) != 0;
     const uint8_t delim = R.delim;
     uint64_t pos = 0, blocks = 0, lines = 0, base = 0, bytes = 0, hits = 0, after_left = 0;

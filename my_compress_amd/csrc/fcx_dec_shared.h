@@ -878,6 +878,44 @@ struct RegexScratch {
     uint64_t stats[FCX_REGEX_SCAN_STATS] = {};
 };
 
+// ---- cut (fcx_cut.hip).  Status words of a cut (fcx_dctx's ct.words, u64 each; host_words mirrors
+// them): what travels from group to group is in them ----
+constexpr uint32_t kKwOut = 0;         // output bytes of the call so far: advanced by k_kbase, group by group
+constexpr uint32_t kKwGroupBase = 1;   // output bytes before the range cut last (k_kbase)
+constexpr uint32_t kKwJudged = 2;      // bytes judged (k_kmark)
+constexpr uint32_t kKwDelims = 3;      // delimiters seen
+constexpr uint32_t kKwSeps = 4;        // separators seen
+constexpr uint32_t kKwSepsKept = 5;    // ... and kept
+constexpr uint32_t kKwTicks = 6;       // the saturated tick count of the line open at the end of the range cut last (k_kentry)
+constexpr uint32_t kKwWords = 8;
+
+// the cut calls behind their argument checks (fcx_cut.hip): *out_len the output's total, stats the FCX_CUT_STATS
+// values (may be null); messages of cut_run number the records from rec_base.  cont: the run continues the text of
+// the cut_run calls before it (the stream form's groups of a longer file): the open line's ticks and the counters
+// go on from the context's words, the output starts at d_out[0] again and *out_len, stats[0] and stats[5] are this
+// run's alone.
+int cut_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const fcx_cut *cut, uint8_t *d_out,
+            uint64_t cap, uint64_t *out_len, uint64_t *stats, hipStream_t st, uint64_t rec_base, bool cont);
+int cut_ranges_run(fcx_dctx *c, char kind, const uint8_t *d_rec, uint64_t rec_len, uint32_t nblocks, const uint64_t *d_rec_off,
+                   const uint64_t *d_dec_off, const uint64_t *d_start, const uint64_t *d_end, uint64_t nranges, const fcx_cut *cut,
+                   uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *stats, hipStream_t st);
+
+// scratch of the cut calls (fcx_cut.hip)
+struct CutScratch {
+    DevBuf<uint32_t> sel;            // the cut's selection table (fcx_cut.h)
+    DevBuf<uint16_t> keep_bits;      // per tile of 4096 bytes 512 B of keep bits, in hit_bits' layout
+    DevBuf<uint32_t> tile_sum;       // per tile its summary: bit 31 it holds a delimiter, the ticks behind the last (or all)
+    DevBuf<uint32_t> tile_entry;     // per tile the open line's ticks at its first byte
+    DevBuf<uint32_t> tile_count;     // per tile its kept bytes, and ...
+    DevBuf<uint32_t> tile_base;      // ... those of the range's tiles before it
+    DevBuf<uint64_t> words;          // kKw*
+    PinnedBuf<uint64_t> host_words;
+    DevBuf<uint8_t> gathered;        // the ranges form: the concatenation of the ranges' bytes
+    DevBuf<uint8_t> out;             // the host form's output
+    uint64_t scratch_bytes = 0;      // device bytes the last call reserved beside the decoded group
+    uint64_t stats[FCX_CUT_STATS] = {};
+};
+
 // FCX7 scratch (fcx_dec.hip): per block, dropped as a whole when a call has more blocks ...
 struct Dec7Blocks {
     uint32_t cap_blocks = 0;
@@ -916,6 +954,7 @@ struct fcx_dctx {
     fcx::SetScratch ps;
     fcx::ContextScratch cx;
     fcx::RegexScratch rx;
+    fcx::CutScratch ct;
     // the last call's stages: FCX7 read on the first fcx_dctx_stage query, FCX8 summed over its batches
     fcx::StageTimes times{fcx::kD78Stages};
 };

@@ -438,6 +438,32 @@ int fcx_decompress_ranges_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, 
     return fetch_out(c, out, *out_len);
 }
 
+// fcx_decompress_ranges_host with the cut behind the gather: only the cut bytes come back
+int fcx_cut_ranges_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, const uint64_t *starts, const uint64_t *ends, uint64_t nranges,
+                        const fcx_cut *cut, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *stats) {
+    if (!c || !in || !cut || !out_len || (nranges && (!starts || !ends)) || (cap && !out))
+        return fail(FCX_ERR_ARG, "fcx_cut_ranges_host: NULL argument");
+    char kind = 0;
+    uint32_t nblocks = 0;
+    uint64_t rec_len = 0;
+    FCX_TRY(walk_file(in, in_len, &kind, &nblocks, &rec_len));
+    *out_len = 0;
+    for (int i = 0; i < FCX_CUT_STATS && stats; i++) stats[i] = 0;
+    if (nranges == 0) return cut_ranges_run(c, kind, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, cut, nullptr, 0, out_len, stats, nullptr);
+    RangesScratch &Q = c->rq;
+    FCX_TRY(stage_file(c, in, rec_len));
+    FCX_TRY(Q.starts.reserve(8 * nranges, "ranges"));
+    FCX_TRY(Q.ends.reserve(8 * nranges, "ranges"));
+    FCX_TRY(c->ct.out.reserve(cap, "cut output"));
+    FCX_HIP(hipMemcpy(Q.starts, starts, 8 * nranges, hipMemcpyHostToDevice));
+    FCX_HIP(hipMemcpy(Q.ends, ends, 8 * nranges, hipMemcpyHostToDevice));
+    FCX_TRY(cut_ranges_run(c, kind, Q.file, rec_len, nblocks, nullptr, nullptr, Q.starts, Q.ends, nranges, cut,
+                           cap ? (uint8_t *)c->ct.out : nullptr, cap, out_len, stats, nullptr));
+    if (*out_len > cap) return fail(FCX_ERR_CAPACITY, "fcx_cut_ranges_host: output capacity too small");
+    if (*out_len) FCX_HIP(hipMemcpy(out, c->ct.out, *out_len, hipMemcpyDeviceToHost));
+    return FCX_OK;
+}
+
 int fcx_grep_host(fcx_dctx *c, const uint8_t *in, uint64_t in_len, uint8_t delim, const uint8_t *pattern, uint32_t plen, uint8_t *out,
                   uint64_t cap, uint64_t *out_len, uint64_t *stats) {
     if (!c || !in || !pattern || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_grep_host: NULL argument");

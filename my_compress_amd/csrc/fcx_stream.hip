@@ -1098,6 +1098,61 @@ int fcx_grep_regex_blocks_stream(fcx_dctx *dctx, fcx_read_fn rd, void *user, uin
     return FCX_OK;
 }
 
+// ---- cut (include/fcx.h): fcx_decompress_stream's twin.  The file is one text: the open line's ticks and
+// the counters stay in the context's words from group to group, each group's kept bytes go through `wr` ----
+int fcx_cut_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in, const fcx_cut *cut, uint64_t *stats) {
+    if (!dctx || !rd || !cut) return fail(FCX_ERR_ARG, "fcx_cut_stream: NULL argument");
+    uint64_t tout = 0, groups = 0, gs[FCX_CUT_STATS] = {};
+    const int r = stream_groups(dctx, rd, user, max_in, nullptr, nullptr,
+                                [&](bool lz78, Slot &x, uint64_t used, uint32_t nb, uint64_t out_cap, uint64_t before, hipStream_t st) -> int {
+        uint64_t got = 0;
+        // (the output is a subsequence of the group's decoded bytes, which the staging holds)
+        FCX_TRY(fcx::cut_run(dctx, lz78 ? '8' : '7', x.din, used, nb, cut, wr ? (uint8_t *)x.dout : nullptr, wr ? out_cap : 0, &got, gs, st,
+                             before, before != 0));
+        groups += gs[5];
+        if (!wr || got == 0) {
+            tout += got;
+            return FCX_OK;
+        }
+        return write_group(x, got, wr, user, st, &tout);
+    });
+    if (r) return r;
+    gs[0] = tout;
+    gs[5] = groups;
+    for (int i = 0; i < FCX_CUT_STATS; i++) dctx->ct.stats[i] = gs[i];
+    for (int i = 0; i < FCX_CUT_STATS && stats; i++) stats[i] = gs[i];
+    return FCX_OK;
+}
+
+int fcx_cut_host(fcx_dctx *dctx, const uint8_t *in, uint64_t in_len, const fcx_cut *cut, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                 uint64_t *stats) {
+    if (!dctx || !in || !cut || !out_len || (cap && !out)) return fail(FCX_ERR_ARG, "fcx_cut_host: NULL argument");
+    if (in_len < FCX_HEADER_BYTES || memcmp(in, "FCX", 3) != 0) return fail(FCX_ERR_FORMAT, "not an FCX stream");
+    *out_len = 0;
+    // what fits is stored, the rest counted: the total is known when the file ends
+    struct Take {
+        uint8_t *out;
+        uint64_t cap, n;
+    } take{out, cap, 0};
+    struct Both {
+        MemIO comp;
+        Take *take;
+    } io{{in, in_len, 0, nullptr, 0, 0}, &take};
+    const fcx_read_fn rd = [](void *u, uint8_t *buf, uint64_t n) { return mem_read(&((Both *)u)->comp, buf, n); };
+    const fcx_write_fn wr = [](void *u, const uint8_t *buf, uint64_t n) {
+        Take *k = ((Both *)u)->take;
+        if (k->n < k->cap) par_memcpy(k->out + k->n, buf, std::min(n, k->cap - k->n));
+        k->n += n;
+        return 0;
+    };
+    uint64_t gs[FCX_CUT_STATS] = {};
+    FCX_TRY(fcx_cut_stream(dctx, rd, cap ? wr : nullptr, &io, in_len - FCX_HEADER_BYTES, cut, gs));
+    for (int i = 0; i < FCX_CUT_STATS && stats; i++) stats[i] = gs[i];
+    *out_len = gs[0];
+    if (gs[0] > cap) return fail(FCX_ERR_CAPACITY, "fcx_cut_host: output capacity too small");
+    return FCX_OK;
+}
+
 int fcx_decompress_ranges_stream(fcx_dctx *dctx, fcx_read_fn rd, fcx_write_fn wr, void *user, uint64_t max_in,
                                  const uint64_t *starts, const uint64_t *ends, uint64_t n, uint64_t *out_len) {
     if (!dctx || !rd || !wr || (n && (!starts || !ends))) return fail(FCX_ERR_ARG, "fcx_decompress_ranges_stream: NULL argument");
